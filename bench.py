@@ -12,7 +12,12 @@ run on top are timed as separate legs and reported under "exchange": the consens
 K^2 + 1 reals per pass, consumed by the next passes through eea_batch_io::d_ck_shared) and the all-gather of
 every agent's c_k that north_star names.
 
-  python bench.py                                  # 1 GPU
+A plain run times the headline leg only and prints its line.  Every other leg (the single-launch form of the headline,
+the other BASELINE configs, latency / tick legs, phi_k, exchange, grid tile, CPU baseline) runs only with `--full`.
+`--dump-outputs DIR` writes what the headline leg's last step left for its caller (u0, ut) as DIR/<name>.npy.
+
+  python bench.py                                  # 1 GPU, headline leg only
+  python bench.py --full                           # every leg
   python bench.py --gpus N --steps K --warmup W    # starts its N ranks itself (one child process per GPU)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W      # what the driver runs for N > 1
@@ -33,6 +38,7 @@ import bench_line  # noqa: E402 -- the compact driver line + bench_detail.json
 
 SPINUP_PASSES = int(os.environ.get("EEA_BENCH_SPINUP_PASSES", "1000"))  # untimed passes before the warm-up steps (clock ramp)
 PARITY_TOL = {"f64": {"ck_phik": 1e-11, "traj_rho_u": 1e-9}, "f32": {"u": 1e-4, "rho": 5e-4}}
+DUMP_LIMIT_BYTES = 64 * 10**6   # --dump-outputs: all files of one run together
 
 
 def parse():
@@ -40,6 +46,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg (single-launch form, other configs, latency / tick, phi_k, exchange, grid tile, CPU "
+                         "baseline) after the headline leg; without it only the headline leg runs (the --no-* options below "
+                         "select among the legs of a --full run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline leg's last step left for its caller (u0 [B][3], ut [B][T][3]) as DIR/<name>.npy, "
+                         "in the run's precision; at most 64 MB in all (a fixed, seeded sample of agents beyond that)")
     ap.add_argument("--passes-per-step", type=int, default=16000,
                     help="consecutive control passes per timed step (receding horizon); the default keeps the GPU "
                          "busy for >= 2 s over the driver's --steps 20")
@@ -95,6 +108,27 @@ def free_port():
     return port
 
 
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array of `arrays` (name -> float32 / float64 numpy array, agents along axis 0) as
+    path/<name>.npy.  Smallest first; an array that would take the total past `limit` keeps a fixed, seeded sample of
+    its rows (sorted), and their indices go to path/<name>_rows.npy (float64)"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    budget = limit - 256 * 2 * len(arrays)   # room for the .npy headers
+    for name, a in sorted(arrays.items(), key=lambda kv: kv[1].nbytes):
+        a = np.ascontiguousarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if a.nbytes > budget:
+            row = a.nbytes // a.shape[0]
+            keep = max(0, min(a.shape[0], budget // (row + 8)))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            a = a[rows]
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+            budget -= rows.size * 8
+        np.save(os.path.join(path, name + ".npy"), a)
+        budget -= a.nbytes
+
+
 def self_launch(args):
     """`python bench.py --gpus N` with no launcher around it: this process has made NO GPU call (torch is not
     even imported); it starts the N ranks as children of torch.distributed.run, forwards their output (rank 0
@@ -114,7 +148,7 @@ from bench_legs import (HBM_PEAK_GBS, MAP_BOUNDS, MEANS, SIGMAS, VALU_F32_PEAK_T
 def dry_run(args):
     """EEA_BENCH_DRYRUN=1: the launch plumbing without a GPU (CPU test of `--gpus N`): the ranks rendezvous over
     gloo, take the max over ranks of a dummy time like the real legs do, run the grid-tile leg's partition + collective
-    on a small grid (numpy in place of the device kernel), and rank 0 prints one JSON line."""
+    on a small grid (numpy in place of the device kernel; --full only, like the real leg), and rank 0 prints one JSON line."""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -129,7 +163,7 @@ def dry_run(args):
         t = torch.tensor([float(rank + 1)], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         assert int(t.item()) == world
-    if not args.no_grid_tile:
+    if args.full and not args.no_grid_tile:
         # the grid-tile leg's structure: rows [row0, row0 + nrows) per rank -> K^2 un-normalised sums -> one all-reduce
         # -> divide by element 0; checked against the un-tiled sums of the same grid
         n, K, res = 48, 4, 0.1
@@ -564,9 +598,14 @@ def main():
         return elapsed, pass_ms, enqueue_s
 
     elapsed, pass_ms, enqueue_s = timed("shard", args.steps, args.warmup)
+    if args.dump_outputs:
+        # what the last timed step left for the caller, before any later leg overwrites the buffers
+        names = ("u0", "ut") if world == 1 else ("rank%d_u0" % rank, "rank%d_ut" % rank)
+        dump_outputs(args.dump_outputs, dict(zip(names, (d_u0.cpu().numpy(), d_ut.cpu().numpy()))),
+                     limit=DUMP_LIMIT_BYTES // world)
     # the same passes as one launch per pass (short: 3 x 400 passes), device work contiguous with the headline leg
     single_pass_ms = pass_ms
-    if SPL > 1 and not args.no_single_launch:
+    if args.full and SPL > 1 and not args.no_single_launch:
         _, single_pass_ms, single_enqueue_s = timed("shard1", 3, 1, passes=400)
 
     out = None
@@ -679,9 +718,6 @@ def main():
             "per_rank": {"timed_region_s": per_rank_s.get("shard"),
                          "values": [B * R * args.steps / t for t in per_rank_s.get("shard", [])]},
             "spinup_passes": SPINUP_PASSES,
-            "single_launch_per_pass": {"ms_per_pass": single_pass_ms, "frac": tflops / vpeak * pass_ms / single_pass_ms,
-                                       "note": "the same passes as ONE launch per pass and agent group (eea_control_batch; "
-                                               "what rounds 1-3 reported), 3 x 400 passes right after the headline leg"},
             "host_enqueue_us_per_pass": 1e6 * enqueue_s / (args.steps * R),
             "parity_tol": PARITY_TOL[args.precision],
             "roofline": {"bound": "valu-%s" % args.precision,
@@ -709,12 +745,17 @@ def main():
                                      "HBM actually saw.  Either way the kernel is nowhere near the HBM roofline: north_star asks for the "
                                      "figure"},
         }
-        if world == 1 and not args.no_other_configs and not args.n_mem:
+        if args.full:
+            out["single_launch_per_pass"] = {
+                "ms_per_pass": single_pass_ms, "frac": tflops / vpeak * pass_ms / single_pass_ms,
+                "note": "the same passes as ONE launch per pass and agent group (eea_control_batch; "
+                        "what rounds 1-3 reported), 3 x 400 passes right after the headline leg"}
+        if args.full and world == 1 and not args.no_other_configs and not args.n_mem:
             try:
                 out["other_configs"] = other_config_legs(args, torch, capi, np, SPL)
             except Exception as exc:  # the headline line must not die with a secondary leg
                 out["other_configs"] = {"error": repr(exc)}
-        if world == 1 and not args.no_latency:
+        if args.full and world == 1 and not args.no_latency:
             x = poses[0].astype(np.float64)
             for _ in range(20):
                 eng.control(MAP_BOUNDS, x)
@@ -736,12 +777,12 @@ def main():
                     "cpp_host": cpp_tick_latency()}
             except Exception as exc:  # noqa: BLE001 -- the headline line must not die with a secondary leg
                 out["single_robot_tick"] = {"error": repr(exc)}
-        if world == 1 and not args.no_latency and not f32:
+        if args.full and world == 1 and not args.no_latency and not f32:
             try:
                 out.update(tick_legs(torch, capi, np))
             except Exception as exc:  # noqa: BLE001 -- the headline line must not die with a secondary leg
                 out["fleet_tick"] = {"error": repr(exc)}
-        if world == 1 and not args.no_phik and not f32:
+        if args.full and world == 1 and not args.no_phik and not f32:
             try:
                 out.update(phik_legs(args, torch, capi, np))
             except Exception as exc:  # the headline line must not die with a secondary leg
@@ -837,7 +878,7 @@ def main():
     # ---- exchange legs: last, and under a watchdog.  They are the only part of this program that has never run on
     # more than one GPU; if a collective never returns, every rank gives up after the timeout, rank 0 still prints
     # the line (with the reason in "exchange") and the processes exit without waiting for the library
-    if not args.no_exchange:
+    if args.full and not args.no_exchange:
         limit = float(os.environ.get("EEA_BENCH_EXCHANGE_TIMEOUT", "300"))
         finished = threading.Event()
         gave_up = threading.Event()
@@ -923,7 +964,7 @@ def main():
         finished.set()
         if rank == 0:
             out["exchange"] = exchange
-    elif world == 1 and not args.no_grid_tile and not f32:
+    elif args.full and world == 1 and not args.no_grid_tile and not f32:
         try:
             out["grid_tile"] = grid_tile_leg()
         except Exception as exc:  # noqa: BLE001
@@ -936,7 +977,7 @@ def main():
     if use_dist:
         dist.destroy_process_group()
     # the CPU baseline LAST: every device leg above ran back to back (the driver samples GPU activity every few seconds)
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         one, allc = cpu_baseline(args, args.cpu_seconds)
         out["cpu_baseline"] = one
         out["cpu_baseline_all_cores"] = allc

@@ -700,7 +700,7 @@ def test_bench_self_launches_its_ranks(extra, tmp_path):
     env = dict(os.environ, EEA_BENCH_DETAIL_DIR=str(tmp_path))
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full",
            "--passes-per-step", "3", "--exchange-passes-per-step", "3", "--agents", "256"] + extra
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
@@ -748,7 +748,7 @@ def test_bench_headline_survives_a_stuck_exchange(gpus):
     env = dict(os.environ, EEA_BENCH_EXCHANGE_TIMEOUT="0.001")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1", "--full",
            "--passes-per-step", "3", "--exchange-passes-per-step", "3", "--agents", "256", "--cpu-seconds", "0",
            "--no-latency", "--no-phik"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)

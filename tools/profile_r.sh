@@ -12,7 +12,7 @@ LEGS="--cpu-seconds 0 --no-latency --no-exchange --no-phik --no-grid-tile --no-o
 #    (steps per launch as the default: 50; pass --steps-per-launch 1 for the one-launch-per-pass shape)
 #    tools/summarize_prof.py takes the average over the dispatches of the TIMED region only (the last steps x passes x
 #    groups control dispatches) and compares it with the ms_per_pass the same run printed
-TRACE_BENCH="python3 bench.py --steps 3 --warmup 1 --passes-per-step 2000 $LEGS $*"
+TRACE_BENCH="python3 bench.py --full --steps 3 --warmup 1 --passes-per-step 2000 $LEGS $*"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o trace -- $TRACE_BENCH > "$OUT/trace.log" 2>&1
 # 2) PMC passes, each in its own run (FETCH_SIZE and WRITE_SIZE do not fit one pass); counter collection serialises
 #    the dispatches, so these runs are short and skip the spin-up

@@ -11,7 +11,7 @@ set -u
 OUT=gpurun_out/r04_evidence
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
-python3 bench.py --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"
+python3 bench.py --full --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"
 bash tools/profile_r.sh r04_spl50 > /dev/null 2>&1
 bash tools/profile_r.sh r04_spl1 --steps-per-launch 1 > /dev/null 2>&1
 for g in spl50 spl1; do
@@ -57,5 +57,5 @@ for impl, name, per in ((0, "per-axis factors (default): ONE launch", (1, 1, 1))
                   ";  ".join("%s avg %.2f us" % (k, sum(v) / len(v) * 1e-3) for k, v in by.items()))
 PY
 python3 tools/make_r04_profiles.py > /dev/null 2>&1
-python3 bench.py --steps 20 --warmup 5 > "$OUT/bench_final.json" 2> "$OUT/bench_final.err"
+python3 bench.py --full --steps 20 --warmup 5 > "$OUT/bench_final.json" 2> "$OUT/bench_final.err"
 ls -la "$OUT"

@@ -12,7 +12,7 @@ set -u
 OUT=gpurun_out/r06_evidence
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
-python3 bench.py --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"
+python3 bench.py --full --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"
 bash tools/profile_r.sh r06_spl50 > /dev/null 2>&1
 bash tools/profile_r.sh r06_spl1 --steps-per-launch 1 > /dev/null 2>&1
 for g in spl50 spl1; do
@@ -31,6 +31,6 @@ PHIK_CASES=16384:10:f64 bash tools/phik_pmc.sh > "$OUT/phik_pmc.txt" 2>&1
 python3 tools/parity_report.py > "$OUT/parity_report.txt" 2>&1
 EEA_PRINT_WORST=1 python3 -m pytest tests/test_analytic_checks.py -m gpu -q -s 2>&1 | grep -E "digits|closed-form|passed|failed" > "$OUT/analytic_checks.txt"
 python3 tools/make_r06_profiles.py > /dev/null 2>&1
-python3 bench.py --steps 20 --warmup 5 > "$OUT/bench_final.json" 2> "$OUT/bench_final.err"
+python3 bench.py --full --steps 20 --warmup 5 > "$OUT/bench_final.json" 2> "$OUT/bench_final.err"
 cp bench_detail.json "$OUT/bench_detail.json"
 python3 tools/make_r06_profiles.py > "$OUT/make_profiles.log" 2>&1
