@@ -513,8 +513,8 @@ struct eea_consensus_plan
   int device = 0;
   unsigned n_groups = 0, lag = 0, slots = 0, passes = 0, B = 0, rec_len = 0;
   size_t rs = 8;
-  std::vector<unsigned> agents, first, rec_first;  // per group: agents, first agent, first record of a pass
-  unsigned n_rec = 0;                               // records per pass (<= B)
+  std::vector<unsigned> agents, first, records;  // per group: agents, first agent, sum records of its launch
+  unsigned n_rec = 0;                             // records per pass (<= B)
   std::vector<eea_batch_io> io;
   std::vector<hipStream_t> gstreams;
   hipStream_t xs = nullptr;
@@ -577,21 +577,34 @@ eea_status plan_enqueue(eea_consensus_plan* p)
   for (unsigned g = 0; g < p->n_groups; ++g) EEA_HIP(hipStreamWaitEvent(p->gstreams[g], p->ev_fork, 0));
   for (unsigned i = 0; i < p->passes; ++i) {
     const unsigned slot = i % p->slots, src = (i + p->slots - p->lag) % p->slots;
+    // the groups' records follow each other in the slot: one record per wavefront where agents share one
+    // (eea_batch_io::rec_per_wavefront), as many as the launch actually made -- pass 0 sets the layout, every later pass
+    // must launch the same forms
+    unsigned rec = 0;
     for (unsigned g = 0; g < p->n_groups; ++g) {
       // the sum record this pass consumes is complete: the exchange of pass i - lag (of the launch before for i < lag --
       // ordered by the device's serialisation of the launches, no captured dependency)
       if (i >= p->lag) EEA_HIP(hipStreamWaitEvent(p->gstreams[g], p->ev_x[src], 0));
       eea_batch_io io = p->io[g];
-      // (one record per wavefront where agents share one, eea_batch_io::rec_per_wavefront: rec_first / n_rec count records)
-      io.d_ck_rec = arec + (static_cast<size_t>(slot) * p->B + p->rec_first[g]) * rec_bytes;
+      io.d_ck_rec = arec + (static_cast<size_t>(slot) * p->B + rec) * rec_bytes;
       io.rec_per_wavefront = 1;
       io.d_ck_shared = sum + static_cast<size_t>(src) * rec_bytes;
       io.ck_shared_parts = 1;
-      const eea_status st = eea_control_batch(p->e, p->agents[g], &io, p->gstreams[g]);
+      eea::ControlForm form;
+      const eea_status st = eea::control_batch(p->e, p->agents[g], &io, p->gstreams[g], &form);
       if (st != EEA_OK) return st;
+      const unsigned n = form.records(p->agents[g]);
+      if (i == 0) {
+        p->records.push_back(n);
+      } else if (n != p->records[g]) {
+        return fail(EEA_ERR_UNSUPPORTED, "an agent group changed its control kernel during the capture (EEA_OPT_CONTROL_KERNEL / "
+                                         "EEA_OPT_AGENT_LANES set meanwhile)");
+      }
+      rec += n;
       EEA_HIP(hipEventRecord(p->ev_group[g], p->gstreams[g]));
       EEA_HIP(hipStreamWaitEvent(p->xs, p->ev_group[g], 0));
     }
+    if (i == 0) p->n_rec = rec;
     void* const s_slot = sum + static_cast<size_t>(slot) * rec_bytes;
     eea_status st = eea_ck_records_sum_ws(p->e, p->n_rec, arec + static_cast<size_t>(slot) * p->B * rec_bytes, s_slot,
                                           static_cast<char*>(p->d_ws) + static_cast<size_t>(slot) * p->ws_bytes,
@@ -640,8 +653,6 @@ eea_status eea_consensus_plan_create(eea_engine* e, eea_comm* c, const eea_conse
     p->first.push_back(p->B);
     p->agents.push_back(d->group_agents[g]);
     p->B += d->group_agents[g];
-    p->rec_first.push_back(p->n_rec);
-    p->n_rec += eea_batch_record_count(e, d->group_agents[g]);  // (= the group's agents for one agent per wavefront)
     eea_batch_io mine = io;  // the exchange fields are the plan's
     mine.d_ck_shared = nullptr;
     mine.d_ck_rec = nullptr;

@@ -125,10 +125,26 @@ template <typename R>
 hipError_t launch_control_resident(const ControlParams<R>& p, int model, int n_mem_max, void* d_mail, void* d_stage,
                                    unsigned first_seen, long long idle_ticks, hipStream_t stream);
 
+// The kernel that runs a control call, chosen in ONE place (engine.cpp control_form) for the launch, the resident form and
+// the record layout (eea_batch_record_count, the consensus plan): lanes per agent -- 0 = one workgroup per agent
+// (launch_control), 64 = one wavefront per agent (launch_control_wave), 8 / 16 / 32 = several agents per wavefront
+// (launch_control_pack).
+struct ControlForm
+{
+  int lanes;
+  // sum records a launch of B agents writes with eea_batch_io::rec_per_wavefront: one per wavefront where agents share one
+  unsigned records(unsigned B) const
+  {
+    if (lanes == 0 || lanes >= 64) return B;
+    const unsigned A = 64u / static_cast<unsigned>(lanes);
+    return (B + A - 1u) / A;
+  }
+};
+
 // Wavefront-per-agent control kernel (control_wave_impl.hpp): horizons of at most 256 steps, K <= 16 or K = 20.
 // launch_control_wave needs control_wave_eligible.
 template <typename R>
-bool control_wave_eligible(const ControlParams<R>& p, bool rollout_only);
+bool control_wave_eligible(const ControlParams<R>& p);
 template <typename R>
 hipError_t launch_control_wave(const ControlParams<R>& p, unsigned B, int model, bool rollout_only,
                                hipStream_t stream);
@@ -138,7 +154,7 @@ bool control_wave_resident_eligible(const ControlParams<double>& p);
 hipError_t launch_control_wave_resident(const ControlParams<double>& p, int model, hipStream_t stream);
 // Several agents per wavefront (control_pack_impl.hpp): groups of 8 / 16 / 32 lanes per agent, fp64, K = 5 / 10,
 // T <= 4 lanes.  control_pack_lanes: the group size for a batch of B agents (0 = one wavefront per agent); forced = the
-// value of EEA_OPT_AGENT_LANES
+// value of EEA_OPT_AGENT_LANES (read by control_form)
 bool control_pack_eligible(const ControlParams<double>& p, int lanes);
 int control_pack_lanes(const ControlParams<double>& p, unsigned B, int forced);
 hipError_t launch_control_pack(const ControlParams<double>& p, unsigned B, int model, bool rollout_only, int lanes,

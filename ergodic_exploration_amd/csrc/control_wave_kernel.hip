@@ -45,9 +45,8 @@ hipError_t launch_wave_k(const ControlParams<R>& p, unsigned B, bool rollout_onl
 }  // namespace
 
 template <typename R>
-bool control_wave_eligible(const ControlParams<R>& p, bool rollout_only)
+bool control_wave_eligible(const ControlParams<R>& p)
 {
-  (void)rollout_only;
   return p.T >= 1 && p.T <= wave::kMaxS * kWave && p.K >= 1 && (p.K <= 16 || p.K == 20);
 }
 
@@ -99,8 +98,8 @@ hipError_t launch_control_wave_resident(const ControlParams<double>& p, int mode
   return model == kModelOmni ? launch_resident_k<kModelOmni>(p, stream) : launch_resident_k<kModelSimpleCart>(p, stream);
 }
 
-template bool control_wave_eligible<double>(const ControlParams<double>&, bool);
-template bool control_wave_eligible<float>(const ControlParams<float>&, bool);
+template bool control_wave_eligible<double>(const ControlParams<double>&);
+template bool control_wave_eligible<float>(const ControlParams<float>&);
 template hipError_t launch_control_wave<double>(const ControlParams<double>&, unsigned, int, bool, hipStream_t);
 template hipError_t launch_control_wave<float>(const ControlParams<float>&, unsigned, int, bool, hipStream_t);
 }  // namespace eea

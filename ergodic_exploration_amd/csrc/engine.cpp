@@ -141,7 +141,6 @@ struct eea_engine
   size_t h_stage_cap = 0;
   double last_pose[3] = { 0, 0, 0 };
   int mail_seq = 0;          // sequence number of the last single-agent launch
-  int* mail_done = nullptr;  // set while eea_control fills the launch parameters
   unsigned long phik_gen = 0;  // bumped whenever phi_k / the domain changes
 
   // resident single-robot workgroup (EEA_OPT_RESIDENT_CONTROL): host-mapped mailbox + replay-memory buffer, its own stream
@@ -601,10 +600,42 @@ eea_status sum_workspace(eea_engine* e, const void* key, unsigned B, hipStream_t
   return EEA_OK;
 }
 
+// The kernel that runs a control call of B agents with these parameters (eea::ControlForm): the one place that reads
+// EEA_OPT_CONTROL_KERNEL and EEA_OPT_AGENT_LANES.  Three kernels ship: one wavefront per agent (horizons <= 256 steps,
+// K <= 16 or K = 20), several agents per wavefront (fp64 short horizons, when the batch still fills the chip) and one
+// workgroup per agent (everything else).  Batches take the wavefront kernels unless EEA_OPT_CONTROL_KERNEL says otherwise.
+// The single-agent call (eea_control and its resident form: one agent, latency) takes the wavefront for horizons of one
+// slot (T <= 64: one step per lane, no barrier -- 3.0 / 4.9 / 4.3 us of device time at configs[0] / configs[1] / the yaml's
+// T = 50 against 5.1 / 7.4 / 5.2 of the workgroup) and keeps four wavefronts per agent beyond (T = 200: 7.2 against 11.6 us;
+// profiles/r05_one_agent_kernels.txt)
 template <typename R>
-eea_status control_batch_impl(eea_engine* e, unsigned B, const eea_batch_io* io, bool rollout_only,
-                              hipStream_t s, long long* d_stamps = nullptr, unsigned n_steps = 1,
-                              unsigned pose_step_stride = 0, unsigned u0_step_stride = 0)
+eea::ControlForm control_form(const eea::ControlParams<R>& p, unsigned B, bool single_agent)
+{
+  if (eea::option(EEA_OPT_CONTROL_KERNEL) != 0) return { 0 };
+  if ((single_agent && p.T > 64) || !eea::control_wave_eligible<R>(p)) return { 0 };
+  if constexpr (sizeof(R) == 8) {
+    const int lanes = eea::control_pack_lanes(p, B, eea::option(EEA_OPT_AGENT_LANES));
+    if (lanes != 0) return { lanes };
+  }
+  return { 64 };
+}
+
+// the form of a batch call of B agents on this engine (eea_batch_agent_lanes, eea_batch_record_count)
+eea::ControlForm batch_form(const eea_engine* e, unsigned B)
+{
+  auto form = [e, B](auto p) {
+    fill_params(e, p);
+    return control_form(p, B, false);
+  };
+  return e->f32 ? form(eea::ControlParams<float>{}) : form(eea::ControlParams<double>{});
+}
+
+// One control launch of B agents in the form control_form picks, reported in *form when not null.  done: the single-agent
+// call's completion word (eea_control), null for batches.
+template <typename R>
+eea_status control_batch_impl(eea_engine* e, unsigned B, const eea_batch_io* io, bool rollout_only, hipStream_t s,
+                              eea::ControlForm* form = nullptr, int* done = nullptr, long long* d_stamps = nullptr,
+                              unsigned n_steps = 1, unsigned pose_step_stride = 0, unsigned u0_step_stride = 0)
 {
   eea::ControlParams<R> p;
   fill_params<R>(e, p);
@@ -632,27 +663,20 @@ eea_status control_batch_impl(eea_engine* e, unsigned B, const eea_batch_io* io,
   p.rhot = static_cast<R*>(io->d_rhot);
   p.status = io->d_status;
   p.skip = io->d_skip;
-  p.done = e->mail_done;
+  p.done = done;
   p.done_seq = e->mail_seq;
   const int n_mem_max = rollout_only ? 0 : static_cast<int>(p.mem_stride);
   p.dbg = d_stamps;  // phase stamps: null in the product (only the A/B library's kernels read it, tools/ab/)
-  // two kernels ship: one wavefront per agent (horizons <= 256 steps, K <= 16 or K = 20) and one workgroup per agent
-  // (everything else).  Batches take the throughput kernel unless EEA_OPT_CONTROL_KERNEL says otherwise.  The single-agent
-  // entry (eea_control: one agent, latency) takes it for horizons of one slot (T <= 64: one step per lane, no barrier --
-  // 3.0 / 4.9 / 4.3 us of device time at configs[0] / configs[1] / the yaml's T = 50 against 5.1 / 7.4 / 5.2 of the
-  // workgroup) and keeps four wavefronts per agent beyond (T = 200: 7.2 against 11.6 us; profiles/r05_one_agent_kernels.txt)
-  const bool use_wave = eea::option(EEA_OPT_CONTROL_KERNEL) == 0 && (e->mail_done == nullptr || p.T <= 64) &&
-                        eea::control_wave_eligible<R>(p, rollout_only);
   p.ck_rec = rollout_only ? nullptr : static_cast<R*>(io->d_ck_rec);
-  if (use_wave) {
-    // short horizons: several agents share a wavefront (control_pack_impl.hpp) when the batch still fills the chip
-    if constexpr (sizeof(R) == 8) {
-      const int lanes = eea::control_pack_lanes(p, B, eea::option(EEA_OPT_AGENT_LANES));
-      if (lanes != 0) {
-        EEA_HIP(eea::launch_control_pack(p, B, e->cfg.model, rollout_only, lanes, s));
-        return EEA_OK;
-      }
+  const eea::ControlForm f = control_form<R>(p, B, done != nullptr);
+  if (form != nullptr) *form = f;
+  if constexpr (sizeof(R) == 8) {
+    if (f.lanes != 0 && f.lanes < 64) {
+      EEA_HIP(eea::launch_control_pack(p, B, e->cfg.model, rollout_only, f.lanes, s));
+      return EEA_OK;
     }
+  }
+  if (f.lanes == 64) {
     EEA_HIP(eea::launch_control_wave<R>(p, B, e->cfg.model, rollout_only, s));
     return EEA_OK;
   }
@@ -795,10 +819,10 @@ eea_status resident_start(eea_engine* e)
   p.mem_cols = static_cast<const R*>(e->d_rmem);
   p.mem_stride = static_cast<unsigned>(eea::kResidentMemCols);
   p.rec_len = eea::ck_record_len(e->K2);
-  // horizons of one slot: ONE wavefront (the kernel the launch path takes at these shapes, control_batch_impl), otherwise the
-  // workgroup
+  p.done = &dm->done;  // (the workgroup announces the answer itself and ignores it)
+  // fp64 horizons of one slot: ONE wavefront (the kernel the launch path takes at these shapes), otherwise the workgroup
   bool one_wavefront = false;
-  if constexpr (sizeof(R) == 8) one_wavefront = eea::option(EEA_OPT_CONTROL_KERNEL) == 0 && eea::control_wave_resident_eligible(p);
+  if constexpr (sizeof(R) == 8) one_wavefront = control_form<R>(p, 1, true).lanes == 64 && eea::control_wave_resident_eligible(p);
   const size_t lds = eea::control_lds_bytes<R>(p.T, p.K, eea::kResidentMemCols, p.chunk);
   if (!one_wavefront && lds > 160 * 1024) return EEA_ERR_UNSUPPORTED;  // (no message: the caller takes the launch path)
   hm->alive = 1;
@@ -806,7 +830,6 @@ eea_status resident_start(eea_engine* e)
   __atomic_thread_fence(__ATOMIC_SEQ_CST);
   if constexpr (sizeof(R) == 8) {
     if (one_wavefront) {
-      p.done = &dm->done;
       p.res_mail = e->d_rmail;
       p.res_first = e->res_seq;
       p.res_idle = resident_idle_ticks();
@@ -885,6 +908,32 @@ eea_status check_engine(const eea_engine* e)
   return EEA_OK;
 }
 }  // namespace
+
+eea_status eea::control_batch(eea_engine* e, unsigned B, const eea_batch_io* io, void* stream, ControlForm* form,
+                              unsigned n_steps, unsigned pose_step_stride, unsigned u0_step_stride)
+{
+  if (check_engine(e) != EEA_OK) return EEA_ERR_INVALID_ARGUMENT;
+  if (io == nullptr || io->d_pose == nullptr || io->d_ut == nullptr || io->d_u0 == nullptr) {
+    return fail(EEA_ERR_INVALID_ARGUMENT, "d_pose, d_ut and d_u0 are required");
+  }
+  if (n_steps == 0 || n_steps > (1u << 20)) return fail(EEA_ERR_INVALID_ARGUMENT, "n_steps must be in 1 .. 2^20");
+  if ((pose_step_stride != 0 && pose_step_stride < B) || (u0_step_stride != 0 && u0_step_stride < B)) {
+    return fail(EEA_ERR_INVALID_ARGUMENT, "a step stride is 0 (the same row every step) or >= B agents");
+  }
+  if (n_steps > 1 && (io->d_rec_ready != nullptr || io->d_ck_flag != nullptr)) {
+    // a step of the launch would wait, inside the kernel, for an exchange the host can only enqueue after this call: that
+    // needs truly concurrent hardware queues (streams may share one) -- the device-bound exchange is one step per launch
+    return fail(EEA_ERR_UNSUPPORTED, "the device-bound exchange (d_rec_ready / d_ck_flag) takes one step per launch");
+  }
+  if (!e->have_phik) return fail(EEA_ERR_NO_TARGET, "no phi_k: call eea_config_domain or eea_set_target_grid first");
+  eea_status st = use_device(e);
+  if (st != EEA_OK) return st;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  st = order_after_rebuild(e, s);  // a phi_k rebuild that was only enqueued on another stream (eea_config_domain_async)
+  if (st != EEA_OK) return st;
+  return e->f32 ? control_batch_impl<float>(e, B, io, false, s, form, nullptr, nullptr, n_steps, pose_step_stride, u0_step_stride)
+                : control_batch_impl<double>(e, B, io, false, s, form, nullptr, nullptr, n_steps, pose_step_stride, u0_step_stride);
+}
 
 extern "C" {
 
@@ -1006,28 +1055,8 @@ void eea_destroy(eea_engine* e)
 }
 
 unsigned eea_steps(const eea_engine* e) { return e ? static_cast<unsigned>(e->T) : 0u; }
-unsigned eea_batch_agent_lanes(const eea_engine* e, unsigned B)
-{
-  if (e == nullptr || eea::option(EEA_OPT_CONTROL_KERNEL) != 0) return 0u;
-  if (e->cfg.precision == EEA_PREC_F64) {
-    eea::ControlParams<double> p;
-    fill_params<double>(e, p);
-    if (!eea::control_wave_eligible<double>(p, false)) return 0u;
-    const int lanes = eea::control_pack_lanes(p, B, eea::option(EEA_OPT_AGENT_LANES));
-    return lanes != 0 ? static_cast<unsigned>(lanes) : 64u;
-  }
-  eea::ControlParams<float> p;
-  fill_params<float>(e, p);
-  return eea::control_wave_eligible<float>(p, false) ? 64u : 0u;
-}
-unsigned eea_batch_record_count(const eea_engine* e, unsigned B)
-{
-  const unsigned lanes = eea_batch_agent_lanes(e, B);
-  if (e == nullptr) return 0u;
-  if (lanes == 0u || lanes >= 64u) return B;
-  const unsigned A = 64u / lanes;
-  return (B + A - 1u) / A;
-}
+unsigned eea_batch_agent_lanes(const eea_engine* e, unsigned B) { return e ? batch_form(e, B).lanes : 0u; }
+unsigned eea_batch_record_count(const eea_engine* e, unsigned B) { return e ? batch_form(e, B).records(B) : 0u; }
 unsigned eea_num_modes(const eea_engine* e) { return e ? static_cast<unsigned>(e->K2) : 0u; }
 size_t eea_real_size(const eea_engine* e) { return e ? e->rs : 0; }
 unsigned eea_ck_record_len(const eea_engine* e) { return e ? static_cast<unsigned>(eea::ck_record_len(e->K2)) : 0u; }
@@ -1299,44 +1328,13 @@ eea_status eea_get_target_grid(eea_engine* e, double* h_phi_vals)
 
 eea_status eea_control_batch(eea_engine* e, unsigned B, const eea_batch_io* io, void* stream)
 {
-  if (check_engine(e) != EEA_OK) return EEA_ERR_INVALID_ARGUMENT;
-  if (io == nullptr || io->d_pose == nullptr || io->d_ut == nullptr || io->d_u0 == nullptr) {
-    return fail(EEA_ERR_INVALID_ARGUMENT, "d_pose, d_ut and d_u0 are required");
-  }
-  if (!e->have_phik) return fail(EEA_ERR_NO_TARGET, "no phi_k: call eea_config_domain or eea_set_target_grid first");
-  eea_status st = use_device(e);
-  if (st != EEA_OK) return st;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  st = order_after_rebuild(e, s);  // a phi_k rebuild that was only enqueued on another stream (eea_config_domain_async)
-  if (st != EEA_OK) return st;
-  return e->f32 ? control_batch_impl<float>(e, B, io, false, s)
-                : control_batch_impl<double>(e, B, io, false, s);
+  return eea::control_batch(e, B, io, stream, nullptr);
 }
 
 eea_status eea_control_batch_steps(eea_engine* e, unsigned B, const eea_batch_io* io, unsigned n_steps,
                                    unsigned pose_step_stride, unsigned u0_step_stride, void* stream)
 {
-  if (check_engine(e) != EEA_OK) return EEA_ERR_INVALID_ARGUMENT;
-  if (io == nullptr || io->d_pose == nullptr || io->d_ut == nullptr || io->d_u0 == nullptr) {
-    return fail(EEA_ERR_INVALID_ARGUMENT, "d_pose, d_ut and d_u0 are required");
-  }
-  if (n_steps == 0 || n_steps > (1u << 20)) return fail(EEA_ERR_INVALID_ARGUMENT, "n_steps must be in 1 .. 2^20");
-  if ((pose_step_stride != 0 && pose_step_stride < B) || (u0_step_stride != 0 && u0_step_stride < B)) {
-    return fail(EEA_ERR_INVALID_ARGUMENT, "a step stride is 0 (the same row every step) or >= B agents");
-  }
-  if (n_steps > 1 && (io->d_rec_ready != nullptr || io->d_ck_flag != nullptr)) {
-    // a step of the launch would wait, inside the kernel, for an exchange the host can only enqueue after this call: that
-    // needs truly concurrent hardware queues (streams may share one) -- the device-bound exchange is one step per launch
-    return fail(EEA_ERR_UNSUPPORTED, "the device-bound exchange (d_rec_ready / d_ck_flag) takes one step per launch");
-  }
-  if (!e->have_phik) return fail(EEA_ERR_NO_TARGET, "no phi_k: call eea_config_domain or eea_set_target_grid first");
-  eea_status st = use_device(e);
-  if (st != EEA_OK) return st;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  st = order_after_rebuild(e, s);
-  if (st != EEA_OK) return st;
-  return e->f32 ? control_batch_impl<float>(e, B, io, false, s, nullptr, n_steps, pose_step_stride, u0_step_stride)
-                : control_batch_impl<double>(e, B, io, false, s, nullptr, n_steps, pose_step_stride, u0_step_stride);
+  return eea::control_batch(e, B, io, stream, nullptr, n_steps, pose_step_stride, u0_step_stride);
 }
 
 static eea_status records_sum_impl(eea_engine* e, unsigned B, const void* d_ck_rec, void* d_sum, void* stream,
@@ -1486,10 +1484,8 @@ eea_status eea_control(eea_engine* e, double xmin, double xmax, double ymin, dou
   io.d_status = &dm->status;
   io.d_ut = e->d_ut1.p;
   e->mail_seq = (e->mail_seq % 1000000) + 1;
-  e->mail_done = &dm->done;
-  st = e->f32 ? control_batch_impl<float>(e, 1, &io, false, e->stream1)
-              : control_batch_impl<double>(e, 1, &io, false, e->stream1);
-  e->mail_done = nullptr;
+  st = e->f32 ? control_batch_impl<float>(e, 1, &io, false, e->stream1, nullptr, &dm->done)
+              : control_batch_impl<double>(e, 1, &io, false, e->stream1, nullptr, &dm->done);
   if (st != EEA_OK) return st;
   // the kernel publishes u0 / status and then the sequence number with a system-scope release: poll it
   // (a few microseconds earlier than the stream's completion signal); bounded, then the ordinary wait

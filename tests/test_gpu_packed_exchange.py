@@ -157,19 +157,28 @@ def test_packed_wavefront_records(lanes, L, steps, model, bound):
     live = [b for b in range(B) if b not in skipped and b not in bad]
     assert s[K2] == n_good == len(live)
     assert np.abs(s[:K2] - arec[live, :K2].sum(0)).max() <= 1e-12 * max(1.0, np.abs(arec[live, :K2].sum(0)).max())
-    # kernels of one agent per wavefront write per-agent records either way
+    # kernels of one agent per wavefront or per workgroup write per-agent records either way: the wavefront kernel (fp64 and
+    # fp32) and the forced workgroup kernel (fp32: within its own rounding -- this checks where the records land)
     lanes(64)
-    assert eng.record_count(B) == B
-    d_rec64 = torch.full((B, RL), -5.0, dtype=torch.float64, device="cuda")
-    eng.control_batch(B, dev(poses), dev(ut0), torch.empty((B, 3), dtype=torch.float64, device="cuda"), ck_rec=d_rec64,
-                      rec_per_wavefront=True, skip=d_skip)
-    torch.cuda.synchronize()
-    r64 = d_rec64.cpu().numpy()
-    for b in range(B):
-        if b in skipped:
-            assert (r64[b] == -5.0).all()
-        else:
-            assert np.abs(r64[b] - arec[b]).max() <= TOL_CK
+    e32, _ = make_pair(model, K, steps * 0.1, n_oracles=0, precision=capi.PREC_F32)
+    for form, e, tdt, tol in (("wavefront", eng, torch.float64, TOL_CK), ("workgroup", eng, torch.float64, TOL_CK),
+                              ("fp32", e32, torch.float32, 1e-4)):
+        capi.set_option(capi.OPT_CONTROL_KERNEL, 1 if form == "workgroup" else 0)
+        try:
+            assert e.record_count(B) == B, form
+            d_rec1 = torch.full((B, RL), -5.0, dtype=tdt, device="cuda")
+            e.control_batch(B, dev(poses, tdt), dev(ut0, tdt), torch.empty((B, 3), dtype=tdt, device="cuda"), ck_rec=d_rec1,
+                            rec_per_wavefront=True, skip=d_skip)
+            torch.cuda.synchronize()
+        finally:
+            capi.set_option(capi.OPT_CONTROL_KERNEL, 0)
+        r1 = d_rec1.cpu().numpy().astype(np.float64)
+        for b in range(B):
+            if b in skipped:
+                assert (r1[b] == -5.0).all(), form
+            else:
+                assert np.abs(r1[b] - arec[b]).max() <= tol, form
+    e32.close()
     eng.close()
 
 

@@ -20,17 +20,16 @@ extern "C" eea_status eea_debug_phase_timing(eea_engine* e, unsigned B, const ee
   eea_status st = use_device(e);
   if (st != EEA_OK) return st;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (e->f32) return control_batch_impl<float>(e, B, io, false, s, d_stamps);  // wavefront-per-agent kernel only
+  if (e->f32) return control_batch_impl<float>(e, B, io, false, s, nullptr, nullptr, d_stamps);  // wavefront-per-agent kernel only
   eea::ControlParams<double> p;
   fill_params<double>(e, p);
   p.pose = static_cast<const double*>(io->d_pose);
   p.ut = static_cast<double*>(io->d_ut);
   p.u0 = static_cast<double*>(io->d_u0);
   p.ck = static_cast<double*>(io->d_ck);
-  const bool wave = eea::option(EEA_OPT_CONTROL_KERNEL) == 0 && eea::control_wave_eligible<double>(p, false);
-  if (wave) return control_batch_impl<double>(e, B, io, false, s, d_stamps);
+  p.dbg = d_stamps;  // (no packed form with stamps: the wavefront kernel or the workgroup)
+  if (control_form<double>(p, B, false).lanes == 64) return control_batch_impl<double>(e, B, io, false, s, nullptr, nullptr, d_stamps);
   // [agent][4 waves][16] stamps of the workgroup-per-agent kernel's instrumented build
-  p.dbg = d_stamps;
   if (eea::control_lds_bytes<double>(p.T, p.K, 0, p.chunk) > 160 * 1024) {
     return fail(EEA_ERR_UNSUPPORTED, "horizon/basis too large for one workgroup's 160 KiB LDS");
   }
