@@ -200,6 +200,16 @@ def lib():
         L.eea_validate_control_batch.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_double, C.c_double,
                                                  C.c_uint, C.c_void_p, C.c_void_p]
+        L.eea_replay_create.argtypes = [C.c_int, C.c_uint, C.c_uint, C.c_uint, C.c_uint64, C.c_uint, C.c_size_t, C.POINTER(C.c_void_p)]
+        L.eea_replay_destroy.argtypes = [C.c_void_p]
+        L.eea_replay_destroy.restype = None
+        L.eea_replay_append.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.eea_replay_sample.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p]
+        L.eea_replay_append_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint,
+                                               C.c_void_p]
+        L.eea_replay_counts.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_ulonglong)]
+        L.eea_replay_read.argtypes = [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p]
+        L.eea_replay_reset.argtypes = [C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -582,6 +592,73 @@ def prepared_stream_wait_flag(flag, timeouts=None, stream=None):
 
 def get_option(option):
     return lib().eea_get_option(option)
+
+
+class ReplayMemory:
+    """eea_replay: the replay memory of a fleet in device memory -- ReplayBuffer::append / sampleMemory (buffer.cpp) for B robots
+    as kernels that fill the mem_cols / n_mem tensors control_batch / tick_batch take.  Poses and columns are device tensors of
+    the dtype real_size names (8: float64, 4: float32), masks and n_mem int32; `draw` is the caller's tick counter (a draw is a
+    pure function of (seed, draw, robot0 + b, column): ergodic_amd.h)."""
+
+    def __init__(self, B, capacity, batch_size, seed=0, robot0=0, real_size=8, device=0):
+        self.h = C.c_void_p()
+        check(lib().eea_replay_create(device, B, capacity, batch_size, seed, robot0, real_size, C.byref(self.h)))
+        self.B, self.capacity, self.batch_size, self.real_size = B, capacity, batch_size, real_size
+
+    def append(self, pose, mask=None, stream=None):
+        check(lib().eea_replay_append(self.h, _ptr(pose), _ptr(mask), C.c_void_p(stream or 0)))
+
+    def sample(self, draw, mem_cols, n_mem, mem_stride=None, stream=None):
+        stride = mem_cols.shape[1] if mem_stride is None else mem_stride
+        check(lib().eea_replay_sample(self.h, draw, _ptr(mem_cols), _ptr(n_mem), stride, C.c_void_p(stream or 0)))
+
+    def append_sample(self, pose, draw, mem_cols, n_mem, mask=None, mem_stride=None, stream=None):
+        """the per-tick form, one launch: append, then sample from the memory that includes the new pose"""
+        stride = mem_cols.shape[1] if mem_stride is None else mem_stride
+        check(lib().eea_replay_append_sample(self.h, _ptr(pose), _ptr(mask), draw, _ptr(mem_cols), _ptr(n_mem), stride,
+                                             C.c_void_p(stream or 0)))
+
+    def prepared_append_sample(self, pose, mem_cols, n_mem, mask=None, stream=None):
+        """a callable tick(draw) with the pointers converted once (the launch is a few microseconds: per-tick host work counts)"""
+        fn, h = lib().eea_replay_append_sample, self.h
+        a = (_ptr(pose), _ptr(mask), _ptr(mem_cols), _ptr(n_mem), mem_cols.shape[1], C.c_void_p(stream or 0))
+        keep = (pose, mask, mem_cols, n_mem)
+
+        def call(draw, _keep=keep):
+            rc = fn(h, a[0], a[1], draw, a[2], a[3], a[4], a[5])
+            if rc != 0:
+                check(rc)
+        return call
+
+    def counts(self):
+        """(poses stored per robot [B], appends dropped by full stores in total); waits for the device"""
+        import numpy as np
+        n, dropped = np.empty(self.B, dtype=np.uint32), C.c_ulonglong(0)
+        check(lib().eea_replay_counts(self.h, _ptr(n), C.byref(dropped)))
+        return n, int(dropped.value)
+
+    def read(self, b, first=0, n=None):
+        """poses first .. first + n - 1 of robot b as a host array [n][3] (n = None: up to the robot's count); waits for the device"""
+        import numpy as np
+        if n is None:
+            n = int(self.counts()[0][b]) - first
+        out = np.empty((n, 3), dtype=np.float64 if self.real_size == 8 else np.float32)
+        check(lib().eea_replay_read(self.h, b, first, n, _ptr(out)))
+        return out
+
+    def reset(self, stream=None):
+        check(lib().eea_replay_reset(self.h, C.c_void_p(stream or 0)))
+
+    def close(self):
+        if self.h:
+            lib().eea_replay_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 COMM_ID_BYTES = 128

@@ -189,7 +189,7 @@ public:
   // validate_control, the dynamic window per agent in its mode, the follow_dwa / i state machine.  The poses are those of
   // setPoses; vb: 3 x n body twists (odometry).  map_seq != 0: the caller vouches that (grid, map_seq) names one map content
   // (the inflated collision map is reused between ticks).  addStateMemory is the caller's (this class keeps no replay
-  // memory).  Returns the commanded twists, 3 x n.
+  // memory; FleetReplayMemory of replay_memory.hpp is the device-resident one for loops that call eea_tick_batch themselves).  Returns the commanded twists, 3 x n.
   mat tick(const GridMap& grid, const DynamicWindow& dwa, const mat& vb, double val_dt, double val_horizon,
            unsigned long long map_seq = 0)
   {

@@ -1,6 +1,7 @@
-// ReplayBuffer: past poses kept on the host (reference buffer.hpp / buffer.cpp).  Sampling stays
-// on the host because its random stream is host state; the device engine receives the sampled
-// columns (sampleColumns) and prepends them itself.
+// ReplayBuffer: past poses of ONE robot kept on the host (reference buffer.hpp / buffer.cpp): the single-robot path, where the
+// host has the pose in hand every tick; the device engine receives the sampled columns (sampleColumns) and prepends them
+// itself.  A FLEET keeps its memory on the device instead: FleetReplayMemory (replay_memory.hpp), whose append and
+// sampleMemory are kernels with a counter-based random stream, so that its loop needs no host round trip.
 #pragma once
 
 #include <iostream>

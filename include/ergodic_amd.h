@@ -53,8 +53,9 @@ typedef enum {
 typedef struct eea_engine eea_engine;
 
 /* Constructor arguments of ErgodicControl (ergodic_control.hpp:90-94, 187-222).
- * collision / buffer_size / batch_size are host-side concerns (the collision object is
- * never read on this path; replay-memory sampling stays on the host, see mem_cols). */
+ * collision / buffer_size / batch_size are not engine state (the collision object is never read on this path; the
+ * sampled replay-memory columns come in through mem_cols: from the host's ReplayBuffer for one robot, from the device
+ * replay memory of a fleet -- eea_replay_* below, which takes buffer_size / batch_size -- without leaving the device). */
 typedef struct {
   int model;          /* EEA_MODEL_* */
   int precision;      /* EEA_PREC_* */
@@ -549,7 +550,8 @@ eea_status eea_dwa_control_batch(int device, const eea_collision_cfg* ccfg, cons
  *      (:243-251); the others track optTraj() -- the rollout of the UPDATED controls -- and follow the result if one was
  *      found (:254-277).  u = 0 where the dynamic window finds nothing.
  * State carried between ticks, per robot, device memory owned by the caller, zero before the first tick: d_follow_dwa,
- * d_dwa_count, d_u.  addStateMemory (:209) stays on the caller's side: io->d_mem_cols / d_n_mem as for eea_control_batch.
+ * d_dwa_count, d_u.  addStateMemory (:209) and sampleMemory come in front of the tick: io->d_mem_cols / d_n_mem as for eea_control_batch, filled on
+ * the same stream by eea_replay_append_sample (the fleet's replay memory in device memory, below) or by the caller.
  * io->d_u0, d_traj, d_skip are ignored (the tick supplies its own); everything else of io is passed to the control call.
  * fp64 engines only (poses and twists are the doubles the collision / DWA kernels take). */
 typedef struct {
@@ -572,7 +574,48 @@ typedef struct {
 eea_status eea_tick_batch(eea_engine* e, unsigned B, const eea_batch_io* io, const eea_tick_io* tick,
                           const eea_collision_cfg* ccfg, const eea_dwa_cfg* dcfg, void* stream);
 
-/* The calls above keep small device caches between calls (the ring offsets per radii, one
+/* ---- the replay memory of a FLEET in device memory (additive to ABI 6: detect these entries by symbol) --------------------
+ * ReplayBuffer (buffer.hpp / buffer.cpp) for B robots: one store of `capacity` poses and a count per robot, in device memory;
+ * append and sampleMemory are kernels that fill the d_mem_cols / d_n_mem buffers eea_control_batch / eea_tick_batch take, so
+ * a closed fleet loop -- eea_replay_append_sample, eea_tick_batch, eea_integrate_twist_batch on one stream -- needs no host
+ * round trip between ticks.  No existing struct or entry changes and eea_abi_version() stays 6: a caller built against this
+ * header that may meet an older library looks the entries up by symbol (dlsym).  The layout of the store is private
+ * (eea_replay_read reads it).
+ * The random stream: Armadillo's global randi stream (buffer.cpp:99) is host state and cannot be pinned; the contract is the
+ * distribution -- batch_size draws with replacement, uniform on [0, n - 1].  A draw is a pure function of (seed, draw, global
+ * robot id, column): Philox4x32-10 with counter (j, robot0 + b, draw_lo, draw_hi) (robot0 + b mod 2^32) and key (seed_lo,
+ * seed_hi); r64 = out[0] | out[1] << 32; index = (r64 * n) >> 64 (bias <= n / 2^64).  So a run is reproducible, a robot's
+ * draws do not depend on how the fleet is sharded over ranks (each shard passes the global id of its first robot), and a
+ * robot that skips control() in a tick simply leaves that tick's draw unused.  `draw` is the caller's tick counter.
+ * real_size: 8 or 4 -- the `real` of the engine the columns are for (d_pose, d_mem_cols and eea_replay_read use it). */
+typedef struct eea_replay eea_replay;
+/* ReplayBuffer::ReplayBuffer(buffer_size, batch_size) per robot.  EEA_ERR_INVALID_ARGUMENT (before any HIP call): B, capacity
+ * or batch_size == 0, real_size not 8 / 4, out == NULL.  EEA_ERR_HIP with a message: the store's size overflows or cannot be
+ * allocated. */
+eea_status eea_replay_create(int device, unsigned B, unsigned capacity, unsigned batch_size, uint64_t seed, unsigned robot0,
+                             size_t real_size, eea_replay** out);
+void eea_replay_destroy(eea_replay* r);
+/* ReplayBuffer::append (buffer.cpp:54-62) of d_pose [B][3] for every robot with d_mask[b] != 0 (d_mask == NULL: all).  A
+ * full store drops the pose and counts the drop (the reference's "Buffer is full" branch; not a ring).  Asynchronous. */
+eea_status eea_replay_append(eea_replay* r, const void* d_pose, const int* d_mask, void* stream);
+/* The columns ReplayBuffer::sampleMemory (buffer.cpp:64-111) prepends, per robot with n = its count: n == 0: d_n_mem[b] = 0;
+ * n <= batch_size: the n stored poses in order, d_n_mem[b] = n (:75-89); otherwise batch_size draws (:91-108, stream above),
+ * d_n_mem[b] = batch_size.  d_mem_cols [B][mem_stride][3] reals, columns past d_n_mem[b] are not written; mem_stride <
+ * batch_size is EEA_ERR_INVALID_ARGUMENT.  Asynchronous. */
+eea_status eea_replay_sample(eea_replay* r, uint64_t draw, void* d_mem_cols, int* d_n_mem, unsigned mem_stride, void* stream);
+/* The per-tick form in ONE launch: append, then sample from the memory that includes the new pose (the reference's order,
+ * exploration.hpp:209 then :232).  Bitwise what eea_replay_append followed by eea_replay_sample gives. */
+eea_status eea_replay_append_sample(eea_replay* r, const void* d_pose, const int* d_mask, uint64_t draw, void* d_mem_cols,
+                                    int* d_n_mem, unsigned mem_stride, void* stream);
+/* Synchronising readers (tests, checkpoints, logs): wait for the device, then h_count [B] = poses stored per robot and
+ * *h_dropped = appends refused by full stores since creation / the last reset, all robots (either may be NULL);
+ * h_cols [n][3] reals = poses first .. first + n - 1 of robot b (EEA_ERR_INVALID_ARGUMENT past the robot's count). */
+eea_status eea_replay_counts(eea_replay* r, unsigned* h_count, unsigned long long* h_dropped);
+eea_status eea_replay_read(eea_replay* r, unsigned b, unsigned first, unsigned n, void* h_cols);
+/* empties every robot's store and zeroes the drop counter.  Asynchronous. */
+eea_status eea_replay_reset(eea_replay* r, void* stream);
+
+/* The collision / DWA / tick calls keep small device caches between calls (the ring offsets per radii, one
  * inflated-map buffer per (device, stream)).  A long-running process that changes streams or map sizes
  * can drop them; synchronises the devices involved.  No reference counterpart. */
 void eea_release_collision_caches(void);
