@@ -210,6 +210,8 @@ def lib():
         L.eea_replay_counts.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_ulonglong)]
         L.eea_replay_read.argtypes = [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p]
         L.eea_replay_reset.argtypes = [C.c_void_p, C.c_void_p]
+        L.eea_replay_history_records.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.eea_records_metric.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -604,6 +606,7 @@ class ReplayMemory:
         self.h = C.c_void_p()
         check(lib().eea_replay_create(device, B, capacity, batch_size, seed, robot0, real_size, C.byref(self.h)))
         self.B, self.capacity, self.batch_size, self.real_size = B, capacity, batch_size, real_size
+        self._coverage_ws = None   # workspaces of coverage(): allocated once per object (and engine), not per call
 
     def append(self, pose, mask=None, stream=None):
         check(lib().eea_replay_append(self.h, _ptr(pose), _ptr(mask), C.c_void_p(stream or 0)))
@@ -649,7 +652,36 @@ class ReplayMemory:
     def reset(self, stream=None):
         check(lib().eea_replay_reset(self.h, C.c_void_p(stream or 0)))
 
+    def history_records(self, engine, out, stream=None):
+        """eea_replay_history_records: out [B][engine.ck_record_len] = the sum record of every robot's whole stored history
+        (sum over its poses of the K^2 basis products in the engine's current domain; element K^2 = its count); asynchronous"""
+        check(lib().eea_replay_history_records(engine.h, self.h, _ptr(out), C.c_void_p(stream or 0)))
+
+    def coverage(self, engine, stream=None):
+        """(eps per robot [B], eps of the fleet [1]) as device tensors: the ergodic metric sum_k lamda_k (c_k - phi_k)^2 of each
+        robot's whole stored history and of all of them together -- history_records, eea_ck_records_sum over the B rows,
+        records_metric on both; asynchronous on `stream`, no host round trip.  The tensors (and the per-robot / fleet records
+        in self.coverage_records) belong to this object and are overwritten by the next call for the same engine."""
+        import torch
+        ws = self._coverage_ws
+        if ws is None or ws[0] is not engine:
+            dt, L = torch.float64 if self.real_size == 8 else torch.float32, engine.ck_record_len
+            new = lambda *shape: torch.empty(shape, dtype=dt, device="cuda")   # (every element is written by the kernels)
+            ws = self._coverage_ws = (engine, new(self.B, L), new(L), new(self.B), new(1))
+        _, rec, fleet, eps, eps_fleet = ws
+        self.history_records(engine, rec, stream)
+        engine.ck_records_sum(self.B, rec, fleet, stream)
+        records_metric(engine, rec, eps, stream=stream)
+        records_metric(engine, fleet, eps_fleet, stream=stream)
+        return eps, eps_fleet
+
+    @property
+    def coverage_records(self):
+        """(per-robot sum records [B][record_len], fleet sum record [record_len]) of the last coverage() call"""
+        return self._coverage_ws[1], self._coverage_ws[2]
+
     def close(self):
+        self._coverage_ws = None
         if self.h:
             lib().eea_replay_destroy(self.h)
             self.h = C.c_void_p()
@@ -659,6 +691,13 @@ class ReplayMemory:
             self.close()
         except Exception:
             pass
+
+
+def records_metric(engine, rec, metric, ck=None, stream=None):
+    """eea_records_metric: metric[j] = sum_m lamda_m (rec[j][m] / rec[j][K^2] - phi_m)^2 for the sum records rec
+    [n][engine.ck_record_len] (or one record [record_len]); ck [n][K^2] (optional) receives the quotients; asynchronous"""
+    n = 1 if rec.dim() == 1 else int(rec.shape[0])
+    check(lib().eea_records_metric(engine.h, n, _ptr(rec), _ptr(metric), _ptr(ck), C.c_void_p(stream or 0)))
 
 
 COMM_ID_BYTES = 128

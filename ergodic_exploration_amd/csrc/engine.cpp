@@ -935,6 +935,26 @@ eea_status eea::control_batch(eea_engine* e, unsigned B, const eea_batch_io* io,
                 : control_batch_impl<double>(e, B, io, false, s, form, nullptr, nullptr, n_steps, pose_step_stride, u0_step_stride);
 }
 
+void eea::engine_view(const eea_engine* e, EngineView* v)
+{
+  v->device = e->cfg.device;
+  v->K = e->K;
+  v->f32 = e->f32;
+  v->have_phik = e->have_phik;
+  v->lx = e->lx;
+  v->ly = e->ly;
+  v->map_x = e->map_x;
+  v->map_y = e->map_y;
+  v->d_phik = e->d_phik.p;
+  v->d_lamdak = e->d_lamdak.p;
+}
+
+eea_status eea::engine_enter(eea_engine* e, hipStream_t s)
+{
+  const eea_status st = use_device(e);
+  return st != EEA_OK ? st : order_after_rebuild(e, s);
+}
+
 extern "C" {
 
 const char* eea_last_error(void) { return eea::g_last_error.c_str(); }

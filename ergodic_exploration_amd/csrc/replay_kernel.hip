@@ -193,6 +193,16 @@ eea_status check_sample_args(const eea_replay* r, const void* d_mem_cols, const 
   return EEA_OK;
 }
 }  // namespace
+
+void replay_view(const eea_replay* r, ReplayView* v)
+{
+  v->device = r->device;
+  v->B = r->B;
+  v->capacity = r->capacity;
+  v->real_size = r->real_size;
+  v->d_store = r->d_store;
+  v->d_count = r->d_count;
+}
 }  // namespace eea
 
 using eea::fail;

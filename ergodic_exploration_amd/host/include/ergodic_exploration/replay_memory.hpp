@@ -65,6 +65,12 @@ public:
     throw_on_error(eea_replay_read(r_, robot, first, n, h_cols));
   }
   void reset(void* stream = nullptr) { throw_on_error(eea_replay_reset(r_, stream)); }
+  // d_rec [n][eea_ck_record_len(e)]: the sum record of every robot's WHOLE stored history in the engine's current domain
+  // (Basis::trajCoeff without the 1/N; element K^2 = the robot's count); eea_ck_records_sum over the rows is the fleet's
+  void historyRecords(eea_engine* e, void* d_rec, void* stream = nullptr)
+  {
+    throw_on_error(eea_replay_history_records(e, r_, d_rec, stream));
+  }
 
   unsigned int robots() const { return n_; }
   unsigned int batchSize() const { return batch_size_; }  // the least mem_stride sample() takes
@@ -76,4 +82,12 @@ private:
   std::size_t real_size_;
   eea_replay* r_ = nullptr;
 };
+
+// the ergodic metric sum_k lamda_k (c_k - phi_k)^2 of n_rec sum records (history records, a fleet record, the consensus
+// records of control passes): d_metric [n_rec], d_ck [n_rec][K^2] optional
+inline void recordsMetric(eea_engine* e, unsigned int n_rec, const void* d_rec, void* d_metric, void* d_ck = nullptr,
+                          void* stream = nullptr)
+{
+  throw_on_error(eea_records_metric(e, n_rec, d_rec, d_metric, d_ck, stream));
+}
 }  // namespace ergodic_exploration

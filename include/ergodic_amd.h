@@ -615,6 +615,35 @@ eea_status eea_replay_read(eea_replay* r, unsigned b, unsigned first, unsigned n
 /* empties every robot's store and zeroes the drop counter.  Asynchronous. */
 eea_status eea_replay_reset(eea_replay* r, void* stream);
 
+/* ---- coverage of a fleet's history (additive to ABI 6, after eea_replay_*: detect these entries by symbol) ------------------
+ * How ergodic is what the fleet has done so far: eps = sum_k lamda_k (c_k - phi_k)^2, the metric whose gradient control()
+ * descends (gradErgodicMetric, ergodic_control.hpp:419-446), with c_k over ALL stored poses.  The reference never forms it and
+ * only samples its history (<= batch_size columns, buffer.cpp:64-111).  Both calls are asynchronous on `stream`, read nothing
+ * on the host and make no synchronising call; eea_abi_version() stays 6.
+ *
+ * eea_replay_history_records: d_rec [B][eea_ck_record_len(e)] reals of the engine's `real`; row b is the SUM RECORD of robot
+ * b's whole stored history in the format of eea_batch_io::d_ck_rec: for m = k2 * K + k1 < K^2
+ *     rec[b][m] = sum_{i < n_b} cos(k1 (pi / lx) (x_i - map_x)) cos(k2 (pi / ly) (y_i - map_y))
+ * -- Basis::trajCoeff (basis.cpp:109-120) without the 1/N and, as there, without the h_k normalisation --, rec[b][K^2] = n_b,
+ * the robot's count as the device holds it, and the padding exactly 0 (a robot without poses: an all-zero record).  The poses
+ * are used as stored (map frame), shifted by map_pos as control() shifts the memory columns (ergodic_control.hpp:243-244);
+ * nothing is clipped to the domain.  lx, ly, map_x, map_y are the engine's current ones (eea_config_domain): a recompute
+ * from the poses, since every term changes when the map grows.  Ordered behind an in-flight eea_config_domain_async rebuild
+ * the way control calls on that stream are.  A robot's record is a pure function of its own poses and the domain, added in a
+ * fixed order: it does not depend on B, on the robot's index or on the other robots' counts -- two calls give the same bits, a
+ * shard of a fleet the bits the whole fleet gives for its robots.  Sum records are closed under addition:
+ * eea_ck_records_sum over the B rows is the fleet's record (N = sum n_b at element K^2), eea_comm_allreduce_sum adds the
+ * fleet records of the ranks.  fp32 engines: counts are exact up to 2^24 poses per record.
+ * EEA_ERR_INVALID_ARGUMENT before any launch: a null argument, r's real_size != eea_real_size(e), different devices;
+ * EEA_ERR_NO_TARGET: no domain yet. */
+eea_status eea_replay_history_records(eea_engine* e, eea_replay* r, void* d_rec, void* stream);
+/* The ergodic metric of n_rec sum records d_rec [n_rec][eea_ck_record_len(e)] -- history records, the fleet record, or the
+ * consensus sum records of control passes (the metric of the planned horizons): c_m = rec[m] / rec[K^2], c = 0 for every m
+ * where rec[K^2] <= 0; d_metric[j] = sum_m lamda_m (c_m - phi_m)^2 with the engine's current phi_k and lamda_k
+ * (basis.cpp:69-75), added in a fixed order; d_ck [n_rec][K^2] (optional) receives the c_m.  One wavefront per record.
+ * EEA_ERR_INVALID_ARGUMENT: e, d_rec or d_metric null, n_rec == 0; EEA_ERR_NO_TARGET: no phi_k yet. */
+eea_status eea_records_metric(eea_engine* e, unsigned n_rec, const void* d_rec, void* d_metric, void* d_ck, void* stream);
+
 /* The collision / DWA / tick calls keep small device caches between calls (the ring offsets per radii, one
  * inflated-map buffer per (device, stream)).  A long-running process that changes streams or map sizes
  * can drop them; synchronises the devices involved.  No reference counterpart. */
