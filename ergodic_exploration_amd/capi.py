@@ -19,6 +19,7 @@ MODEL_OMNI, MODEL_SIMPLE_CART = 0, 1
 PREC_F64, PREC_F32 = 0, 1
 OK, ERR_INVALID_ARGUMENT, ERR_INVALID_TWIST, ERR_UNSUPPORTED, ERR_HIP, ERR_NO_TARGET, ERR_TIMEOUT = range(7)
 # eea_set_option (process-wide dispatch options; the library reads no environment variable)
+FIELD_DENSITY, FIELD_DEFICIT, FIELD_POTENTIAL = range(3)   # eea_field_kind (eea_records_field)
 OPT_CONTROL_KERNEL, OPT_WORKGROUP_THREADS, OPT_COLLISION_IMPL, OPT_MAILBOX_POLL, OPT_REBUILD_IMPL, OPT_AGENT_LANES, OPT_RESIDENT_CONTROL, OPT_RESIDENT_IDLE_MS = range(8)
 
 
@@ -212,6 +213,8 @@ def lib():
         L.eea_replay_reset.argtypes = [C.c_void_p, C.c_void_p]
         L.eea_replay_history_records.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.eea_records_metric.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.eea_records_field.argtypes = [C.c_void_p, C.c_int, C.c_uint, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_uint,
+                                        C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -335,6 +338,13 @@ class Engine:
         out = np.empty(self.K2)
         check(lib().eea_get_lamdak(self.h, _ptr(out)))
         return out
+
+    @property
+    def target_grid_size(self):
+        """(nx, ny) of the target grid of the last rebuild / eea_set_target_grid (eea_target_grid_size)"""
+        nx, ny = C.c_uint(), C.c_uint()
+        check(lib().eea_target_grid_size(self.h, C.byref(nx), C.byref(ny)))
+        return nx.value, ny.value
 
     def target_grid(self):
         import numpy as np
@@ -607,6 +617,7 @@ class ReplayMemory:
         check(lib().eea_replay_create(device, B, capacity, batch_size, seed, robot0, real_size, C.byref(self.h)))
         self.B, self.capacity, self.batch_size, self.real_size = B, capacity, batch_size, real_size
         self._coverage_ws = None   # workspaces of coverage(): allocated once per object (and engine), not per call
+        self._field_ws = {}        # ... and of coverage_fields(): per kind
 
     def append(self, pose, mask=None, stream=None):
         check(lib().eea_replay_append(self.h, _ptr(pose), _ptr(mask), C.c_void_p(stream or 0)))
@@ -680,8 +691,29 @@ class ReplayMemory:
         """(per-robot sum records [B][record_len], fleet sum record [record_len]) of the last coverage() call"""
         return self._coverage_ws[1], self._coverage_ws[2]
 
+    def coverage_fields(self, engine, kind, fleet_only=True, stream=None):
+        """(fields per robot [B][ny][nx] -- None with fleet_only --, field of the fleet [ny][nx]) on the engine's target grid:
+        records_field of `kind` (FIELD_*) on the records the last coverage(engine) call left in coverage_records; asynchronous
+        on `stream`, no host round trip.  The tensors belong to this object, one set per kind, and are overwritten by the next
+        call for that kind; the per-robot tensor is only allocated when asked for."""
+        import torch
+        cov = self._coverage_ws
+        if cov is None or cov[0] is not engine:
+            raise EngineError(ERR_INVALID_ARGUMENT, "coverage_fields: call coverage() with this engine first")
+        nx, ny = engine.target_grid_size
+        ws = self._field_ws.get(kind)
+        if ws is None or ws[0] is not engine or ws[1] != (nx, ny):
+            ws = self._field_ws[kind] = [engine, (nx, ny), None, torch.empty((ny, nx), dtype=cov[1].dtype, device="cuda")]
+        if not fleet_only:
+            if ws[2] is None:
+                ws[2] = torch.empty((self.B, ny, nx), dtype=cov[1].dtype, device="cuda")
+            records_field(engine, kind, cov[1], ws[2], nx, ny, stream=stream)
+        records_field(engine, kind, cov[2], ws[3], nx, ny, stream=stream)
+        return (None if fleet_only else ws[2]), ws[3]
+
     def close(self):
         self._coverage_ws = None
+        self._field_ws = {}
         if self.h:
             lib().eea_replay_destroy(self.h)
             self.h = C.c_void_p()
@@ -698,6 +730,19 @@ def records_metric(engine, rec, metric, ck=None, stream=None):
     [n][engine.ck_record_len] (or one record [record_len]); ck [n][K^2] (optional) receives the quotients; asynchronous"""
     n = 1 if rec.dim() == 1 else int(rec.shape[0])
     check(lib().eea_records_metric(engine.h, n, _ptr(rec), _ptr(metric), _ptr(ck), C.c_void_p(stream or 0)))
+
+
+def records_field(engine, kind, rec, out, nx=None, ny=None, row0=0, nrows=None, stream=None):
+    """eea_records_field: out [n][nrows][nx] = the field `kind` (FIELD_DENSITY / FIELD_DEFICIT / FIELD_POTENTIAL) of the sum
+    records rec [n][engine.ck_record_len] (or one record [record_len]) on the rows row0 .. row0 + nrows - 1 of an nx x ny grid
+    (default: the engine's target grid, all rows); asynchronous"""
+    n = 1 if rec.dim() == 1 else int(rec.shape[0])
+    if nx is None or ny is None:
+        gx, gy = engine.target_grid_size
+        nx, ny = (gx if nx is None else nx), (gy if ny is None else ny)
+    if nrows is None:
+        nrows = max(ny - row0, 0)
+    check(lib().eea_records_field(engine.h, kind, n, _ptr(rec), nx, ny, row0, nrows, _ptr(out), C.c_void_p(stream or 0)))
 
 
 COMM_ID_BYTES = 128

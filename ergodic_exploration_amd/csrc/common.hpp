@@ -269,6 +269,14 @@ template <typename R>
 hipError_t launch_point_coeff(const R* d_x, const R* d_y, const R* d_w, unsigned P, int K, R pi_lx,
                               R pi_ly, R scale, R* d_work, R* d_out, hipStream_t s);
 
+// ---- coverage fields (field_kernel.hip) --------------------------------------------------
+// d_out [n_rec][nrows][nx] = the field `kind` (eea_field_kind) of the sum records d_rec [n_rec][ck_record_len(K^2)] on the grid
+// rows row0 .. row0 + nrows - 1; d_cx: [K][nx], d_cy: [ny_total][K] (the layouts of launch_axis_tables), area = lx * ly
+template <typename R>
+hipError_t launch_records_field(int kind, unsigned n_rec, const R* d_rec, int K, const R* d_phik, const R* d_lamdak,
+                                const R* d_cx, const R* d_cy, unsigned nx, unsigned row0, unsigned nrows, R area, R* d_out,
+                                hipStream_t s);
+
 // ---- collision path (integer, bit-exact) ------------------------------------------------
 struct CollisionParams
 {

@@ -111,6 +111,18 @@ struct eea_engine
   bool rebuild_pending = false;
   DevBuf d_lut, d_raw, d_occ;  // occupancy targets: decode table, un-normalised sums, staged cells
 
+  // eea_records_field's OWN coordinates and cos tables (cx [K][nx], cy [ny][K]), keyed like the phi_k path's and apart from
+  // them: a field on another grid never evicts d_cx / d_cy / d_work and adds no wait to a rebuild
+  struct FieldTables
+  {
+    DevBuf axis, cx, cy;
+    unsigned axis_n = 0, nx = 0, ny = 0;
+    double lx = 0.0, ly = 0.0;
+    hipEvent_t ev_used = nullptr;  // behind the last field launch: tables are rewritten in place only after it
+  };
+  FieldTables field;
+  std::mutex field_mutex;
+
   // workspaces of eea_ck_records_sum (group records of both levels + the tickets of its tree), one per distinct output
   // buffer: concurrent calls on several streams must not share tickets
   struct SumWs
@@ -305,6 +317,67 @@ eea_status finish_rebuild(eea_engine* e)
   if (!e->rebuild_pending) return EEA_OK;
   EEA_HIP(hipEventSynchronize(e->ev_rebuild));
   e->rebuild_pending = false;
+  return EEA_OK;
+}
+
+// eea_records_field: the axis tables of the current domain on an nx x ny grid in the field's own buffers.  Unchanged
+// (nx, ny, lx, ly): nothing happens here.  Otherwise one table launch on s, behind the last field launch of any stream; a
+// grid larger than the buffers waits for the device before they are replaced (first call / change only).
+template <typename R>
+eea_status field_tables(eea_engine* e, unsigned nx, unsigned ny, hipStream_t s)
+{
+  eea_engine::FieldTables& f = e->field;
+  if (f.nx == nx && f.ny == ny && f.lx == e->lx && f.ly == e->ly) return EEA_OK;
+  const unsigned n = nx > ny ? nx : ny;
+  const size_t need_cx = sizeof(R) * nx * e->K, need_cy = sizeof(R) * ny * e->K;
+  const bool grow = n > f.axis_n || need_cx > f.cx.cap || need_cy > f.cy.cap;
+  f.nx = f.ny = 0;  // (a failure below leaves no key on tables that were never written)
+  if (grow) EEA_HIP(hipDeviceSynchronize());  // field kernels may still read the buffers about to be replaced
+  if (n > f.axis_n) {
+    // the coordinate sequence of ensure_axis: repeated += resolution from 0 (ergodic_control.hpp:387-408)
+    unsigned cap = f.axis_n ? 2 * f.axis_n : 2048;
+    if (cap < n) cap = n;
+    std::vector<R> v(cap);
+    double x = 0.0;
+    for (unsigned i = 0; i < cap; ++i) {
+      v[i] = static_cast<R>(x);
+      x += e->cfg.resolution;
+    }
+    f.axis_n = 0;
+    EEA_HIP(f.axis.reserve(sizeof(R) * cap));
+    EEA_HIP(hipMemcpy(f.axis.p, v.data(), sizeof(R) * cap, hipMemcpyHostToDevice));
+    f.axis_n = cap;
+  }
+  EEA_HIP(f.cx.reserve(need_cx));
+  EEA_HIP(f.cy.reserve(need_cy));
+  if (f.ev_used == nullptr) {
+    EEA_HIP(hipEventCreateWithFlags(&f.ev_used, hipEventDisableTiming));
+  } else if (!grow) {
+    EEA_HIP(hipStreamWaitEvent(s, f.ev_used, 0));  // a field launch of another stream may still read the old tables
+  }
+  const R pi_lx = static_cast<R>(eea::kPi / e->lx), pi_ly = static_cast<R>(eea::kPi / e->ly);
+  EEA_HIP(eea::launch_axis_tables<R>(static_cast<const R*>(f.axis.p), nx, ny, e->K, pi_lx, pi_ly, static_cast<R*>(f.cx.p),
+                                     static_cast<R*>(f.cy.p), s));
+  f.nx = nx;
+  f.ny = ny;
+  f.lx = e->lx;
+  f.ly = e->ly;
+  return EEA_OK;
+}
+
+template <typename R>
+eea_status records_field_impl(eea_engine* e, int kind, unsigned n_rec, const void* d_rec, unsigned nx, unsigned ny_total,
+                              unsigned row0, unsigned nrows, void* d_field, hipStream_t s)
+{
+  std::lock_guard<std::mutex> lock(e->field_mutex);
+  const eea_status st = field_tables<R>(e, nx, ny_total, s);
+  if (st != EEA_OK) return st;
+  const eea_engine::FieldTables& f = e->field;
+  EEA_HIP(eea::launch_records_field<R>(kind, n_rec, static_cast<const R*>(d_rec), e->K, static_cast<const R*>(e->d_phik.p),
+                                       static_cast<const R*>(e->d_lamdak.p), static_cast<const R*>(f.cx.p),
+                                       static_cast<const R*>(f.cy.p), nx, row0, nrows, static_cast<R>(e->lx * e->ly),
+                                       static_cast<R*>(d_field), s));
+  EEA_HIP(hipEventRecord(f.ev_used, s));
   return EEA_OK;
 }
 
@@ -1054,8 +1127,9 @@ void eea_destroy(eea_engine* e)
   }
   DevBuf* bufs[] = { &e->d_phik, &e->d_lamdak, &e->d_phi, &e->d_axis, &e->d_cx, &e->d_cy,
                      &e->d_work, &e->d_gauss, &e->d_sum, &e->d_ut1, &e->d_traj1, &e->d_mem1, &e->d_rstage,
-                     &e->d_lut, &e->d_raw, &e->d_occ };
+                     &e->d_lut, &e->d_raw, &e->d_occ, &e->field.axis, &e->field.cx, &e->field.cy };
   for (DevBuf* b : bufs) b->release();
+  if (e->field.ev_used) (void)hipEventDestroy(e->field.ev_used);
   for (auto& w : e->sum_ws) {
     w->ws.release();
     w->ctr.release();
@@ -1317,6 +1391,36 @@ eea_status eea_target_grid_size(const eea_engine* e, unsigned* nx, unsigned* ny)
   *nx = e->nx;
   *ny = e->ny;
   return EEA_OK;
+}
+
+eea_status eea_records_field(eea_engine* e, int kind, unsigned n_rec, const void* d_rec, unsigned nx, unsigned ny_total,
+                             unsigned row0, unsigned nrows, void* d_field, void* stream)
+{
+  // every argument check comes before the engine is read and before any HIP call
+  if (e == nullptr || d_rec == nullptr || d_field == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  if (n_rec == 0 || nx == 0 || ny_total == 0 || nrows == 0) {
+    return fail(EEA_ERR_INVALID_ARGUMENT, "n_rec, nx, ny_total and nrows must be positive");
+  }
+  if (row0 > ny_total || nrows > ny_total - row0) return fail(EEA_ERR_INVALID_ARGUMENT, "row0 + nrows > ny_total");
+  if (kind != EEA_FIELD_DENSITY && kind != EEA_FIELD_DEFICIT && kind != EEA_FIELD_POTENTIAL) {
+    return fail(EEA_ERR_INVALID_ARGUMENT, "unknown field kind");
+  }
+  if (static_cast<unsigned long long>(nx) * ny_total > (1ull << 31)) {
+    return fail(EEA_ERR_UNSUPPORTED, "field grid: nx * ny_total <= 2^31");
+  }
+  // (the axis tables are indexed with int: (nx + ny_total) * K < 2^31 for every K <= 32)
+  if (static_cast<unsigned long long>(nx) + ny_total > (1ull << 26) - 1) {
+    return fail(EEA_ERR_UNSUPPORTED, "field grid: nx + ny_total < 2^26");
+  }
+  if (!e->have_phik) return fail(EEA_ERR_NO_TARGET, "no phi_k: call eea_config_domain or eea_set_target_grid first");
+  if (reinterpret_cast<uintptr_t>(d_field) % e->rs != 0 || reinterpret_cast<uintptr_t>(d_rec) % e->rs != 0) {
+    return fail(EEA_ERR_INVALID_ARGUMENT, "d_rec / d_field are not aligned to the engine's real");
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const eea_status st = eea::engine_enter(e, s);  // the device, and behind a rebuild that was only enqueued on another stream
+  if (st != EEA_OK) return st;
+  return e->f32 ? records_field_impl<float>(e, kind, n_rec, d_rec, nx, ny_total, row0, nrows, d_field, s)
+                : records_field_impl<double>(e, kind, n_rec, d_rec, nx, ny_total, row0, nrows, d_field, s);
 }
 
 eea_status eea_get_target_grid(eea_engine* e, double* h_phi_vals)

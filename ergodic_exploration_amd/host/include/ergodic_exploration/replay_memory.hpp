@@ -90,4 +90,13 @@ inline void recordsMetric(eea_engine* e, unsigned int n_rec, const void* d_rec, 
 {
   throw_on_error(eea_records_metric(e, n_rec, d_rec, d_metric, d_ck, stream));
 }
+
+// the same records as maps on the target grid: d_field [n_rec][nrows][nx] = the band-limited visit density, the deficit
+// against the target or the potential control() descends (kind: EEA_FIELD_*), rows row0 .. row0 + nrows - 1 of an
+// nx x ny_total grid in the Fourier frame (eea_records_field)
+inline void recordsField(eea_engine* e, int kind, unsigned int n_rec, const void* d_rec, unsigned int nx,
+                         unsigned int ny_total, unsigned int row0, unsigned int nrows, void* d_field, void* stream = nullptr)
+{
+  throw_on_error(eea_records_field(e, kind, n_rec, d_rec, nx, ny_total, row0, nrows, d_field, stream));
+}
 }  // namespace ergodic_exploration

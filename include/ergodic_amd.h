@@ -644,6 +644,35 @@ eea_status eea_replay_history_records(eea_engine* e, eea_replay* r, void* d_rec,
  * EEA_ERR_INVALID_ARGUMENT: e, d_rec or d_metric null, n_rec == 0; EEA_ERR_NO_TARGET: no phi_k yet. */
 eea_status eea_records_metric(eea_engine* e, unsigned n_rec, const void* d_rec, void* d_metric, void* d_ck, void* stream);
 
+/* ---- coverage fields (additive to ABI 6: detect by symbol) -----------------------------------------------------------------
+ * What the metric summarises, as maps: n_rec sum records d_rec [n_rec][eea_ck_record_len(e)] -- history records, the fleet
+ * record, an all-reduced record, the consensus records of control passes -- taken back from the K^2 cosine coefficients to
+ * the grid configTarget builds (ergodic_control.hpp:387-408; Fourier frame, x_i and y_j by repeated += resolution from 0, the
+ * sequence of eea_set_target_grid).  The reference has no counterpart beyond publishing its target (Target::markers).
+ * d_field [n_rec][nrows][nx] reals of the engine's `real`, x fastest (the layout of eea_set_target_grid's phi_vals); row r of
+ * record j is grid row row0 + r of a grid of nx x ny_total points, which need not be the target grid's own size; row0 = 0,
+ * nrows = ny_total: the whole grid; a rank that holds a row tile asks for its rows as with eea_spatial_coeff_rows.  With
+ * c_m = rec[m] / rec[K^2] (0 for every m where rec[K^2] <= 0, the rule of eea_records_metric), m = k2 K + k1:
+ *     field[j][r][i] = sum_m a_m cos((k1 (pi / lx)) x_i) cos((k2 (pi / ly)) y_{row0 + r})          (basis.cpp:85's grouping)
+ *   EEA_FIELD_DENSITY    a_m = w_k1 w_k2 c_m / (lx ly), w_0 = 1, w_k = 2: the band-limited visit density (w_k / l is the inverse
+ *                        squared norm of cos(k pi x / l) on [0, l]); its mean over the domain is 1 / (lx ly);
+ *   EEA_FIELD_DEFICIT    a_m = w_k1 w_k2 (phi_m - c_m) / (lx ly): positive where the target wants more than the record has
+ *                        delivered; an all-zero record gives the band-limited target itself;
+ *   EEA_FIELD_POTENTIAL  a_m = lamda_m (c_m - phi_m): the potential whose gradient, times expl_weight, is edx
+ *                        (ergodic_control.hpp:418-436); unweighted, as eea_records_metric is.
+ * lx, ly, phi_k, lamda_k: the engine's current ones.  Asynchronous on `stream`; ordered behind an in-flight
+ * eea_config_domain_async rebuild as eea_records_metric is.  The axis tables are cached per (nx, ny_total, lx, ly) in buffers
+ * of the field's own (the phi_k path's tables are never touched): a repeated call reads nothing on the host, allocates nothing
+ * and makes no synchronising call; a first call, or one after a change, builds them (and waits for the device when it has to
+ * grow them).  A record's field is a pure function of the record, the domain, phi_k and the grid point, the modes added in a
+ * fixed order: a record alone gives the bits it gives inside a batch, a row tile the bits of the same rows of the whole grid.
+ * Before any launch -- EEA_ERR_INVALID_ARGUMENT: e, d_rec or d_field null (or not aligned to the engine's real); n_rec, nx,
+ * ny_total or nrows 0; row0 + nrows > ny_total; an unknown kind.  EEA_ERR_UNSUPPORTED: nx * ny_total > 2^31 (or an axis of
+ * 2^26 points and more).  EEA_ERR_NO_TARGET: no phi_k yet.  Every K (1 .. 32) and both precisions. */
+typedef enum { EEA_FIELD_DENSITY = 0, EEA_FIELD_DEFICIT = 1, EEA_FIELD_POTENTIAL = 2 } eea_field_kind;
+eea_status eea_records_field(eea_engine* e, int kind, unsigned n_rec, const void* d_rec, unsigned nx, unsigned ny_total,
+                             unsigned row0, unsigned nrows, void* d_field, void* stream);
+
 /* The collision / DWA / tick calls keep small device caches between calls (the ring offsets per radii, one
  * inflated-map buffer per (device, stream)).  A long-running process that changes streams or map sizes
  * can drop them; synchronises the devices involved.  No reference counterpart. */
