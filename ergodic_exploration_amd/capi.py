@@ -211,6 +211,8 @@ def lib():
         L.eea_replay_counts.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_ulonglong)]
         L.eea_replay_read.argtypes = [C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p]
         L.eea_replay_reset.argtypes = [C.c_void_p, C.c_void_p]
+        L.eea_replay_pool_sample.argtypes = [C.c_void_p, C.c_uint64, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint,
+                                             C.c_void_p]
         L.eea_replay_history_records.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.eea_records_metric.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.eea_records_field.argtypes = [C.c_void_p, C.c_int, C.c_uint, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_uint,
@@ -643,6 +645,14 @@ class ReplayMemory:
             if rc != 0:
                 check(rc)
         return call
+
+    def sample_pool(self, draw, n_cols, mem_cols, n_mem, exclude_self=False, accumulate=False, mem_stride=None, stream=None):
+        """eea_replay_pool_sample: up to n_cols columns per robot from the pooled history of ALL robots of this object
+        (exclude_self: without the robot's own poses); accumulate: behind the n_mem[b] columns the row already holds (after
+        sample / append_sample on the same stream), clipped at the stride; asynchronous, two launches"""
+        stride = mem_cols.shape[1] if mem_stride is None else mem_stride
+        check(lib().eea_replay_pool_sample(self.h, draw, n_cols, 1 if exclude_self else 0, 1 if accumulate else 0, _ptr(mem_cols),
+                                           _ptr(n_mem), stride, C.c_void_p(stream or 0)))
 
     def counts(self):
         """(poses stored per robot [B], appends dropped by full stores in total); waits for the device"""

@@ -13,6 +13,10 @@
 // tests/test_replay_memory.py): counter (j, robot0 + b, draw_lo, draw_hi), key (seed_lo, seed_hi); r64 = out[0] | out[1] << 32;
 // index = (r64 * n) >> 64.  A draw is a pure function of (seed, draw, global robot id, column): reproducible, and
 // independent of how the fleet is sharded.
+//
+// The POOLED memory (eea_replay_pool_sample, at the end of the kernels below): the columns of a robot drawn from the stored
+// poses of ALL robots of the object, optionally without its own -- two launches, an exclusive 64-bit prefix sum of count[B]
+// and a sampler of the form of replay_sample_kernel that looks the owner of a pool index up in the offsets.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -31,6 +35,7 @@ struct eea_replay
   void* d_store = nullptr;                  // [B][capacity][3] reals
   unsigned* d_count = nullptr;              // [B] stored poses
   unsigned long long* d_dropped = nullptr;  // [B] appends refused because the store was full
+  unsigned long long* d_pool_off = nullptr;  // [B + 1] pool offsets, rewritten by every eea_replay_pool_sample on its stream
 };
 
 namespace eea
@@ -157,6 +162,144 @@ __global__ void __launch_bounds__(kWave* kRobotsPerBlock) replay_sample_kernel(r
   }
 }
 
+// ---- the pooled memory: eea_replay_pool_sample ------------------------------------------------------------------------------
+// The pool is every stored pose of every robot in robot-major order (the order of the store): robot q owns the pool indices
+// [off[q], off[q + 1]), off = the exclusive prefix sum of count[], N = off[B].  Two launches ordered by the stream: the
+// offsets, then the sampler.  A robot's columns come from OTHER robots' rows, which are complete only when the append launch
+// in front has finished: the sampler is ordered behind it by the stream and never fused with it; no wavefront of either
+// kernel waits for another workgroup.
+constexpr unsigned kScanThreads = 1024;
+constexpr unsigned kCoarseMax = 1024;  // entries of the coarse offset table in LDS (8 KB)
+
+// off[0 .. B] = exclusive prefix sum of count[0 .. B), 64-bit.  ONE workgroup: chunks of 1024 counts (coalesced loads), per
+// chunk a wavefront scan by shuffles, one LDS hop for the 16 wavefront totals, and the carry of the chunks in front in a
+// register every thread keeps (all threads add the same total).  65 536 robots are 64 chunks.
+__global__ void __launch_bounds__(kScanThreads) pool_offsets_kernel(const unsigned* count, unsigned long long* off, unsigned B)
+{
+  __shared__ unsigned long long wave_total[kScanThreads / kWave];
+  const unsigned lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
+  unsigned long long carry = 0;
+  for (unsigned first = 0; first < B; first += kScanThreads) {  // (uniform trip count: every thread meets every barrier)
+    const unsigned i = first + threadIdx.x;
+    const unsigned long long own = i < B ? count[i] : 0u;
+    unsigned long long incl = own;
+#pragma unroll
+    for (unsigned d = 1; d < kWave; d *= 2) {
+      const unsigned long long up = __shfl_up(incl, d);
+      if (lane >= d) incl += up;
+    }
+    if (lane == kWave - 1) wave_total[wave] = incl;
+    __syncthreads();
+    unsigned long long before = 0, chunk = 0;
+#pragma unroll
+    for (unsigned w = 0; w < kScanThreads / kWave; ++w) {  // 16 LDS reads, the same address in every lane: broadcasts
+      const unsigned long long t = wave_total[w];
+      if (w < wave) before += t;
+      chunk += t;
+    }
+    if (i < B) off[i] = carry + before + incl - own;
+    carry += chunk;
+    __syncthreads();  // wave_total is rewritten by the next chunk
+  }
+  if (threadIdx.x == 0) off[B] = carry;
+}
+
+struct PoolParams
+{
+  unsigned B, capacity, robot0, mem_stride, n_cols, stride, n_coarse;  // stride (a power of two) x n_coarse >= B
+  int exclude_self, accumulate;
+  uint32_t key_lo, key_hi, draw_lo, draw_hi;
+};
+
+// One WAVEFRONT per robot, lanes along the column index, as replay_sample_kernel.  off[] is read-only here (the launch in
+// front wrote it), so every lane reads off[b], off[b + 1], off[B] itself; the one word this launch reads AND writes is
+// n_mem[b] (accumulate), and ONLY LANE 0 touches it: it loads the base once, hands it to the other lanes in a register
+// (__shfl) and stores the new value once.
+// Owner of a pool index g < N: the last q with off[q] <= g (so off[q] <= g < off[q + 1]: a robot without poses, whose
+// offset equals the next one, is never the last).  Two levels: every `stride`-th offset of off[0 .. B) staged in LDS by the
+// workgroup (n_coarse <= 1024 entries; B <= 1024: the whole table), a binary search there, and the last log2(stride) steps
+// in off[] itself, which a fleet's wavefronts keep hot in L2.
+template <typename real>
+__global__ void __launch_bounds__(kWave* kRobotsPerBlock) pool_sample_kernel(const real* store, const unsigned long long* off,
+                                                                            real* mem_cols, int* n_mem, PoolParams q)
+{
+  __shared__ unsigned long long coarse[kCoarseMax];
+  for (unsigned i = threadIdx.x; i < q.n_coarse; i += kWave * kRobotsPerBlock) coarse[i] = off[static_cast<size_t>(i) * q.stride];
+  __syncthreads();
+  const unsigned lane = threadIdx.x % kWave;
+  const unsigned b = blockIdx.x * kRobotsPerBlock + threadIdx.x / kWave;
+  if (b >= q.B) return;  // (behind the barrier; the same for all lanes of a wavefront: the __shfl below sees all 64)
+  const unsigned long long off_b = off[b];
+  const unsigned long long own = q.exclude_self ? off[b + 1] - off_b : 0ull;  // the robot's own poses, when they are left out
+  const unsigned long long n_pool = off[q.B] - own;
+  const bool all = n_pool <= q.n_cols;  // buffer.cpp:75-89: all poses in pool order; :91-108: n_cols draws
+  unsigned cols = all ? static_cast<unsigned>(n_pool) : q.n_cols;
+  unsigned base = 0;
+  if (q.accumulate) {
+    if (lane == 0) {
+      const int have = n_mem[b];
+      base = have > 0 ? static_cast<unsigned>(have) : 0u;
+    }
+    base = __shfl(base, 0);
+    const unsigned room = base < q.mem_stride ? q.mem_stride - base : 0u;
+    if (cols > room) cols = room;  // a clipped robot keeps the FIRST columns of its sequence: column j depends on j alone
+  }
+  if (lane == 0) n_mem[b] = static_cast<int>(base + cols);
+  real* const out_b = mem_cols + 3 * (static_cast<size_t>(b) * q.mem_stride + base);
+  for (unsigned j = lane; j < cols; j += kWave) {
+    unsigned long long g = j;
+    if (!all) {
+      const Philox r = philox4x32_10(j, q.robot0 + b, q.draw_lo, q.draw_hi, q.key_lo, q.key_hi);
+      const uint64_t r64 = static_cast<uint64_t>(r.v[0]) | (static_cast<uint64_t>(r.v[1]) << 32);
+      g = __umul64hi(r64, n_pool);  // uniform on [0, n_pool - 1], bias <= n_pool / 2^64
+    }
+    if (g >= off_b) g += own;  // (own == 0 unless the robot's poses are left out: then its segment is skipped)
+    unsigned lo = 0, hi = q.n_coarse;  // coarse[lo] <= g, (hi == n_coarse or coarse[hi] > g); coarse[0] == 0
+    while (hi - lo > 1) {
+      const unsigned mid = (lo + hi) / 2;
+      if (coarse[mid] <= g) lo = mid; else hi = mid;
+    }
+    lo *= q.stride;
+    hi = lo + q.stride < q.B ? lo + q.stride : q.B;  // off[lo] <= g < off[hi] (off[B] = N > g)
+    while (hi - lo > 1) {
+      const unsigned mid = (lo + hi) / 2;
+      if (off[mid] <= g) lo = mid; else hi = mid;
+    }
+    const size_t slot = static_cast<size_t>(lo) * q.capacity + static_cast<size_t>(g - off[lo]);
+    const Pose<real> c = load_pose(store, slot);
+    out_b[3 * static_cast<size_t>(j) + 0] = c.x;
+    out_b[3 * static_cast<size_t>(j) + 1] = c.y;
+    out_b[3 * static_cast<size_t>(j) + 2] = c.th;
+  }
+}
+
+template <typename real>
+hipError_t launch_pool(const eea_replay* r, uint64_t draw, unsigned n_cols, int exclude_self, int accumulate, void* d_mem_cols,
+                       int* d_n_mem, unsigned mem_stride, hipStream_t s)
+{
+  hipLaunchKernelGGL(pool_offsets_kernel, dim3(1), dim3(kScanThreads), 0, s, r->d_count, r->d_pool_off, r->B);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return err;
+  unsigned stride = 1;
+  while ((r->B + stride - 1) / stride > kCoarseMax) stride *= 2;  // B < 2^31: no overflow
+  const PoolParams q{r->B,
+                     r->capacity,
+                     r->robot0,
+                     mem_stride,
+                     n_cols,
+                     stride,
+                     (r->B + stride - 1) / stride,
+                     exclude_self != 0 ? 1 : 0,
+                     accumulate != 0 ? 1 : 0,
+                     static_cast<uint32_t>(r->seed),
+                     static_cast<uint32_t>(r->seed >> 32) ^ 0x9E3779B9u,  // apart from the own-memory draws at the same (draw, robot, j)
+                     static_cast<uint32_t>(draw),
+                     static_cast<uint32_t>(draw >> 32)};
+  hipLaunchKernelGGL(pool_sample_kernel<real>, dim3((r->B + kRobotsPerBlock - 1) / kRobotsPerBlock), dim3(kWave * kRobotsPerBlock),
+                     0, s, static_cast<const real*>(r->d_store), r->d_pool_off, static_cast<real*>(d_mem_cols), d_n_mem, q);
+  return hipGetLastError();
+}
+
 template <typename real>
 hipError_t launch_append(const eea_replay* r, const void* d_pose, const int* d_mask, hipStream_t s)
 {
@@ -236,6 +379,7 @@ eea_status eea_replay_create(int device, unsigned B, unsigned capacity, unsigned
   if (err == hipSuccess) err = hipMalloc(&r->d_store, bytes);
   if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&r->d_count), sizeof(unsigned) * B);
   if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&r->d_dropped), sizeof(unsigned long long) * B);
+  if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&r->d_pool_off), sizeof(unsigned long long) * (static_cast<size_t>(B) + 1));
   if (err == hipSuccess) err = hipMemset(r->d_count, 0, sizeof(unsigned) * B);
   if (err == hipSuccess) err = hipMemset(r->d_dropped, 0, sizeof(unsigned long long) * B);
   if (err != hipSuccess) {
@@ -251,11 +395,12 @@ eea_status eea_replay_create(int device, unsigned B, unsigned capacity, unsigned
 void eea_replay_destroy(eea_replay* r)
 {
   if (r == nullptr) return;
-  if (r->d_store != nullptr || r->d_count != nullptr || r->d_dropped != nullptr) {
+  if (r->d_store != nullptr || r->d_count != nullptr || r->d_dropped != nullptr || r->d_pool_off != nullptr) {
     if (hipSetDevice(r->device) == hipSuccess) {
       if (r->d_store != nullptr) (void)hipFree(r->d_store);  // waits for its users
       if (r->d_count != nullptr) (void)hipFree(r->d_count);
       if (r->d_dropped != nullptr) (void)hipFree(r->d_dropped);
+      if (r->d_pool_off != nullptr) (void)hipFree(r->d_pool_off);
     }
   }
   delete r;
@@ -291,6 +436,23 @@ eea_status eea_replay_append_sample(eea_replay* r, const void* d_pose, const int
   hipStream_t s = static_cast<hipStream_t>(stream);
   EEA_HIP(r->real_size == 8 ? (eea::launch_sample<double, true>(r, d_pose, d_mask, draw, d_mem_cols, d_n_mem, mem_stride, s))
                             : (eea::launch_sample<float, true>(r, d_pose, d_mask, draw, d_mem_cols, d_n_mem, mem_stride, s)));
+  return EEA_OK;
+}
+
+eea_status eea_replay_pool_sample(eea_replay* r, uint64_t draw, unsigned n_cols, int exclude_self, int accumulate,
+                                  void* d_mem_cols, int* d_n_mem, unsigned mem_stride, void* stream)
+{
+  if (r == nullptr || d_mem_cols == nullptr || d_n_mem == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  if (n_cols == 0) return fail(EEA_ERR_INVALID_ARGUMENT, "pooled sample: n_cols must be at least 1");
+  if (mem_stride == 0) return fail(EEA_ERR_INVALID_ARGUMENT, "pooled sample: mem_stride must be at least 1");
+  if (accumulate == 0 && mem_stride < n_cols) {
+    return fail(EEA_ERR_INVALID_ARGUMENT, "pooled sample: mem_stride must be at least n_cols unless the columns are accumulated");
+  }
+  EEA_HIP(hipSetDevice(r->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  EEA_HIP(r->real_size == 8
+            ? eea::launch_pool<double>(r, draw, n_cols, exclude_self, accumulate, d_mem_cols, d_n_mem, mem_stride, s)
+            : eea::launch_pool<float>(r, draw, n_cols, exclude_self, accumulate, d_mem_cols, d_n_mem, mem_stride, s));
   return EEA_OK;
 }
 

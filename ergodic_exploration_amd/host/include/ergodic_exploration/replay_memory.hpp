@@ -45,6 +45,15 @@ public:
   {
     throw_on_error(eea_replay_append_sample(r_, d_pose, d_mask, tick, d_mem_cols, d_n_mem, mem_stride, stream));
   }
+  // up to n_cols columns per robot from the POOLED history of all robots of this object (exclude_self: without the robot's
+  // own poses); accumulate: behind the d_n_mem[b] columns the row already holds -- appendSample(..), then
+  // samplePool(.., accumulate = true, ..) on the same buffers and stream puts the fleet's past behind the robot's own
+  void samplePool(std::uint64_t tick, unsigned int n_cols, void* d_mem_cols, int* d_n_mem, unsigned int mem_stride,
+                  bool exclude_self = false, bool accumulate = false, void* stream = nullptr)
+  {
+    throw_on_error(eea_replay_pool_sample(r_, tick, n_cols, exclude_self ? 1 : 0, accumulate ? 1 : 0, d_mem_cols, d_n_mem,
+                                          mem_stride, stream));
+  }
   // poses stored per robot (ReplayBuffer::size); waits for the device
   std::vector<unsigned int> sizes() const
   {

@@ -614,6 +614,34 @@ eea_status eea_replay_counts(eea_replay* r, unsigned* h_count, unsigned long lon
 eea_status eea_replay_read(eea_replay* r, unsigned b, unsigned first, unsigned n, void* h_cols);
 /* empties every robot's store and zeroes the drop counter.  Asynchronous. */
 eea_status eea_replay_reset(eea_replay* r, void* stream);
+/* The POOLED memory (additive to ABI 6: detect by symbol): columns for every robot drawn from the stored poses of ALL B robots
+ * of `r` -- the shared past of decentralised ergodic control (the reference README's ref. [2]) in the slot sampleMemory's
+ * columns take; the estimator keeps the form of buffer.cpp:64-111 (all poses in order while they fit, :75-89; otherwise
+ * uniform draws with replacement, :91-108).  The control kernels are handed other columns and compute what they computed.
+ * The pool: the stored poses in robot-major order -- robot 0's slots 0 .. n_0 - 1, then robot 1's, ...; off[q] = sum_{p<q} n_p
+ * (64-bit), N = off[B]; the counts are the ones the device holds at the call's place in the stream (behind earlier appends
+ * on it).  Robot b: N_b = N - n_b with exclude_self != 0 (the pool without its own poses), N otherwise; w = min(N_b, n_cols)
+ * columns.  N_b <= n_cols: column j is pool pose j (N_b == 0: nothing).  Otherwise column j is the pool pose
+ * g = (r64 * N_b) >> 64 (N_b a 64-bit factor; bias <= N_b / 2^64), r64 = out[0] | out[1] << 32 of Philox4x32-10 with counter
+ * (j, robot0 + b, draw_lo, draw_hi) and key (seed_lo, seed_hi ^ 0x9E3779B9): the xor keeps these draws apart from the robot's
+ * own-memory draws at the same (draw, robot, column), which would otherwise sit at the same relative position of both pools.
+ * With exclude_self, g >= off[b] stands for g + n_b.  The pose of g: robot q = the last one with off[q] <= g (a robot without
+ * poses is never chosen), slot g - off[q].
+ * accumulate == 0: the columns go to [0, w) of row b of d_mem_cols [B][mem_stride][3], d_n_mem[b] = w, columns past w are not
+ * written.  accumulate != 0: base = d_n_mem[b] as the device holds it at that place in the stream (below 0 counts as 0); the
+ * columns go to [base, base + w') with w' = min(w, mem_stride - base) (0 when base >= mem_stride), d_n_mem[b] = base + w'; a
+ * clipped robot gets the first w' columns of its sequence.  Pooled columns behind the robot's own: eea_replay_append_sample,
+ * then this call with accumulate on the same buffers and the same stream.
+ * EEA_ERR_INVALID_ARGUMENT, before any launch: r, d_mem_cols or d_n_mem null; n_cols == 0; mem_stride == 0; accumulate == 0
+ * and mem_stride < n_cols.  EEA_ERR_HIP: a launch failed.
+ * Asynchronous on `stream`: two launches (the offsets, then the sampler; a robot's columns come from other robots' rows, so
+ * the call is ordered behind an append by the stream, never fused with it); a repeated call reads nothing on the host,
+ * allocates nothing and makes no synchronising call.  The offsets buffer (B + 1 64-bit words) belongs to `r` and is allocated
+ * by eea_replay_create; every call rewrites it, so the calls on one eea_replay are issued on one stream or ordered by the
+ * caller.  Ranks: the pool is the object's own robots -- a fleet sharded over ranks pools per rank, robot0 enters only the
+ * counter; a pool across ranks is not built. */
+eea_status eea_replay_pool_sample(eea_replay* r, uint64_t draw, unsigned n_cols, int exclude_self, int accumulate,
+                                  void* d_mem_cols, int* d_n_mem, unsigned mem_stride, void* stream);
 
 /* ---- coverage of a fleet's history (additive to ABI 6, after eea_replay_*: detect these entries by symbol) ------------------
  * How ergodic is what the fleet has done so far: eps = sum_k lamda_k (c_k - phi_k)^2, the metric whose gradient control()
