@@ -41,16 +41,29 @@ unsigned axis_length(double lower, double upper, double resolution)
   return static_cast<unsigned>(std::round((upper - lower) / resolution));
 }
 
+// Device memory that goes with its owner: a member of the engine (freed by `delete e`, after eea_destroy has stopped
+// everything that reads it) or a local of one call.  Never of static storage duration: a free during static destruction
+// would run after the HIP runtime has gone.
 struct DevBuf
 {
   void* p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.detach(); }
+  DevBuf& operator=(DevBuf&& o) noexcept
+  {
+    if (this != &o) {
+      release();
+      cap = o.cap;
+      p = o.detach();
+    }
+    return *this;
+  }
+  ~DevBuf() { release(); }
   hipError_t reserve(size_t bytes)
   {
     if (bytes <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
+    release();
     const hipError_t e = hipMalloc(&p, bytes);
     if (e == hipSuccess) cap = bytes;
     return e;
@@ -58,8 +71,80 @@ struct DevBuf
   void release()
   {
     if (p) (void)hipFree(p);
+    detach();
+  }
+  // the pointer, no longer owned (buffers retired behind an event: sum_workspace)
+  void* detach()
+  {
+    void* const q = p;
     p = nullptr;
     cap = 0;
+    return q;
+  }
+};
+
+// device pointers cross the C ABI and sit in DevBuf untyped: as<R>(p) is p as reals of the call's precision
+template <typename R>
+R* as(void* p)
+{
+  return static_cast<R*>(p);
+}
+template <typename R>
+const R* as(const void* p)
+{
+  return static_cast<const R*>(p);
+}
+
+// Accumulated grid coordinates and the cos tables built from them (cx [K][nx], cy [ny][K]) of ONE grid and domain.  The
+// coordinates 0, res, res + res, ... (ergodic_control.hpp:387-408) depend only on the resolution: one array serves both
+// axes of every grid, generated once and extended when a larger grid appears -- no upload on a repeated call.  The key
+// says which tables cx / cy hold: a repeated call on the same grid and domain reuses them.  When the buffers may be
+// replaced or rewritten under earlier launches is the owner's business (the phi_k path and eea_records_field differ).
+struct AxisTables
+{
+  DevBuf axis, cx, cy;
+  unsigned axis_n = 0;
+  unsigned nx = 0, ny = 0;  // key (0: none)
+  double lx = 0.0, ly = 0.0;
+
+  bool holds(unsigned nx_, unsigned ny_, double lx_, double ly_) const { return nx == nx_ && ny == ny_ && lx == lx_ && ly == ly_; }
+  void forget() { nx = ny = 0; }
+  // records the key once the launch that writes the tables is enqueued: a failure before must not leave it on tables that
+  // were never written
+  void remember(unsigned nx_, unsigned ny_, double lx_, double ly_)
+  {
+    nx = nx_;
+    ny = ny_;
+    lx = lx_;
+    ly = ly_;
+  }
+  // at least n coordinates: repeated += resolution from 0, cast per element (blocking upload)
+  template <typename R>
+  eea_status extend_axis(unsigned n, double resolution)
+  {
+    if (n <= axis_n) return EEA_OK;
+    unsigned count = axis_n ? 2 * axis_n : 2048;
+    if (count < n) count = n;
+    std::vector<R> v(count);
+    double x = 0.0;
+    for (unsigned i = 0; i < count; ++i) {
+      v[i] = static_cast<R>(x);
+      x += resolution;
+    }
+    axis_n = 0;
+    EEA_HIP(axis.reserve(sizeof(R) * count));
+    EEA_HIP(hipMemcpy(axis.p, v.data(), sizeof(R) * count, hipMemcpyHostToDevice));
+    axis_n = count;
+    return EEA_OK;
+  }
+  // one launch on s writes both tables (cx / cy hold nx * K and ny * K reals) and records the key
+  template <typename R>
+  eea_status launch(unsigned nx_, unsigned ny_, int K, double lx_, double ly_, hipStream_t s)
+  {
+    EEA_HIP(eea::launch_axis_tables<R>(as<R>(axis.p), nx_, ny_, K, static_cast<R>(eea::kPi / lx_), static_cast<R>(eea::kPi / ly_),
+                                       as<R>(cx.p), as<R>(cy.p), s));
+    remember(nx_, ny_, lx_, ly_);
+    return EEA_OK;
   }
 };
 
@@ -81,7 +166,8 @@ struct eea_engine
   size_t rs = 8;  // sizeof(real)
   int chunk = 128;
 
-  // Basis state (basis_.lx_, ly_ start at 0: ergodic_control.hpp:208)
+  // Basis state (basis_.lx_, ly_ start at 0: ergodic_control.hpp:208): the domain of the phi_k the engine holds, written by
+  // commit_phik alone
   double lx = 0.0, ly = 0.0, map_x = 0.0, map_y = 0.0;
   bool have_phik = false;
   std::vector<double> mu, sigma;  // target Gaussians, map frame
@@ -96,13 +182,8 @@ struct eea_engine
   // filled when eea_get_target_grid asks for it, from the Gaussians as they were at the rebuild (Fourier frame)
   bool fill_deferred = false;
   std::vector<double> fill_gauss;  // [n][4] of the last rebuild: mean - map_pos, diag(cov_inv)
-  DevBuf d_phi, d_axis, d_cx, d_cy, d_work, d_gauss, d_sum;
-  // accumulated grid coordinates 0, res, res + res, ... (ergodic_control.hpp:387-408): one device array serves
-  // both axes of every grid of this engine (the resolution is fixed); grown on demand
-  unsigned axis_n = 0;
-  // key of the cos tables in d_cx / d_cy: a repeated rebuild / row tile on the same grid and domain reuses them
-  unsigned tab_nx = 0, tab_ny = 0;
-  double tab_lx = 0.0, tab_ly = 0.0;
+  DevBuf d_phi, d_work, d_gauss, d_sum;
+  AxisTables tab;         // of the last rebuild / row tile
   bool have_lut = false;  // the entropy decode table is uploaded once
   hipEvent_t ev_done = nullptr;  // completion of a rebuild: polled (a few microseconds earlier than a blocking wait)
   // a rebuild that was only enqueued (eea_config_domain_async): control calls on OTHER streams wait for this event
@@ -111,16 +192,10 @@ struct eea_engine
   bool rebuild_pending = false;
   DevBuf d_lut, d_raw, d_occ;  // occupancy targets: decode table, un-normalised sums, staged cells
 
-  // eea_records_field's OWN coordinates and cos tables (cx [K][nx], cy [ny][K]), keyed like the phi_k path's and apart from
-  // them: a field on another grid never evicts d_cx / d_cy / d_work and adds no wait to a rebuild
-  struct FieldTables
-  {
-    DevBuf axis, cx, cy;
-    unsigned axis_n = 0, nx = 0, ny = 0;
-    double lx = 0.0, ly = 0.0;
-    hipEvent_t ev_used = nullptr;  // behind the last field launch: tables are rewritten in place only after it
-  };
-  FieldTables field;
+  // eea_records_field's OWN tables, apart from the phi_k path's: a field on another grid never evicts tab / d_work and adds no
+  // wait to a rebuild
+  AxisTables field;
+  hipEvent_t ev_field_used = nullptr;  // behind the last field launch: its tables are rewritten in place only after it
   std::mutex field_mutex;
 
   // workspaces of eea_ck_records_sum (group records of both levels + the tickets of its tree), one per distinct output
@@ -176,6 +251,19 @@ void to_real(const double* in, R* out, size_t n)
   for (size_t i = 0; i < n; ++i) out[i] = static_cast<R>(in[i]);
 }
 
+// f(float{}) or f(double{}) by the engine's precision: what a call does is written once, with R = the type of f's argument
+template <typename F>
+auto by_precision(const eea_engine* e, F&& f)
+{
+  return e->f32 ? f(float{}) : f(double{});
+}
+
+// n doubles of the caller as the engine's reals in host memory (the mirror of download_reals)
+void store_reals(const eea_engine* e, const double* in, void* out, size_t n)
+{
+  by_precision(e, [&](auto r) { to_real(in, as<decltype(r)>(out), n); });
+}
+
 eea_status use_device(const eea_engine* e)
 {
   EEA_HIP(hipSetDevice(e->cfg.device));
@@ -228,62 +316,55 @@ eea_status upload_lamdak(eea_engine* e)
   return EEA_OK;
 }
 
-// coordinates of configTarget's grid: repeated += resolution (ergodic_control.hpp:387-408).  The sequence does
-// not depend on the domain, only on the resolution, so it is generated once per engine (and extended when a
-// larger grid appears): no upload, no synchronisation on the rebuild path.
+// The one place a new phi_k becomes the engine's: the domain it was formed on (fill_params and engine_view read it, and
+// eea_config_domain compares the next map with it) and the generation the resident single-robot workgroup restarts on.
+// Called once the last launch or copy of the call that forms phi_k has been issued successfully -- a call that fails
+// leaves the engine on the domain of the phi_k it still holds.
+void commit_phik(eea_engine* e, double lx, double ly)
+{
+  e->lx = lx;
+  e->ly = ly;
+  e->have_phik = true;
+  ++e->phik_gen;
+}
+
+// the phi_k path's coordinates (e->tab.axis): extended behind everything on the device, no synchronisation otherwise
 template <typename R>
 eea_status ensure_axis(eea_engine* e, unsigned n)
 {
-  if (n <= e->axis_n) return EEA_OK;
-  unsigned cap = e->axis_n ? 2 * e->axis_n : 2048;
-  if (cap < n) cap = n;
-  std::vector<R> v(cap);
-  double x = 0.0;
-  for (unsigned i = 0; i < cap; ++i) {
-    v[i] = static_cast<R>(x);
-    x += e->cfg.resolution;
-  }
+  if (n <= e->tab.axis_n) return EEA_OK;
   EEA_HIP(hipDeviceSynchronize());  // kernels of earlier rebuilds may still read the old array
-  EEA_HIP(e->d_axis.reserve(sizeof(R) * cap));
-  EEA_HIP(hipMemcpy(e->d_axis.p, v.data(), sizeof(R) * cap, hipMemcpyHostToDevice));
-  e->axis_n = cap;
-  return EEA_OK;
+  return e->tab.extend_axis<R>(n, e->cfg.resolution);
 }
 
-// cos tables of the current domain (e->lx, e->ly) on an nx x ny grid: one launch, reused while grid and domain
-// stay the same
-// returns through *stale whether the tables have to be (re)computed; the caller that fuses their computation
-// into its own launch passes stale != nullptr, everybody else gets the separate table launch
+// The phi_k path's cos tables (e->tab) of the domain (lx, ly) on an nx x ny grid, and d_work for the streaming pass over
+// that grid: one launch, reused while grid and domain stay the same.
+// Returns through *stale whether the tables have to be (re)computed; the caller that fuses their computation into its own
+// launch passes stale != nullptr (and records the key once that launch is enqueued), everybody else gets the separate
+// table launch
 template <typename R>
-eea_status upload_axes_and_tables(eea_engine* e, unsigned nx, unsigned ny, hipStream_t s, bool* stale = nullptr)
+eea_status upload_axes_and_tables(eea_engine* e, unsigned nx, unsigned ny, double lx, double ly, hipStream_t s,
+                                  bool* stale = nullptr)
 {
   if (stale) *stale = false;
-  eea_status st = ensure_axis<R>(e, nx > ny ? nx : ny);
+  AxisTables& t = e->tab;
+  const eea_status st = ensure_axis<R>(e, nx > ny ? nx : ny);
   if (st != EEA_OK) return st;
   const size_t need_cx = sizeof(R) * nx * e->K, need_cy = sizeof(R) * ny * e->K;
   const size_t need_work = sizeof(R) * eea::spatial_work_elems(nx, ny, e->K);
-  if (need_cx > e->d_cx.cap || need_cy > e->d_cy.cap || need_work > e->d_work.cap) {
+  if (need_cx > t.cx.cap || need_cy > t.cy.cap || need_work > e->d_work.cap) {
     EEA_HIP(hipDeviceSynchronize());  // the buffers about to be replaced may still be in use
-    EEA_HIP(e->d_cx.reserve(need_cx));
-    EEA_HIP(e->d_cy.reserve(need_cy));
+    EEA_HIP(t.cx.reserve(need_cx));
+    EEA_HIP(t.cy.reserve(need_cy));
     EEA_HIP(e->d_work.reserve(need_work));
-    e->tab_nx = e->tab_ny = 0;
+    t.forget();
   }
-  if (e->tab_nx == nx && e->tab_ny == ny && e->tab_lx == e->lx && e->tab_ly == e->ly) return EEA_OK;
-  const R pi_lx = static_cast<R>(eea::kPi / e->lx), pi_ly = static_cast<R>(eea::kPi / e->ly);
+  if (t.holds(nx, ny, lx, ly)) return EEA_OK;
   if (stale) {
-    // the caller computes the tables inside its own launch and records the key once that launch is enqueued: a
-    // failure in between must not leave the key on tables that were never written
     *stale = true;
     return EEA_OK;
   }
-  EEA_HIP(eea::launch_axis_tables<R>(static_cast<const R*>(e->d_axis.p), nx, ny, e->K, pi_lx, pi_ly,
-                                     static_cast<R*>(e->d_cx.p), static_cast<R*>(e->d_cy.p), s));
-  e->tab_nx = nx;
-  e->tab_ny = ny;
-  e->tab_lx = e->lx;
-  e->tab_ly = e->ly;
-  return EEA_OK;
+  return t.launch<R>(nx, ny, e->K, lx, ly, s);
 }
 
 // A row tile is launched with ny = nrows and its tile geometry is recomputed from nrows; the rows-per-tile
@@ -298,8 +379,6 @@ eea_status reserve_tile_work(eea_engine* e, unsigned nx, unsigned ny_total, unsi
   return EEA_OK;
 }
 
-// Target::fill + Basis::spatialCoeff on the device: three launches (tables + fill, streaming pass, final sums
-// with the normalisation folded in) and ONE host synchronisation at the end
 // orders stream s behind a rebuild that was only enqueued on another stream (no-op once it has completed)
 eea_status order_after_rebuild(eea_engine* e, hipStream_t s)
 {
@@ -320,49 +399,30 @@ eea_status finish_rebuild(eea_engine* e)
   return EEA_OK;
 }
 
-// eea_records_field: the axis tables of the current domain on an nx x ny grid in the field's own buffers.  Unchanged
-// (nx, ny, lx, ly): nothing happens here.  Otherwise one table launch on s, behind the last field launch of any stream; a
-// grid larger than the buffers waits for the device before they are replaced (first call / change only).
+// eea_records_field: the axis tables of the domain (lx, ly) on an nx x ny grid in the field's own buffers (e->field; the
+// caller holds field_mutex).  Unchanged (nx, ny, lx, ly): nothing happens here.  Otherwise one table launch on s, behind
+// the last field launch of any stream; a grid larger than the buffers waits for the device before they are replaced (first
+// call / change only).
 template <typename R>
-eea_status field_tables(eea_engine* e, unsigned nx, unsigned ny, hipStream_t s)
+eea_status field_tables(eea_engine* e, unsigned nx, unsigned ny, double lx, double ly, hipStream_t s)
 {
-  eea_engine::FieldTables& f = e->field;
-  if (f.nx == nx && f.ny == ny && f.lx == e->lx && f.ly == e->ly) return EEA_OK;
+  AxisTables& f = e->field;
+  if (f.holds(nx, ny, lx, ly)) return EEA_OK;
   const unsigned n = nx > ny ? nx : ny;
   const size_t need_cx = sizeof(R) * nx * e->K, need_cy = sizeof(R) * ny * e->K;
   const bool grow = n > f.axis_n || need_cx > f.cx.cap || need_cy > f.cy.cap;
-  f.nx = f.ny = 0;  // (a failure below leaves no key on tables that were never written)
+  f.forget();  // (a failure below leaves no key on tables that were never written)
   if (grow) EEA_HIP(hipDeviceSynchronize());  // field kernels may still read the buffers about to be replaced
-  if (n > f.axis_n) {
-    // the coordinate sequence of ensure_axis: repeated += resolution from 0 (ergodic_control.hpp:387-408)
-    unsigned cap = f.axis_n ? 2 * f.axis_n : 2048;
-    if (cap < n) cap = n;
-    std::vector<R> v(cap);
-    double x = 0.0;
-    for (unsigned i = 0; i < cap; ++i) {
-      v[i] = static_cast<R>(x);
-      x += e->cfg.resolution;
-    }
-    f.axis_n = 0;
-    EEA_HIP(f.axis.reserve(sizeof(R) * cap));
-    EEA_HIP(hipMemcpy(f.axis.p, v.data(), sizeof(R) * cap, hipMemcpyHostToDevice));
-    f.axis_n = cap;
-  }
+  const eea_status st = f.extend_axis<R>(n, e->cfg.resolution);
+  if (st != EEA_OK) return st;
   EEA_HIP(f.cx.reserve(need_cx));
   EEA_HIP(f.cy.reserve(need_cy));
-  if (f.ev_used == nullptr) {
-    EEA_HIP(hipEventCreateWithFlags(&f.ev_used, hipEventDisableTiming));
+  if (e->ev_field_used == nullptr) {
+    EEA_HIP(hipEventCreateWithFlags(&e->ev_field_used, hipEventDisableTiming));
   } else if (!grow) {
-    EEA_HIP(hipStreamWaitEvent(s, f.ev_used, 0));  // a field launch of another stream may still read the old tables
+    EEA_HIP(hipStreamWaitEvent(s, e->ev_field_used, 0));  // a field launch of another stream may still read the old tables
   }
-  const R pi_lx = static_cast<R>(eea::kPi / e->lx), pi_ly = static_cast<R>(eea::kPi / e->ly);
-  EEA_HIP(eea::launch_axis_tables<R>(static_cast<const R*>(f.axis.p), nx, ny, e->K, pi_lx, pi_ly, static_cast<R*>(f.cx.p),
-                                     static_cast<R*>(f.cy.p), s));
-  f.nx = nx;
-  f.ny = ny;
-  f.lx = e->lx;
-  f.ly = e->ly;
-  return EEA_OK;
+  return f.launch<R>(nx, ny, e->K, lx, ly, s);
 }
 
 template <typename R>
@@ -370,27 +430,83 @@ eea_status records_field_impl(eea_engine* e, int kind, unsigned n_rec, const voi
                               unsigned row0, unsigned nrows, void* d_field, hipStream_t s)
 {
   std::lock_guard<std::mutex> lock(e->field_mutex);
-  const eea_status st = field_tables<R>(e, nx, ny_total, s);
+  const eea_status st = field_tables<R>(e, nx, ny_total, e->lx, e->ly, s);
   if (st != EEA_OK) return st;
-  const eea_engine::FieldTables& f = e->field;
-  EEA_HIP(eea::launch_records_field<R>(kind, n_rec, static_cast<const R*>(d_rec), e->K, static_cast<const R*>(e->d_phik.p),
-                                       static_cast<const R*>(e->d_lamdak.p), static_cast<const R*>(f.cx.p),
-                                       static_cast<const R*>(f.cy.p), nx, row0, nrows, static_cast<R>(e->lx * e->ly),
-                                       static_cast<R*>(d_field), s));
-  EEA_HIP(hipEventRecord(f.ev_used, s));
+  EEA_HIP(eea::launch_records_field<R>(kind, n_rec, as<R>(d_rec), e->K, as<R>(e->d_phik.p), as<R>(e->d_lamdak.p),
+                                       as<R>(e->field.cx.p), as<R>(e->field.cy.p), nx, row0, nrows,
+                                       static_cast<R>(e->lx * e->ly), as<R>(d_field), s));
+  EEA_HIP(hipEventRecord(e->ev_field_used, s));
   return EEA_OK;
 }
 
-template <typename R>
-eea_status rebuild_phik(eea_engine* e, hipStream_t s, bool wait)
+// Gaussians as Target::fill takes them, [n][4]: the mean translated into the Fourier frame (target.hpp:99) and the
+// diagonal of cov_inv = inv(diagmat(sigma^2)) (target.hpp:69; 2x2 inverse), formed in double
+std::vector<double> gauss_params(unsigned n, const double* mu, const double* sigma, double trans_x, double trans_y)
 {
-  {  // the engine's grid / table / phi_k buffers: behind a rebuild still in flight on another stream
-    const eea_status st0 = order_after_rebuild(e, s);
-    if (st0 != EEA_OK) return st0;
+  std::vector<double> g(static_cast<size_t>(4) * n);
+  for (unsigned i = 0; i < n; ++i) {
+    const double a = sigma[2 * i] * sigma[2 * i], d = sigma[2 * i + 1] * sigma[2 * i + 1];
+    const double det = a * d - 0.0 * 0.0;
+    g[4 * i + 0] = mu[2 * i] - trans_x;
+    g[4 * i + 1] = mu[2 * i + 1] - trans_y;
+    g[4 * i + 2] = d / det;
+    g[4 * i + 3] = a / det;
   }
+  return g;
+}
+// ... and by value in the arguments of a launch, cast to its precision (at most kMaxGaussArgs of them)
+template <typename R>
+eea::GaussArgs<R> gauss_args(const std::vector<double>& g)
+{
+  eea::GaussArgs<R> ga;
+  std::memset(&ga, 0, sizeof(ga));
+  ga.n = static_cast<int>(g.size() / 4);
+  for (int i = 0; i < ga.n; ++i) {
+    for (int c = 0; c < 4; ++c) ga.g[i][c] = static_cast<R>(g[4 * i + c]);
+  }
+  return ga;
+}
+
+// The event the last launch of a rebuild is bound to: the one other streams and the getters wait for when the rebuild is
+// only enqueued, none when this call waits itself
+eea_status rebuild_event(eea_engine* e, bool wait, hipEvent_t* ev)
+{
+  *ev = nullptr;
+  if (wait) return EEA_OK;
+  if (e->ev_rebuild == nullptr) EEA_HIP(hipEventCreateWithFlags(&e->ev_rebuild, hipEventDisableTiming | hipEventDisableSystemFence));
+  *ev = e->ev_rebuild;
+  return EEA_OK;
+}
+// ... and behind that launch on s: wait for it, or leave it enqueued -- whatever follows on s is ordered by the stream,
+// other streams wait for the event (order_after_rebuild, finish_rebuild).  Then phi_k is the engine's.
+eea_status rebuild_issued(eea_engine* e, double lx, double ly, hipStream_t s, bool wait)
+{
+  if (wait) {
+    const eea_status st = wait_stream_spin(e, s);
+    if (st != EEA_OK) return st;
+    e->rebuild_pending = false;
+  } else {
+    e->rebuild_stream = s;
+    e->rebuild_pending = true;
+  }
+  commit_phik(e, lx, ly);
+  e->have_fill_grid = true;
+  e->phi_is_raw = true;
+  return EEA_OK;
+}
+
+// Target::fill + Basis::spatialCoeff of the Gaussian target on the domain (lx, ly), on the device: one launch from the
+// per-axis factors, or three (tables + fill, streaming pass, final sums with the normalisation folded in); ONE host
+// synchronisation at the end (wait) or none (enqueue only)
+template <typename R>
+eea_status rebuild_phik(eea_engine* e, double lx, double ly, hipStream_t s, bool wait)
+{
+  // the engine's grid / table / phi_k buffers: behind a rebuild still in flight on another stream
+  eea_status st = order_after_rebuild(e, s);
+  if (st != EEA_OK) return st;
   // Add 1 to include the boundary (ergodic_control.hpp:383-385)
-  const unsigned nx = axis_length(0.0, e->lx, e->cfg.resolution) + 1;
-  const unsigned ny = axis_length(0.0, e->ly, e->cfg.resolution) + 1;
+  const unsigned nx = axis_length(0.0, lx, e->cfg.resolution) + 1;
+  const unsigned ny = axis_length(0.0, ly, e->cfg.resolution) + 1;
   const size_t P = static_cast<size_t>(nx) * ny;
   if (P == 0 || P > (static_cast<size_t>(1) << 31)) {
     return fail(EEA_ERR_UNSUPPORTED, "target grid size out of range");
@@ -398,122 +514,70 @@ eea_status rebuild_phik(eea_engine* e, hipStream_t s, bool wait)
   e->nx = nx;
   e->ny = ny;
   const int ng = static_cast<int>(e->mu.size() / 2);
-  // Gaussian parameters as the reference prepares them: mean translated into the Fourier
-  // frame (target.hpp:99), cov_inv = inv(diagmat(sigma^2)) (target.hpp:69; 2x2 inverse)
-  std::vector<R> g(static_cast<size_t>(4) * (ng ? ng : 1));
-  e->fill_gauss.assign(static_cast<size_t>(4) * ng, 0.0);
-  for (int i = 0; i < ng; ++i) {
-    const double a = e->sigma[2 * i] * e->sigma[2 * i], d = e->sigma[2 * i + 1] * e->sigma[2 * i + 1];
-    const double det = a * d - 0.0 * 0.0;
-    e->fill_gauss[4 * i + 0] = e->mu[2 * i] - e->map_x;
-    e->fill_gauss[4 * i + 1] = e->mu[2 * i + 1] - e->map_y;
-    e->fill_gauss[4 * i + 2] = d / det;
-    e->fill_gauss[4 * i + 3] = a / det;
-    for (int c = 0; c < 4; ++c) g[4 * i + c] = static_cast<R>(e->fill_gauss[4 * i + c]);
-  }
+  e->fill_gauss = gauss_params(ng, e->mu.data(), e->sigma.data(), e->map_x, e->map_y);
+  hipEvent_t ev = nullptr;
   // A sum of axis-aligned Gaussians on the rectangular grid factors per axis, and so do phi_k and the mass: ONE launch
   // of one workgroup, (nx + ny)(G + K) transcendentals, no grid (gaussian_phik_kernel).  The grid itself is filled only
   // when eea_get_target_grid asks for it.  EEA_OPT_REBUILD_IMPL = 1 forces the streaming form below (A/B, tests).
   if (ng >= 1 && ng <= eea::kMaxGaussArgs && eea::option(EEA_OPT_REBUILD_IMPL) != 1 &&
       eea::gaussian_phik_lds_bytes(nx, ny, ng, e->K, sizeof(R)) <= 160 * 1024) {
-    eea_status st = ensure_axis<R>(e, nx > ny ? nx : ny);
+    st = ensure_axis<R>(e, nx > ny ? nx : ny);
     if (st != EEA_OK) return st;
     if (e->d_sum.cap < sizeof(R)) {
       EEA_HIP(hipDeviceSynchronize());
       EEA_HIP(e->d_sum.reserve(sizeof(R) * 64));
     }
-    eea::GaussArgs<R> ga;
-    std::memset(&ga, 0, sizeof(ga));
-    ga.n = ng;
-    for (int i = 0; i < ng; ++i) {
-      for (int c = 0; c < 4; ++c) ga.g[i][c] = g[4 * i + c];
-    }
-    if (!wait && e->ev_rebuild == nullptr) EEA_HIP(hipEventCreateWithFlags(&e->ev_rebuild, hipEventDisableTiming | hipEventDisableSystemFence));
-    EEA_HIP(eea::launch_gaussian_phik<R>(static_cast<const R*>(e->d_axis.p), nx, ny, ga, e->K,
-                                         static_cast<R>(1.0 / e->lx), static_cast<R>(1.0 / e->ly),
-                                         static_cast<R*>(e->d_phik.p), static_cast<R*>(e->d_sum.p), s,
-                                         wait ? nullptr : e->ev_rebuild));
-    if (wait) {
-      st = wait_stream_spin(e, s);
-      if (st != EEA_OK) return st;
-      e->rebuild_pending = false;
-    } else {
-      e->rebuild_stream = s;
-      e->rebuild_pending = true;
-    }
-    e->have_phik = true;
-  ++e->phik_gen;  // (the resident single-robot workgroup restarts on the next call)
-    e->have_fill_grid = true;
-    e->phi_is_raw = true;
-    e->fill_deferred = true;
-    return EEA_OK;
+    st = rebuild_event(e, wait, &ev);
+    if (st != EEA_OK) return st;
+    EEA_HIP(eea::launch_gaussian_phik<R>(as<R>(e->tab.axis.p), nx, ny, gauss_args<R>(e->fill_gauss), e->K,
+                                         static_cast<R>(1.0 / lx), static_cast<R>(1.0 / ly), as<R>(e->d_phik.p),
+                                         as<R>(e->d_sum.p), s, ev));
+    st = rebuild_issued(e, lx, ly, s, wait);
+    if (st == EEA_OK) e->fill_deferred = true;
+    return st;
   }
   e->fill_deferred = false;
+  const bool by_args = ng <= eea::kMaxGaussArgs;  // the Gaussians fit the kernel arguments
   bool tables_stale = false;
-  eea_status st = upload_axes_and_tables<R>(e, nx, ny, s, ng <= eea::kMaxGaussArgs ? &tables_stale : nullptr);
+  st = upload_axes_and_tables<R>(e, nx, ny, lx, ly, s, by_args ? &tables_stale : nullptr);
   if (st != EEA_OK) return st;
   const size_t need_phi = sizeof(R) * P;
   const int fill_blocks_args = eea::target_fill_blocks(P);
   const int fill_blocks_buf = static_cast<int>((P + eea::kBlock - 1) / eea::kBlock);
-  const size_t need_sum = sizeof(R) * (static_cast<size_t>(ng <= eea::kMaxGaussArgs ? fill_blocks_args : fill_blocks_buf) + 1);
+  const size_t need_sum = sizeof(R) * (static_cast<size_t>(by_args ? fill_blocks_args : fill_blocks_buf) + 1);
   if (need_phi > e->d_phi.cap || need_sum > e->d_sum.cap) {
     EEA_HIP(hipDeviceSynchronize());
     EEA_HIP(e->d_phi.reserve(need_phi));
     EEA_HIP(e->d_sum.reserve(need_sum));
   }
-  R* const d_mass = static_cast<R*>(e->d_sum.p);
+  AxisTables& t = e->tab;
+  R* const d_mass = as<R>(e->d_sum.p);
   R* const d_partials = d_mass + 1;
   int n_partials = 0;
-  if (ng <= eea::kMaxGaussArgs) {
-    eea::GaussArgs<R> ga;
-    std::memset(&ga, 0, sizeof(ga));
-    ga.n = ng;
-    for (int i = 0; i < ng; ++i) {
-      for (int c = 0; c < 4; ++c) ga.g[i][c] = g[4 * i + c];
-    }
+  if (by_args) {
     n_partials = fill_blocks_args;
     // the fill and (when the domain changed) the two axis tables in ONE launch
-    EEA_HIP(eea::launch_target_fill_args<R>(static_cast<const R*>(e->d_axis.p), nx, ny, ga,
-                                            static_cast<R*>(e->d_phi.p), d_partials, e->K,
-                                            static_cast<R>(eea::kPi / e->lx), static_cast<R>(eea::kPi / e->ly),
-                                            tables_stale ? static_cast<R*>(e->d_cx.p) : nullptr,
-                                            static_cast<R*>(e->d_cy.p), s));
-    if (tables_stale) {
-      e->tab_nx = nx;
-      e->tab_ny = ny;
-      e->tab_lx = e->lx;
-      e->tab_ly = e->ly;
-    }
+    EEA_HIP(eea::launch_target_fill_args<R>(as<R>(t.axis.p), nx, ny, gauss_args<R>(e->fill_gauss), as<R>(e->d_phi.p),
+                                            d_partials, e->K, static_cast<R>(eea::kPi / lx), static_cast<R>(eea::kPi / ly),
+                                            tables_stale ? as<R>(t.cx.p) : nullptr, as<R>(t.cy.p), s));
+    if (tables_stale) t.remember(nx, ny, lx, ly);
   } else {
     // more Gaussians than the kernel arguments hold: parameters through a device buffer (one more sync)
+    const std::vector<R> g(e->fill_gauss.begin(), e->fill_gauss.end());
     EEA_HIP(e->d_gauss.reserve(sizeof(R) * g.size()));
     EEA_HIP(hipMemcpyAsync(e->d_gauss.p, g.data(), sizeof(R) * g.size(), hipMemcpyHostToDevice, s));
     EEA_HIP(hipStreamSynchronize(s));
-    EEA_HIP(eea::launch_target_fill<R>(static_cast<const R*>(e->d_axis.p), static_cast<const R*>(e->d_axis.p),
-                                       nx, ny, static_cast<const R*>(e->d_gauss.p), ng,
-                                       static_cast<R*>(e->d_phi.p), d_partials, &n_partials, s));
+    EEA_HIP(eea::launch_target_fill<R>(as<R>(t.axis.p), as<R>(t.axis.p), nx, ny, as<R>(e->d_gauss.p), ng, as<R>(e->d_phi.p),
+                                       d_partials, &n_partials, s));
   }
   // phi_k = spatialCoeff(phi / sum(phi)) = spatialCoeff(phi) / sum(phi)  (target.cpp:87, basis.cpp:122-133)
   // enqueue-only form: the event other streams (and the getters) wait for is bound to the last launch itself
-  if (!wait && e->ev_rebuild == nullptr) EEA_HIP(hipEventCreateWithFlags(&e->ev_rebuild, hipEventDisableTiming | hipEventDisableSystemFence));
-  EEA_HIP(eea::launch_spatial_coeff_normalised<R>(static_cast<const R*>(e->d_phi.p), nx, ny, e->K,
-                                                  static_cast<const R*>(e->d_cx.p), static_cast<const R*>(e->d_cy.p),
-                                                  static_cast<R*>(e->d_work.p), static_cast<R*>(e->d_phik.p),
-                                                  d_partials, n_partials, d_mass, s, wait ? nullptr : e->ev_rebuild));
-  if (wait) {
-    st = wait_stream_spin(e, s);
-    if (st != EEA_OK) return st;
-    e->rebuild_pending = false;
-  } else {
-    // enqueue only: whatever follows on s is ordered by the stream; other streams wait for the event
-    e->rebuild_stream = s;
-    e->rebuild_pending = true;
-  }
-  e->have_phik = true;
-  ++e->phik_gen;  // (the resident single-robot workgroup restarts on the next call)
-  e->have_fill_grid = true;
-  e->phi_is_raw = true;
-  return EEA_OK;
+  st = rebuild_event(e, wait, &ev);
+  if (st != EEA_OK) return st;
+  EEA_HIP(eea::launch_spatial_coeff_normalised<R>(as<R>(e->d_phi.p), nx, ny, e->K, as<R>(t.cx.p), as<R>(t.cy.p),
+                                                  as<R>(e->d_work.p), as<R>(e->d_phik.p), d_partials, n_partials, d_mass, s,
+                                                  ev));
+  return rebuild_issued(e, lx, ly, s, wait);
 }
 
 // Target::fill of the last Gaussian rebuild on demand (eea_get_target_grid): the un-normalised grid into d_phi; d_sum[0]
@@ -523,51 +587,38 @@ eea_status fill_deferred_grid(eea_engine* e)
 {
   const unsigned nx = e->nx, ny = e->ny;
   const size_t P = static_cast<size_t>(nx) * ny;
-  const int ng = static_cast<int>(e->fill_gauss.size() / 4);
-  const int blocks = eea::target_fill_blocks(P);
   EEA_HIP(hipDeviceSynchronize());
   EEA_HIP(e->d_phi.reserve(sizeof(R) * P));
   DevBuf partials;  // (the fill's per-workgroup sums are not needed: the mass is already known)
-  EEA_HIP(partials.reserve(sizeof(R) * (static_cast<size_t>(blocks) + 1)));
-  eea::GaussArgs<R> ga;
-  std::memset(&ga, 0, sizeof(ga));
-  ga.n = ng;
-  for (int i = 0; i < ng; ++i) {
-    for (int c = 0; c < 4; ++c) ga.g[i][c] = static_cast<R>(e->fill_gauss[4 * i + c]);
-  }
-  const hipError_t err = eea::launch_target_fill_args<R>(static_cast<const R*>(e->d_axis.p), nx, ny, ga, static_cast<R*>(e->d_phi.p),
-                                                         static_cast<R*>(partials.p), e->K, R(0), R(0), nullptr, nullptr, nullptr);
-  const hipError_t err2 = hipDeviceSynchronize();
-  partials.release();
-  EEA_HIP(err);
-  EEA_HIP(err2);
+  EEA_HIP(partials.reserve(sizeof(R) * (static_cast<size_t>(eea::target_fill_blocks(P)) + 1)));
+  EEA_HIP(eea::launch_target_fill_args<R>(as<R>(e->tab.axis.p), nx, ny, gauss_args<R>(e->fill_gauss), as<R>(e->d_phi.p),
+                                          as<R>(partials.p), e->K, R(0), R(0), nullptr, nullptr, nullptr));
+  EEA_HIP(hipDeviceSynchronize());  // (partials goes only behind the launch)
   e->fill_deferred = false;
   return EEA_OK;
 }
 
 template <typename R>
-eea_status set_target_grid_impl(eea_engine* e, unsigned nx, unsigned ny, const void* phi_vals,
-                                int on_device, hipStream_t s)
+eea_status set_target_grid_impl(eea_engine* e, unsigned nx, unsigned ny, const void* phi_vals, int on_device, double lx,
+                                double ly, hipStream_t s)
 {
   const size_t P = static_cast<size_t>(nx) * ny;
   e->nx = nx;
   e->ny = ny;
   e->have_fill_grid = false;
-  eea_status st = upload_axes_and_tables<R>(e, nx, ny, s);
+  const eea_status st = upload_axes_and_tables<R>(e, nx, ny, lx, ly, s);
   if (st != EEA_OK) return st;
-  const R* d_phi = static_cast<const R*>(phi_vals);
+  const R* d_phi = as<R>(phi_vals);
   if (!on_device) {
     EEA_HIP(e->d_phi.reserve(sizeof(R) * P));
     EEA_HIP(hipMemcpyAsync(e->d_phi.p, phi_vals, sizeof(R) * P, hipMemcpyHostToDevice, s));
     EEA_HIP(hipStreamSynchronize(s));
-    d_phi = static_cast<const R*>(e->d_phi.p);
+    d_phi = as<R>(e->d_phi.p);
   }
-  EEA_HIP(eea::launch_spatial_coeff<R>(d_phi, nx, ny, e->K, static_cast<const R*>(e->d_cx.p),
-                                       static_cast<const R*>(e->d_cy.p), static_cast<R*>(e->d_work.p),
-                                       static_cast<R*>(e->d_phik.p), s));
+  EEA_HIP(eea::launch_spatial_coeff<R>(d_phi, nx, ny, e->K, as<R>(e->tab.cx.p), as<R>(e->tab.cy.p), as<R>(e->d_work.p),
+                                       as<R>(e->d_phik.p), s));
   EEA_HIP(hipStreamSynchronize(s));
-  e->have_phik = true;
-  ++e->phik_gen;  // (the resident single-robot workgroup restarts on the next call)
+  commit_phik(e, lx, ly);
   return EEA_OK;
 }
 
@@ -651,8 +702,7 @@ eea_status sum_workspace(eea_engine* e, const void* key, unsigned B, hipStream_t
     // CALLER-owned handle remembered from an earlier call: if the caller has destroyed it the record fails -- the event is
     // destroyed and the buffer stays in the list without one, until eea_destroy (its last launch cannot be proven complete).
     for (DevBuf* buf : { &w->ws, &w->ctr }) {
-      void* const q = buf->p;
-      if (q == nullptr) continue;
+      if (buf->p == nullptr) continue;
       hipEvent_t ev = nullptr;
       if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) ev = nullptr;
       if (ev != nullptr && hipEventRecord(ev, w->last_stream) != hipSuccess) {
@@ -660,9 +710,8 @@ eea_status sum_workspace(eea_engine* e, const void* key, unsigned B, hipStream_t
         ev = nullptr;
       }
       (void)hipGetLastError();
-      e->retired.push_back({ q, ev });
-      buf->p = nullptr;  // (ownership moved to the retired list)
-      *buf = DevBuf();
+      e->retired.push_back({ buf->p, ev });
+      (void)buf->detach();  // (ownership moved to the retired list)
     }
     EEA_HIP(w->ws.reserve(need_ws));
     EEA_HIP(w->ctr.reserve(need_ctr));
@@ -696,11 +745,11 @@ eea::ControlForm control_form(const eea::ControlParams<R>& p, unsigned B, bool s
 // the form of a batch call of B agents on this engine (eea_batch_agent_lanes, eea_batch_record_count)
 eea::ControlForm batch_form(const eea_engine* e, unsigned B)
 {
-  auto form = [e, B](auto p) {
+  return by_precision(e, [&](auto r) {
+    eea::ControlParams<decltype(r)> p;
     fill_params(e, p);
     return control_form(p, B, false);
-  };
-  return e->f32 ? form(eea::ControlParams<float>{}) : form(eea::ControlParams<double>{});
+  });
 }
 
 // One control launch of B agents in the form control_form picks, reported in *form when not null.  done: the single-agent
@@ -794,21 +843,21 @@ eea_status upload_entropy_table(eea_engine* e, hipStream_t s)
   return EEA_OK;
 }
 
-// un-normalised coefficient sums of rows [row0, row0 + nrows) of an occupancy grid
+// un-normalised coefficient sums of rows [row0, row0 + nrows) of an occupancy grid on the domain (lx, ly)
 template <typename R>
-eea_status occupancy_rows_impl(eea_engine* e, unsigned nx, unsigned ny_total, unsigned row0, unsigned nrows,
-                               const int8_t* d_occ_rows, void* d_raw_out, hipStream_t s, void* d_mass_out = nullptr)
+eea_status occupancy_rows_impl(eea_engine* e, unsigned nx, unsigned ny_total, unsigned row0, unsigned nrows, double lx,
+                               double ly, const int8_t* d_occ_rows, void* d_raw_out, hipStream_t s,
+                               void* d_mass_out = nullptr)
 {
-  eea_status st = upload_axes_and_tables<R>(e, nx, ny_total, s);
+  eea_status st = upload_axes_and_tables<R>(e, nx, ny_total, lx, ly, s);
   if (st != EEA_OK) return st;
   st = upload_entropy_table<R>(e, s);
   if (st != EEA_OK) return st;
   st = reserve_tile_work<R>(e, nx, ny_total, nrows);
   if (st != EEA_OK) return st;
-  EEA_HIP(eea::launch_spatial_coeff_cells<R>(d_occ_rows, nx, nrows, e->K, static_cast<const R*>(e->d_cx.p),
-                                             static_cast<const R*>(e->d_cy.p) + static_cast<size_t>(row0) * e->K,
-                                             static_cast<const R*>(e->d_lut.p), static_cast<R*>(e->d_work.p),
-                                             static_cast<R*>(d_raw_out), s, static_cast<R*>(d_mass_out)));
+  EEA_HIP(eea::launch_spatial_coeff_cells<R>(d_occ_rows, nx, nrows, e->K, as<R>(e->tab.cx.p),
+                                             as<R>(e->tab.cy.p) + static_cast<size_t>(row0) * e->K, as<R>(e->d_lut.p),
+                                             as<R>(e->d_work.p), as<R>(d_raw_out), s, as<R>(d_mass_out)));
   return EEA_OK;
 }
 
@@ -975,17 +1024,30 @@ eea_status control_resident(eea_engine* e, const double x[3], const double* h_me
   return EEA_OK;
 }
 
-eea_status check_engine(const eea_engine* e)
+// Prologue of the entries that launch on the engine: refuses a null engine, then the call's own arguments (bad_args: what is
+// wrong with them, null when nothing is), then selects the engine's device.
+eea_status enter_launch(const eea_engine* e, const char* bad_args = nullptr)
 {
   if (e == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null engine");
-  return EEA_OK;
+  if (bad_args != nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, bad_args);
+  return use_device(e);
+}
+
+// Prologue of the entries that write the engine's grid / table / phi_k buffers: the same, but a rebuild that was only
+// enqueued owns those buffers and is waited for first (a failed wait is reported before the arguments are).
+eea_status enter_target(eea_engine* e, const char* bad_args)
+{
+  if (e == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null engine");
+  if (finish_rebuild(e) != EEA_OK) return EEA_ERR_HIP;
+  return enter_launch(e, bad_args);
 }
 }  // namespace
 
 eea_status eea::control_batch(eea_engine* e, unsigned B, const eea_batch_io* io, void* stream, ControlForm* form,
                               unsigned n_steps, unsigned pose_step_stride, unsigned u0_step_stride)
 {
-  if (check_engine(e) != EEA_OK) return EEA_ERR_INVALID_ARGUMENT;
+  // (its refusals are of three kinds, in this order, and all come before the device is touched: no shared prologue)
+  if (e == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null engine");
   if (io == nullptr || io->d_pose == nullptr || io->d_ut == nullptr || io->d_u0 == nullptr) {
     return fail(EEA_ERR_INVALID_ARGUMENT, "d_pose, d_ut and d_u0 are required");
   }
@@ -999,13 +1061,13 @@ eea_status eea::control_batch(eea_engine* e, unsigned B, const eea_batch_io* io,
     return fail(EEA_ERR_UNSUPPORTED, "the device-bound exchange (d_rec_ready / d_ck_flag) takes one step per launch");
   }
   if (!e->have_phik) return fail(EEA_ERR_NO_TARGET, "no phi_k: call eea_config_domain or eea_set_target_grid first");
-  eea_status st = use_device(e);
-  if (st != EEA_OK) return st;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  st = order_after_rebuild(e, s);  // a phi_k rebuild that was only enqueued on another stream (eea_config_domain_async)
+  // the device, and behind a phi_k rebuild that was only enqueued on another stream (eea_config_domain_async)
+  const eea_status st = engine_enter(e, s);
   if (st != EEA_OK) return st;
-  return e->f32 ? control_batch_impl<float>(e, B, io, false, s, form, nullptr, nullptr, n_steps, pose_step_stride, u0_step_stride)
-                : control_batch_impl<double>(e, B, io, false, s, form, nullptr, nullptr, n_steps, pose_step_stride, u0_step_stride);
+  return by_precision(e, [&](auto r) {
+    return control_batch_impl<decltype(r)>(e, B, io, false, s, form, nullptr, nullptr, n_steps, pose_step_stride, u0_step_stride);
+  });
 }
 
 void eea::engine_view(const eea_engine* e, EngineView* v)
@@ -1089,7 +1151,7 @@ eea_status eea_create(const eea_config* cfg, eea_engine** out)
   e->K2 = e->K * e->K;
   e->f32 = cfg->precision == EEA_PREC_F32;
   e->rs = e->f32 ? 4 : 8;
-  eea_status st = e->f32 ? upload_lamdak<float>(e) : upload_lamdak<double>(e);
+  const eea_status st = by_precision(e, [&](auto r) { return upload_lamdak<decltype(r)>(e); });
   if (st != EEA_OK) {
     eea_destroy(e);
     return st;
@@ -1125,15 +1187,7 @@ void eea_destroy(eea_engine* e)
     (void)hipStreamSynchronize(e->stream1);
     (void)hipStreamDestroy(e->stream1);
   }
-  DevBuf* bufs[] = { &e->d_phik, &e->d_lamdak, &e->d_phi, &e->d_axis, &e->d_cx, &e->d_cy,
-                     &e->d_work, &e->d_gauss, &e->d_sum, &e->d_ut1, &e->d_traj1, &e->d_mem1, &e->d_rstage,
-                     &e->d_lut, &e->d_raw, &e->d_occ, &e->field.axis, &e->field.cx, &e->field.cy };
-  for (DevBuf* b : bufs) b->release();
-  if (e->field.ev_used) (void)hipEventDestroy(e->field.ev_used);
-  for (auto& w : e->sum_ws) {
-    w->ws.release();
-    w->ctr.release();
-  }
+  if (e->ev_field_used) (void)hipEventDestroy(e->ev_field_used);
   for (auto& r : e->retired) {
     if (r.done != nullptr) (void)hipEventDestroy(r.done);
     (void)hipFree(r.p);
@@ -1145,7 +1199,7 @@ void eea_destroy(eea_engine* e)
   if (e->h_rmail) (void)hipHostFree(e->h_rmail);
   if (e->h_rmem) (void)hipHostFree(e->h_rmem);
   if (e->stream_res) (void)hipStreamDestroy(e->stream_res);
-  delete e;
+  delete e;  // every DevBuf of the engine and of its sum workspaces
 }
 
 unsigned eea_steps(const eea_engine* e) { return e ? static_cast<unsigned>(e->T) : 0u; }
@@ -1158,7 +1212,7 @@ double eea_time_step(const eea_engine* e) { return e ? e->cfg.dt : 0.0; }
 
 eea_status eea_set_target_gaussians(eea_engine* e, unsigned n, const double* mu, const double* sigma)
 {
-  if (check_engine(e) != EEA_OK) return EEA_ERR_INVALID_ARGUMENT;
+  if (e == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null engine");
   if (n > 0 && (mu == nullptr || sigma == nullptr)) return fail(EEA_ERR_INVALID_ARGUMENT, "null target");
   e->mu.assign(mu, mu + 2 * static_cast<size_t>(n));
   e->sigma.assign(sigma, sigma + 2 * static_cast<size_t>(n));
@@ -1169,65 +1223,43 @@ eea_status eea_set_target_gaussians(eea_engine* e, unsigned n, const double* mu,
 eea_status eea_set_target_grid(eea_engine* e, unsigned nx, unsigned ny, const void* phi_vals,
                                int on_device, double lx, double ly, void* stream)
 {
-  if (check_engine(e) != EEA_OK) return EEA_ERR_INVALID_ARGUMENT;
-  if (finish_rebuild(e) != EEA_OK) return EEA_ERR_HIP;  // a rebuild that was only enqueued owns the buffers below
-  if (phi_vals == nullptr || nx == 0 || ny == 0 || !(lx > 0.0) || !(ly > 0.0)) {
-    return fail(EEA_ERR_INVALID_ARGUMENT, "bad target grid");
-  }
-  eea_status st = use_device(e);
+  // (the arguments are judged here, without touching e, and reported by the prologue in its order: null engine first, then a
+  // failed wait for an enqueued rebuild, then this message, then the device -- the same at every entry below)
+  const bool ok = phi_vals != nullptr && nx != 0 && ny != 0 && lx > 0.0 && ly > 0.0;
+  const eea_status st = enter_target(e, ok ? nullptr : "bad target grid");
   if (st != EEA_OK) return st;
-  e->lx = lx;
-  e->ly = ly;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  return e->f32 ? set_target_grid_impl<float>(e, nx, ny, phi_vals, on_device, s)
-                : set_target_grid_impl<double>(e, nx, ny, phi_vals, on_device, s);
+  return by_precision(e, [&](auto r) { return set_target_grid_impl<decltype(r)>(e, nx, ny, phi_vals, on_device, lx, ly, s); });
 }
 
 eea_status eea_spatial_coeff_rows(eea_engine* e, unsigned nx, unsigned ny_total, unsigned row0,
                                   unsigned nrows, const void* d_phi_rows, double lx, double ly,
                                   void* d_phik_partial, void* stream)
 {
-  if (check_engine(e) != EEA_OK) return EEA_ERR_INVALID_ARGUMENT;
-  if (finish_rebuild(e) != EEA_OK) return EEA_ERR_HIP;  // a rebuild that was only enqueued owns the buffers below
-  if (d_phi_rows == nullptr || d_phik_partial == nullptr || nx == 0 || ny_total == 0 || nrows == 0 ||
-      row0 + nrows > ny_total || !(lx > 0.0) || !(ly > 0.0)) {
-    return fail(EEA_ERR_INVALID_ARGUMENT, "bad grid tile");
-  }
-  eea_status st = use_device(e);
-  if (st != EEA_OK) return st;
+  const bool ok = d_phi_rows != nullptr && d_phik_partial != nullptr && nx != 0 && ny_total != 0 && nrows != 0 &&
+                  row0 + nrows <= ny_total && lx > 0.0 && ly > 0.0;
+  const eea_status st0 = enter_target(e, ok ? nullptr : "bad grid tile");
+  if (st0 != EEA_OK) return st0;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const double keep_lx = e->lx, keep_ly = e->ly;
-  e->lx = lx;  // the tables are built for the tile's domain; the engine's own domain is restored
-  e->ly = ly;
-  st = e->f32 ? upload_axes_and_tables<float>(e, nx, ny_total, s) : upload_axes_and_tables<double>(e, nx, ny_total, s);
-  e->lx = keep_lx;
-  e->ly = keep_ly;
-  if (st != EEA_OK) return st;
-  st = e->f32 ? reserve_tile_work<float>(e, nx, ny_total, nrows) : reserve_tile_work<double>(e, nx, ny_total, nrows);
-  if (st != EEA_OK) return st;
-  if (e->f32) {
-    EEA_HIP(eea::launch_spatial_coeff<float>(static_cast<const float*>(d_phi_rows), nx, nrows, e->K,
-                                             static_cast<const float*>(e->d_cx.p),
-                                             static_cast<const float*>(e->d_cy.p) + static_cast<size_t>(row0) * e->K,
-                                             static_cast<float*>(e->d_work.p), static_cast<float*>(d_phik_partial), s));
-  } else {
-    EEA_HIP(eea::launch_spatial_coeff<double>(static_cast<const double*>(d_phi_rows), nx, nrows, e->K,
-                                              static_cast<const double*>(e->d_cx.p),
-                                              static_cast<const double*>(e->d_cy.p) + static_cast<size_t>(row0) * e->K,
-                                              static_cast<double*>(e->d_work.p), static_cast<double*>(d_phik_partial), s));
-  }
-  return EEA_OK;
+  return by_precision(e, [&](auto r) {
+    using R = decltype(r);
+    // the tables are built for the tile's domain; the engine's own domain is not involved
+    eea_status st = upload_axes_and_tables<R>(e, nx, ny_total, lx, ly, s);
+    if (st != EEA_OK) return st;
+    st = reserve_tile_work<R>(e, nx, ny_total, nrows);
+    if (st != EEA_OK) return st;
+    EEA_HIP(eea::launch_spatial_coeff<R>(as<R>(d_phi_rows), nx, nrows, e->K, as<R>(e->tab.cx.p),
+                                         as<R>(e->tab.cy.p) + static_cast<size_t>(row0) * e->K, as<R>(e->d_work.p),
+                                         as<R>(d_phik_partial), s));
+    return EEA_OK;
+  });
 }
 
 eea_status eea_set_target_occupancy(eea_engine* e, unsigned nx, unsigned ny, const int8_t* occ,
                                     int on_device, double lx, double ly, void* stream)
 {
-  if (check_engine(e) != EEA_OK) return EEA_ERR_INVALID_ARGUMENT;
-  if (finish_rebuild(e) != EEA_OK) return EEA_ERR_HIP;  // a rebuild that was only enqueued owns the buffers below
-  if (occ == nullptr || nx == 0 || ny == 0 || !(lx > 0.0) || !(ly > 0.0)) {
-    return fail(EEA_ERR_INVALID_ARGUMENT, "bad occupancy grid");
-  }
-  eea_status st = use_device(e);
+  const bool ok = occ != nullptr && nx != 0 && ny != 0 && lx > 0.0 && ly > 0.0;
+  eea_status st = enter_target(e, ok ? nullptr : "bad occupancy grid");
   if (st != EEA_OK) return st;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const size_t P = static_cast<size_t>(nx) * ny;
@@ -1238,8 +1270,6 @@ eea_status eea_set_target_occupancy(eea_engine* e, unsigned nx, unsigned ny, con
     EEA_HIP(hipStreamSynchronize(s));
     d_occ = static_cast<const int8_t*>(e->d_occ.p);
   }
-  e->lx = lx;
-  e->ly = ly;
   e->nx = nx;
   e->ny = ny;
   e->have_fill_grid = false;
@@ -1247,12 +1277,12 @@ eea_status eea_set_target_occupancy(eea_engine* e, unsigned nx, unsigned ny, con
   // the whole grid on this engine: the reduction launch normalises by mode (0, 0)'s sum itself (phi_k / sum(phi), target.cpp:87) --
   // two launches, the same bits as sums -> launch_normalise_by_first (which the row-tiled multi-rank form still uses, behind its
   // all-reduce); the normaliser goes to d_raw[0]
-  st = e->f32 ? occupancy_rows_impl<float>(e, nx, ny, 0, ny, d_occ, e->d_phik.p, s, e->d_raw.p)
-              : occupancy_rows_impl<double>(e, nx, ny, 0, ny, d_occ, e->d_phik.p, s, e->d_raw.p);
+  st = by_precision(e, [&](auto r) {
+    return occupancy_rows_impl<decltype(r)>(e, nx, ny, 0, ny, lx, ly, d_occ, e->d_phik.p, s, e->d_raw.p);
+  });
   if (st != EEA_OK) return st;
   EEA_HIP(hipStreamSynchronize(s));
-  e->have_phik = true;
-  ++e->phik_gen;  // (the resident single-robot workgroup restarts on the next call)
+  commit_phik(e, lx, ly);
   return EEA_OK;
 }
 
@@ -1260,66 +1290,47 @@ eea_status eea_spatial_coeff_occupancy_rows(eea_engine* e, unsigned nx, unsigned
                                             unsigned nrows, const int8_t* d_occ_rows, double lx, double ly,
                                             void* d_sums_partial, void* stream)
 {
-  if (check_engine(e) != EEA_OK) return EEA_ERR_INVALID_ARGUMENT;
-  if (finish_rebuild(e) != EEA_OK) return EEA_ERR_HIP;  // a rebuild that was only enqueued owns the buffers below
-  if (d_occ_rows == nullptr || d_sums_partial == nullptr || nx == 0 || ny_total == 0 || nrows == 0 ||
-      row0 + nrows > ny_total || !(lx > 0.0) || !(ly > 0.0)) {
-    return fail(EEA_ERR_INVALID_ARGUMENT, "bad occupancy tile");
-  }
-  eea_status st = use_device(e);
+  const bool ok = d_occ_rows != nullptr && d_sums_partial != nullptr && nx != 0 && ny_total != 0 && nrows != 0 &&
+                  row0 + nrows <= ny_total && lx > 0.0 && ly > 0.0;
+  const eea_status st = enter_target(e, ok ? nullptr : "bad occupancy tile");
   if (st != EEA_OK) return st;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const double keep_lx = e->lx, keep_ly = e->ly;
-  e->lx = lx;  // the tables are built for the tile's domain; the engine's own domain is restored
-  e->ly = ly;
-  st = e->f32 ? occupancy_rows_impl<float>(e, nx, ny_total, row0, nrows, d_occ_rows, d_sums_partial, s)
-              : occupancy_rows_impl<double>(e, nx, ny_total, row0, nrows, d_occ_rows, d_sums_partial, s);
-  e->lx = keep_lx;
-  e->ly = keep_ly;
-  return st;
+  // (the tables are built for the tile's domain; the engine's own domain is not involved)
+  return by_precision(e, [&](auto r) {
+    return occupancy_rows_impl<decltype(r)>(e, nx, ny_total, row0, nrows, lx, ly, d_occ_rows, d_sums_partial, s);
+  });
 }
 
 eea_status eea_set_phik(eea_engine* e, const void* phik, int on_device, double lx, double ly)
 {
-  if (check_engine(e) != EEA_OK) return EEA_ERR_INVALID_ARGUMENT;
-  if (finish_rebuild(e) != EEA_OK) return EEA_ERR_HIP;  // a rebuild that was only enqueued owns the buffers below
-  if (phik == nullptr || !(lx > 0.0) || !(ly > 0.0)) return fail(EEA_ERR_INVALID_ARGUMENT, "bad phi_k");
-  eea_status st = use_device(e);
+  const bool ok = phik != nullptr && lx > 0.0 && ly > 0.0;
+  const eea_status st = enter_target(e, ok ? nullptr : "bad phi_k");
   if (st != EEA_OK) return st;
   EEA_HIP(hipMemcpy(e->d_phik.p, phik, e->rs * e->K2, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-  e->lx = lx;
-  e->ly = ly;
-  e->have_phik = true;
-  ++e->phik_gen;  // (the resident single-robot workgroup restarts on the next call)
+  commit_phik(e, lx, ly);
   return EEA_OK;
 }
 
 eea_status eea_set_phik_from_sums(eea_engine* e, const void* d_sums, double lx, double ly, void* stream)
 {
-  if (check_engine(e) != EEA_OK) return EEA_ERR_INVALID_ARGUMENT;
-  if (finish_rebuild(e) != EEA_OK) return EEA_ERR_HIP;  // a rebuild that was only enqueued owns the buffers below
-  if (d_sums == nullptr || !(lx > 0.0) || !(ly > 0.0)) return fail(EEA_ERR_INVALID_ARGUMENT, "bad sums");
-  eea_status st = use_device(e);
-  if (st != EEA_OK) return st;
+  const bool ok = d_sums != nullptr && lx > 0.0 && ly > 0.0;
+  const eea_status st0 = enter_target(e, ok ? nullptr : "bad sums");
+  if (st0 != EEA_OK) return st0;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (e->f32) {
-    EEA_HIP(eea::launch_normalise_by_first<float>(static_cast<const float*>(d_sums), e->K2,
-                                                  static_cast<float*>(e->d_phik.p), s));
-  } else {
-    EEA_HIP(eea::launch_normalise_by_first<double>(static_cast<const double*>(d_sums), e->K2,
-                                                   static_cast<double*>(e->d_phik.p), s));
-  }
-  e->lx = lx;
-  e->ly = ly;
-  e->have_phik = true;
-  ++e->phik_gen;  // (the resident single-robot workgroup restarts on the next call)
+  const eea_status st = by_precision(e, [&](auto r) {
+    using R = decltype(r);
+    EEA_HIP(eea::launch_normalise_by_first<R>(as<R>(d_sums), e->K2, as<R>(e->d_phik.p), s));
+    return EEA_OK;
+  });
+  if (st != EEA_OK) return st;
+  commit_phik(e, lx, ly);
   return EEA_OK;
 }
 
 static eea_status config_domain_impl(eea_engine* e, double xmin, double xmax, double ymin, double ymax, int* rebuilt,
                                      void* stream, bool wait)
 {
-  if (check_engine(e) != EEA_OK) return EEA_ERR_INVALID_ARGUMENT;
+  if (e == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null engine");
   if (rebuilt) *rebuilt = 0;
   // translation from map to fourier domain is refreshed on every call (:366-367)
   e->map_x = xmin;
@@ -1330,18 +1341,11 @@ static eea_status config_domain_impl(eea_engine* e, double xmin, double xmax, do
   if (!e->have_gauss) return fail(EEA_ERR_NO_TARGET, "configTarget before setTarget");
   eea_status st = use_device(e);
   if (st != EEA_OK) return st;
-  const double keep_lx = e->lx, keep_ly = e->ly;
-  e->lx = mx;
-  e->ly = my;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  st = e->f32 ? rebuild_phik<float>(e, s, wait) : rebuild_phik<double>(e, s, wait);
-  if (st != EEA_OK) {
-    // the reference throws out of the controller here; a failed rebuild must not leave the new extent
-    // behind (the next call would take the almost_equal early return with a stale phi_k)
-    e->lx = keep_lx;
-    e->ly = keep_ly;
-    return st;
-  }
+  // the reference throws out of the controller when this fails; the new extent becomes the engine's only with its phi_k
+  // (left behind by a failed rebuild, the next call would take the almost_equal early return with a stale phi_k)
+  st = by_precision(e, [&](auto r) { return rebuild_phik<decltype(r)>(e, mx, my, s, wait); });
+  if (st != EEA_OK) return st;
   if (rebuilt) *rebuilt = 1;
   return st;
 }
@@ -1374,14 +1378,14 @@ static eea_status download_reals(eea_engine* e, const void* d, size_t n, double*
 
 eea_status eea_get_phik(eea_engine* e, double* h_phik)
 {
-  if (check_engine(e) != EEA_OK || h_phik == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  if (e == nullptr || h_phik == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
   if (finish_rebuild(e) != EEA_OK) return EEA_ERR_HIP;
   return download_reals(e, e->d_phik.p, e->K2, h_phik);
 }
 
 eea_status eea_get_lamdak(eea_engine* e, double* h_lamdak)
 {
-  if (check_engine(e) != EEA_OK || h_lamdak == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  if (e == nullptr || h_lamdak == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
   return download_reals(e, e->d_lamdak.p, e->K2, h_lamdak);
 }
 
@@ -1419,20 +1423,21 @@ eea_status eea_records_field(eea_engine* e, int kind, unsigned n_rec, const void
   hipStream_t s = static_cast<hipStream_t>(stream);
   const eea_status st = eea::engine_enter(e, s);  // the device, and behind a rebuild that was only enqueued on another stream
   if (st != EEA_OK) return st;
-  return e->f32 ? records_field_impl<float>(e, kind, n_rec, d_rec, nx, ny_total, row0, nrows, d_field, s)
-                : records_field_impl<double>(e, kind, n_rec, d_rec, nx, ny_total, row0, nrows, d_field, s);
+  return by_precision(e, [&](auto r) {
+    return records_field_impl<decltype(r)>(e, kind, n_rec, d_rec, nx, ny_total, row0, nrows, d_field, s);
+  });
 }
 
 eea_status eea_get_target_grid(eea_engine* e, double* h_phi_vals)
 {
-  if (check_engine(e) != EEA_OK || h_phi_vals == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  if (e == nullptr || h_phi_vals == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
   if (e->nx == 0 || !e->have_fill_grid || (e->d_phi.p == nullptr && !e->fill_deferred)) {
     return fail(EEA_ERR_NO_TARGET, "no Target::fill grid on the device (explicit / occupancy targets are not kept)");
   }
   if (finish_rebuild(e) != EEA_OK) return EEA_ERR_HIP;
   const size_t P = static_cast<size_t>(e->nx) * e->ny;
   if (e->fill_deferred) {  // the Gaussian rebuild never needed the grid: fill it now (un-normalised; the mass is in d_sum[0])
-    const eea_status stf = e->f32 ? fill_deferred_grid<float>(e) : fill_deferred_grid<double>(e);
+    const eea_status stf = by_precision(e, [&](auto r) { return fill_deferred_grid<decltype(r)>(e); });
     if (stf != EEA_OK) return stf;
   }
   eea_status st = download_reals(e, e->d_phi.p, P, h_phi_vals);
@@ -1464,25 +1469,20 @@ eea_status eea_control_batch_steps(eea_engine* e, unsigned B, const eea_batch_io
 static eea_status records_sum_impl(eea_engine* e, unsigned B, const void* d_ck_rec, void* d_sum, void* stream,
                                    const unsigned* d_ready, unsigned seq, unsigned* d_flag)
 {
-  if (check_engine(e) != EEA_OK) return EEA_ERR_INVALID_ARGUMENT;
-  if (d_ck_rec == nullptr || d_sum == nullptr || B == 0) return fail(EEA_ERR_INVALID_ARGUMENT, "d_ck_rec, d_sum and B > 0 are required");
-  eea_status st = use_device(e);
-  if (st != EEA_OK) return st;
+  const bool ok = d_ck_rec != nullptr && d_sum != nullptr && B != 0;
+  const eea_status st0 = enter_launch(e, ok ? nullptr : "d_ck_rec, d_sum and B > 0 are required");
+  if (st0 != EEA_OK) return st0;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  eea_engine::SumWs* w = nullptr;
   std::lock_guard<std::mutex> lock(e->sum_mutex);  // across the launch: the workspace must not be recycled under it
-  st = e->f32 ? sum_workspace<float>(e, d_sum, B, s, &w) : sum_workspace<double>(e, d_sum, B, s, &w);
-  if (st != EEA_OK) return st;
-  if (e->f32) {
-    EEA_HIP(eea::launch_ck_records_sum<float>(static_cast<const float*>(d_ck_rec), B, e->K2, static_cast<float*>(w->ws.p),
-                                              static_cast<unsigned*>(w->ctr.p), static_cast<float*>(d_sum), s, d_ready, seq,
-                                              d_flag));
-  } else {
-    EEA_HIP(eea::launch_ck_records_sum<double>(static_cast<const double*>(d_ck_rec), B, e->K2, static_cast<double*>(w->ws.p),
-                                               static_cast<unsigned*>(w->ctr.p), static_cast<double*>(d_sum), s, d_ready, seq,
-                                               d_flag));
-  }
-  return EEA_OK;
+  return by_precision(e, [&](auto r) {
+    using R = decltype(r);
+    eea_engine::SumWs* w = nullptr;
+    const eea_status st = sum_workspace<R>(e, d_sum, B, s, &w);
+    if (st != EEA_OK) return st;
+    EEA_HIP(eea::launch_ck_records_sum<R>(as<R>(d_ck_rec), B, e->K2, as<R>(w->ws.p), static_cast<unsigned*>(w->ctr.p),
+                                          as<R>(d_sum), s, d_ready, seq, d_flag));
+    return EEA_OK;
+  });
 }
 
 eea_status eea_ck_records_sum(eea_engine* e, unsigned B, const void* d_ck_rec, void* d_sum, void* stream)
@@ -1492,8 +1492,8 @@ eea_status eea_ck_records_sum(eea_engine* e, unsigned B, const void* d_ck_rec, v
 
 eea_status eea_ck_records_sum_ws_bytes(const eea_engine* e, unsigned B, size_t* ws_bytes, size_t* ticket_bytes)
 {
-  if (check_engine(e) != EEA_OK || B == 0) return fail(EEA_ERR_INVALID_ARGUMENT, "null engine / B == 0");
-  if (ws_bytes) *ws_bytes = (e->f32 ? sizeof(float) : sizeof(double)) * eea::ck_sum_ws_elems(B, e->K2);
+  if (e == nullptr || B == 0) return fail(EEA_ERR_INVALID_ARGUMENT, "null engine / B == 0");
+  if (ws_bytes) *ws_bytes = e->rs * eea::ck_sum_ws_elems(B, e->K2);
   if (ticket_bytes) *ticket_bytes = sizeof(unsigned) * eea::ck_sum_tickets(B, e->K2);
   return EEA_OK;
 }
@@ -1502,21 +1502,16 @@ eea_status eea_ck_records_sum_ws_bytes(const eea_engine* e, unsigned B, size_t* 
 eea_status eea_ck_records_sum_ws(eea_engine* e, unsigned B, const void* d_ck_rec, void* d_sum, void* d_ws, void* d_tickets,
                                  void* stream)
 {
-  if (check_engine(e) != EEA_OK) return EEA_ERR_INVALID_ARGUMENT;
-  if (d_ck_rec == nullptr || d_sum == nullptr || d_ws == nullptr || d_tickets == nullptr || B == 0) {
-    return fail(EEA_ERR_INVALID_ARGUMENT, "d_ck_rec, d_sum, d_ws, d_tickets and B > 0 are required");
-  }
-  eea_status st = use_device(e);
+  const bool ok = d_ck_rec != nullptr && d_sum != nullptr && d_ws != nullptr && d_tickets != nullptr && B != 0;
+  const eea_status st = enter_launch(e, ok ? nullptr : "d_ck_rec, d_sum, d_ws, d_tickets and B > 0 are required");
   if (st != EEA_OK) return st;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (e->f32) {
-    EEA_HIP(eea::launch_ck_records_sum<float>(static_cast<const float*>(d_ck_rec), B, e->K2, static_cast<float*>(d_ws),
-                                              static_cast<unsigned*>(d_tickets), static_cast<float*>(d_sum), s, nullptr, 0u, nullptr));
-  } else {
-    EEA_HIP(eea::launch_ck_records_sum<double>(static_cast<const double*>(d_ck_rec), B, e->K2, static_cast<double*>(d_ws),
-                                               static_cast<unsigned*>(d_tickets), static_cast<double*>(d_sum), s, nullptr, 0u, nullptr));
-  }
-  return EEA_OK;
+  return by_precision(e, [&](auto r) {
+    using R = decltype(r);
+    EEA_HIP(eea::launch_ck_records_sum<R>(as<R>(d_ck_rec), B, e->K2, as<R>(d_ws), static_cast<unsigned*>(d_tickets), as<R>(d_sum),
+                                          s, nullptr, 0u, nullptr));
+    return EEA_OK;
+  });
 }
 
 eea_status eea_ck_records_sum_bound(eea_engine* e, unsigned B, const void* d_ck_rec, const unsigned* d_rec_ready, unsigned seq,
@@ -1528,25 +1523,23 @@ eea_status eea_ck_records_sum_bound(eea_engine* e, unsigned B, const void* d_ck_
 
 eea_status eea_publish_record(eea_engine* e, const void* d_src, void* d_pub, unsigned* d_flag, unsigned seq, void* stream)
 {
-  if (check_engine(e) != EEA_OK) return EEA_ERR_INVALID_ARGUMENT;
-  if (d_src == nullptr || d_pub == nullptr || d_flag == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
-  eea_status st = use_device(e);
+  const bool ok = d_src != nullptr && d_pub != nullptr && d_flag != nullptr;
+  const eea_status st = enter_launch(e, ok ? nullptr : "null argument");
   if (st != EEA_OK) return st;
   const int n = eea::ck_record_len(e->K2);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (e->f32) EEA_HIP(eea::launch_publish_record<float>(static_cast<const float*>(d_src), n, static_cast<float*>(d_pub), d_flag, seq, s));
-  else EEA_HIP(eea::launch_publish_record<double>(static_cast<const double*>(d_src), n, static_cast<double*>(d_pub), d_flag, seq, s));
-  return EEA_OK;
+  return by_precision(e, [&](auto r) {
+    using R = decltype(r);
+    EEA_HIP(eea::launch_publish_record<R>(as<R>(d_src), n, as<R>(d_pub), d_flag, seq, s));
+    return EEA_OK;
+  });
 }
 
 eea_status eea_rollout_batch(eea_engine* e, unsigned B, const void* d_pose, const void* d_ut,
                              void* d_traj, int* d_status, void* stream)
 {
-  if (check_engine(e) != EEA_OK) return EEA_ERR_INVALID_ARGUMENT;
-  if (d_pose == nullptr || d_ut == nullptr || d_traj == nullptr) {
-    return fail(EEA_ERR_INVALID_ARGUMENT, "d_pose, d_ut and d_traj are required");
-  }
-  eea_status st = use_device(e);
+  const bool ok = d_pose != nullptr && d_ut != nullptr && d_traj != nullptr;
+  const eea_status st = enter_launch(e, ok ? nullptr : "d_pose, d_ut and d_traj are required");
   if (st != EEA_OK) return st;
   eea_batch_io io;
   std::memset(&io, 0, sizeof(io));
@@ -1555,17 +1548,16 @@ eea_status eea_rollout_batch(eea_engine* e, unsigned B, const void* d_pose, cons
   io.d_traj = d_traj;
   io.d_status = d_status;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  return e->f32 ? control_batch_impl<float>(e, B, &io, true, s)
-                : control_batch_impl<double>(e, B, &io, true, s);
+  return by_precision(e, [&](auto r) { return control_batch_impl<decltype(r)>(e, B, &io, true, s); });
 }
 
 eea_status eea_control(eea_engine* e, double xmin, double xmax, double ymin, double ymax,
                        const double x[3], const double* h_mem_cols, unsigned n_mem, double u_out[3])
 {
-  if (check_engine(e) != EEA_OK) return EEA_ERR_INVALID_ARGUMENT;
-  if (x == nullptr || u_out == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
-  if (n_mem > 0 && h_mem_cols == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null mem_cols");
-  eea_status st = use_device(e);
+  const char* bad = nullptr;
+  if (x == nullptr || u_out == nullptr) bad = "null argument";
+  else if (n_mem > 0 && h_mem_cols == nullptr) bad = "null mem_cols";
+  eea_status st = enter_launch(e, bad);
   if (st != EEA_OK) return st;
   // pose_ = x; configTarget(grid)  (:227-230): enqueued on the same stream as the control kernel, no host wait
   st = eea_config_domain_async(e, xmin, xmax, ymin, ymax, nullptr, e->stream1);
@@ -1575,7 +1567,7 @@ eea_status eea_control(eea_engine* e, double xmin, double xmax, double ymin, dou
   // one robot, one control() per tick without a launch per call (EEA_OPT_RESIDENT_CONTROL); a replay-memory sample beyond
   // the mapped buffer takes the launch path
   if (eea::option(EEA_OPT_RESIDENT_CONTROL) != 0 && n_mem <= static_cast<unsigned>(eea::kResidentMemCols)) {
-    st = e->f32 ? control_resident<float>(e, x, h_mem_cols, n_mem, u_out) : control_resident<double>(e, x, h_mem_cols, n_mem, u_out);
+    st = by_precision(e, [&](auto r) { return control_resident<decltype(r)>(e, x, h_mem_cols, n_mem, u_out); });
     if (st != EEA_ERR_UNSUPPORTED) return st;  // (UNSUPPORTED: the shape does not fit a resident workgroup -- launch path)
   } else {
     st = resident_stop(e);  // (the option was switched off, or this call does not fit: the launch path owns d_ut1 now)
@@ -1593,14 +1585,12 @@ eea_status eea_control(eea_engine* e, double xmin, double xmax, double ymin, dou
       while (want < bytes) want *= 2;
       EEA_HIP(e->d_mem1.reserve(want));
     }
-    if (e->f32) to_real<float>(h_mem_cols, static_cast<float*>(e->h_stage), 3 * static_cast<size_t>(n_mem));
-    else std::memcpy(e->h_stage, h_mem_cols, bytes);
+    store_reals(e, h_mem_cols, e->h_stage, 3 * static_cast<size_t>(n_mem));
     EEA_HIP(hipMemcpyAsync(e->d_mem1.p, e->h_stage, bytes, hipMemcpyHostToDevice, e->stream1));
     io.d_mem_cols = e->d_mem1.p;
     io.mem_stride = n_mem;  // d_n_mem == NULL: every reserved column is valid
   }
-  if (e->f32) to_real<float>(x, reinterpret_cast<float*>(e->h_mail->pose), 3);
-  else std::memcpy(e->h_mail->pose, x, sizeof(double) * 3);
+  store_reals(e, x, e->h_mail->pose, 3);
   e->h_mail->status = 0;
   Mailbox* const dm = static_cast<Mailbox*>(e->d_mail);
   io.d_pose = dm->pose;
@@ -1608,8 +1598,7 @@ eea_status eea_control(eea_engine* e, double xmin, double xmax, double ymin, dou
   io.d_status = &dm->status;
   io.d_ut = e->d_ut1.p;
   e->mail_seq = (e->mail_seq % 1000000) + 1;
-  st = e->f32 ? control_batch_impl<float>(e, 1, &io, false, e->stream1, nullptr, &dm->done)
-              : control_batch_impl<double>(e, 1, &io, false, e->stream1, nullptr, &dm->done);
+  st = by_precision(e, [&](auto r) { return control_batch_impl<decltype(r)>(e, 1, &io, false, e->stream1, nullptr, &dm->done); });
   if (st != EEA_OK) return st;
   // the kernel publishes u0 / status and then the sequence number with a system-scope release: poll it
   // (a few microseconds earlier than the stream's completion signal); bounded, then the ordinary wait
@@ -1628,30 +1617,25 @@ eea_status eea_control(eea_engine* e, double xmin, double xmax, double ymin, dou
   if (e->h_mail->status == EEA_ERR_INVALID_TWIST) {
     return fail(EEA_ERR_INVALID_TWIST, "Invalid twist y-velocity must be 0.");
   }
-  if (e->f32) {
-    const float* u = reinterpret_cast<const float*>(e->h_mail->u0);
-    for (int i = 0; i < 3; ++i) u_out[i] = u[i];
-  } else {
-    std::memcpy(u_out, e->h_mail->u0, sizeof(double) * 3);
-  }
+  by_precision(e, [&](auto r) {
+    for (int i = 0; i < 3; ++i) u_out[i] = as<decltype(r)>(e->h_mail->u0)[i];
+  });
   return EEA_OK;
 }
 
 eea_status eea_resident_stop(eea_engine* e)
 {
-  if (check_engine(e) != EEA_OK) return fail(EEA_ERR_INVALID_ARGUMENT, "null engine");
-  eea_status st = use_device(e);
+  const eea_status st = enter_launch(e);
   if (st != EEA_OK) return st;
   return resident_stop(e);
 }
 
 eea_status eea_opt_traj(eea_engine* e, double* h_traj)
 {
-  if (check_engine(e) != EEA_OK || h_traj == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  if (e == nullptr || h_traj == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
   eea_status st = use_device(e);
   if (st != EEA_OK) return st;
-  if (e->f32) to_real<float>(e->last_pose, reinterpret_cast<float*>(e->h_mail->pose), 3);
-  else std::memcpy(e->h_mail->pose, e->last_pose, sizeof(double) * 3);
+  store_reals(e, e->last_pose, e->h_mail->pose, 3);
   e->h_mail->status = 0;
   Mailbox* const dm = static_cast<Mailbox*>(e->d_mail);
   st = eea_rollout_batch(e, 1, dm->pose, e->d_ut1.p, e->d_traj1.p, &dm->status, e->stream1);
@@ -1665,14 +1649,14 @@ eea_status eea_opt_traj(eea_engine* e, double* h_traj)
 
 eea_status eea_get_ut(eea_engine* e, double* h_ut)
 {
-  if (check_engine(e) != EEA_OK || h_ut == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  if (e == nullptr || h_ut == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
   EEA_HIP(hipStreamSynchronize(e->stream1));
   return download_reals(e, e->d_ut1.p, 3 * static_cast<size_t>(e->T), h_ut);
 }
 
 eea_status eea_set_ut(eea_engine* e, const double* h_ut)
 {
-  if (check_engine(e) != EEA_OK || h_ut == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  if (e == nullptr || h_ut == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
   eea_status st = use_device(e);
   if (st != EEA_OK) return st;
   const size_t n = 3 * static_cast<size_t>(e->T);
@@ -1681,13 +1665,14 @@ eea_status eea_set_ut(eea_engine* e, const double* h_ut)
     if (st != EEA_OK) return st;
   }
   EEA_HIP(hipStreamSynchronize(e->stream1));
+  const void* src = h_ut;  // fp64: straight from the caller, as download_reals copies straight to it
+  std::vector<float> narrowed;
   if (e->f32) {
-    std::vector<float> tmp(n);
-    to_real<float>(h_ut, tmp.data(), n);
-    EEA_HIP(hipMemcpy(e->d_ut1.p, tmp.data(), sizeof(float) * n, hipMemcpyHostToDevice));
-  } else {
-    EEA_HIP(hipMemcpy(e->d_ut1.p, h_ut, sizeof(double) * n, hipMemcpyHostToDevice));
+    narrowed.resize(n);
+    store_reals(e, h_ut, narrowed.data(), n);
+    src = narrowed.data();
   }
+  EEA_HIP(hipMemcpy(e->d_ut1.p, src, e->rs * n, hipMemcpyHostToDevice));
   return EEA_OK;
 }
 
@@ -1700,30 +1685,20 @@ static eea_status basis_points(int device, double lx, double ly, unsigned K, con
   EEA_HIP(hipSetDevice(device));
   const size_t K2 = static_cast<size_t>(K) * K;
   DevBuf dx, dy, dw, dwork, dout;
-  auto cleanup = [&]() {
-    dx.release();
-    dy.release();
-    dw.release();
-    dwork.release();
-    dout.release();
-  };
-  hipError_t err = dx.reserve(sizeof(double) * (P ? P : 1));
-  if (err == hipSuccess) err = dy.reserve(sizeof(double) * (P ? P : 1));
-  if (err == hipSuccess && ws) err = dw.reserve(sizeof(double) * (P ? P : 1));
-  if (err == hipSuccess) err = dwork.reserve(sizeof(double) * eea::point_work_elems(P, K));
-  if (err == hipSuccess) err = dout.reserve(sizeof(double) * K2);
-  if (err == hipSuccess && P) err = hipMemcpy(dx.p, xs, sizeof(double) * P, hipMemcpyHostToDevice);
-  if (err == hipSuccess && P) err = hipMemcpy(dy.p, ys, sizeof(double) * P, hipMemcpyHostToDevice);
-  if (err == hipSuccess && P && ws) err = hipMemcpy(dw.p, ws, sizeof(double) * P, hipMemcpyHostToDevice);
-  if (err == hipSuccess) {
-    err = eea::launch_point_coeff<double>(static_cast<const double*>(dx.p), static_cast<const double*>(dy.p),
-                                          ws ? static_cast<const double*>(dw.p) : nullptr, P, K,
-                                          eea::kPi / lx, eea::kPi / ly, scale,
-                                          static_cast<double*>(dwork.p), static_cast<double*>(dout.p), nullptr);
+  EEA_HIP(dx.reserve(sizeof(double) * (P ? P : 1)));
+  EEA_HIP(dy.reserve(sizeof(double) * (P ? P : 1)));
+  if (ws) EEA_HIP(dw.reserve(sizeof(double) * (P ? P : 1)));
+  EEA_HIP(dwork.reserve(sizeof(double) * eea::point_work_elems(P, K)));
+  EEA_HIP(dout.reserve(sizeof(double) * K2));
+  if (P) {
+    EEA_HIP(hipMemcpy(dx.p, xs, sizeof(double) * P, hipMemcpyHostToDevice));
+    EEA_HIP(hipMemcpy(dy.p, ys, sizeof(double) * P, hipMemcpyHostToDevice));
+    if (ws) EEA_HIP(hipMemcpy(dw.p, ws, sizeof(double) * P, hipMemcpyHostToDevice));
   }
-  if (err == hipSuccess) err = hipMemcpy(out, dout.p, sizeof(double) * K2, hipMemcpyDeviceToHost);
-  cleanup();
-  if (err != hipSuccess) return fail(EEA_ERR_HIP, std::string("basis op: ") + hipGetErrorString(err));
+  EEA_HIP(eea::launch_point_coeff<double>(as<double>(dx.p), as<double>(dy.p), ws ? as<double>(dw.p) : nullptr, P, K,
+                                          eea::kPi / lx, eea::kPi / ly, scale, as<double>(dwork.p), as<double>(dout.p),
+                                          nullptr));
+  EEA_HIP(hipMemcpy(out, dout.p, sizeof(double) * K2, hipMemcpyDeviceToHost));
   return EEA_OK;
 }
 
@@ -1765,42 +1740,34 @@ eea_status eea_rk4_rollout(int device, int model, double dt, double horizon, con
   if (steps == 0) return EEA_OK;
   EEA_HIP(hipSetDevice(device));
   DevBuf dpose, dut, dtraj, dstat;
-  hipError_t err = dpose.reserve(sizeof(double) * 3);
-  if (err == hipSuccess) err = dut.reserve(sizeof(double) * 3 * steps);
-  if (err == hipSuccess) err = dtraj.reserve(sizeof(double) * 3 * steps);
-  if (err == hipSuccess) err = dstat.reserve(sizeof(int));
-  if (err == hipSuccess) err = hipMemcpy(dpose.p, x0, sizeof(double) * 3, hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemcpy(dut.p, h_ut, sizeof(double) * 3 * steps, hipMemcpyHostToDevice);
-  int status = 0;
-  if (err == hipSuccess) {
-    eea::ControlParams<double> p;
-    std::memset(&p, 0, sizeof(p));
-    p.T = static_cast<int>(steps);
-    p.K = 1;
-    p.n_steps = 1;
-    p.chunk = 64;
-    p.dt = dt;
-    p.dt6 = dt / 6.0;
-    p.half_dt = 0.5 * dt;
-    p.lx = p.ly = 1.0;
-    p.inv_lx = p.inv_ly = 1.0;
-    p.pose = static_cast<const double*>(dpose.p);
-    p.ut = static_cast<double*>(dut.p);
-    p.traj = static_cast<double*>(dtraj.p);
-    p.status = static_cast<int*>(dstat.p);
-    if (eea::control_lds_bytes<double>(p.T, p.K, 0, p.chunk) > 160 * 1024) {
-      err = hipErrorInvalidValue;
-    } else {
-      err = eea::launch_control<double>(p, 1, model, 0, true, nullptr);
-    }
+  EEA_HIP(dpose.reserve(sizeof(double) * 3));
+  EEA_HIP(dut.reserve(sizeof(double) * 3 * steps));
+  EEA_HIP(dtraj.reserve(sizeof(double) * 3 * steps));
+  EEA_HIP(dstat.reserve(sizeof(int)));
+  EEA_HIP(hipMemcpy(dpose.p, x0, sizeof(double) * 3, hipMemcpyHostToDevice));
+  EEA_HIP(hipMemcpy(dut.p, h_ut, sizeof(double) * 3 * steps, hipMemcpyHostToDevice));
+  eea::ControlParams<double> p;
+  std::memset(&p, 0, sizeof(p));
+  p.T = static_cast<int>(steps);
+  p.K = 1;
+  p.n_steps = 1;
+  p.chunk = 64;
+  p.dt = dt;
+  p.dt6 = dt / 6.0;
+  p.half_dt = 0.5 * dt;
+  p.lx = p.ly = 1.0;
+  p.inv_lx = p.inv_ly = 1.0;
+  p.pose = as<double>(dpose.p);
+  p.ut = as<double>(dut.p);
+  p.traj = as<double>(dtraj.p);
+  p.status = static_cast<int*>(dstat.p);
+  if (eea::control_lds_bytes<double>(p.T, p.K, 0, p.chunk) > 160 * 1024) {
+    return fail(EEA_ERR_HIP, std::string("rk4 rollout: ") + hipGetErrorString(hipErrorInvalidValue));
   }
-  if (err == hipSuccess) err = hipMemcpy(&status, dstat.p, sizeof(int), hipMemcpyDeviceToHost);
-  if (err == hipSuccess && status == 0) err = hipMemcpy(h_xt, dtraj.p, sizeof(double) * 3 * steps, hipMemcpyDeviceToHost);
-  dpose.release();
-  dut.release();
-  dtraj.release();
-  dstat.release();
-  if (err != hipSuccess) return fail(EEA_ERR_HIP, std::string("rk4 rollout: ") + hipGetErrorString(err));
+  EEA_HIP(eea::launch_control<double>(p, 1, model, 0, true, nullptr));
+  int status = 0;
+  EEA_HIP(hipMemcpy(&status, dstat.p, sizeof(int), hipMemcpyDeviceToHost));
+  if (status == 0) EEA_HIP(hipMemcpy(h_xt, dtraj.p, sizeof(double) * 3 * steps, hipMemcpyDeviceToHost));
   if (status == EEA_ERR_INVALID_TWIST) return fail(EEA_ERR_INVALID_TWIST, "Invalid twist y-velocity must be 0.");
   return EEA_OK;
 }
@@ -1814,45 +1781,32 @@ eea_status eea_target_fill(int device, unsigned n_gauss, const double* mu, const
   }
   if (P == 0) return EEA_OK;
   EEA_HIP(hipSetDevice(device));
-  std::vector<double> xs(P), ys(P), g(4 * static_cast<size_t>(n_gauss ? n_gauss : 1));
+  std::vector<double> xs(P), ys(P);
   for (unsigned i = 0; i < P; ++i) {
     xs[i] = h_phi_grid[2 * static_cast<size_t>(i)];
     ys[i] = h_phi_grid[2 * static_cast<size_t>(i) + 1];
   }
-  for (unsigned i = 0; i < n_gauss; ++i) {  // target.hpp:69,99
-    const double a = sigma[2 * i] * sigma[2 * i], d = sigma[2 * i + 1] * sigma[2 * i + 1];
-    const double det = a * d - 0.0 * 0.0;
-    g[4 * i + 0] = mu[2 * i] - trans[0];
-    g[4 * i + 1] = mu[2 * i + 1] - trans[1];
-    g[4 * i + 2] = d / det;
-    g[4 * i + 3] = a / det;
-  }
+  std::vector<double> g = gauss_params(n_gauss, mu, sigma, trans[0], trans[1]);
+  if (g.empty()) g.assign(4, 0.0);  // (no Gaussian: the kernel reads none of it)
   const int blocks = static_cast<int>((P + eea::kBlock - 1) / eea::kBlock);
   DevBuf dx, dy, dg, dphi, dsum;
-  hipError_t err = dx.reserve(sizeof(double) * P);
-  if (err == hipSuccess) err = dy.reserve(sizeof(double) * P);
-  if (err == hipSuccess) err = dg.reserve(sizeof(double) * g.size());
-  if (err == hipSuccess) err = dphi.reserve(sizeof(double) * P);
-  if (err == hipSuccess) err = dsum.reserve(sizeof(double) * (static_cast<size_t>(blocks) + 1));
-  if (err == hipSuccess) err = hipMemcpy(dx.p, xs.data(), sizeof(double) * P, hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemcpy(dy.p, ys.data(), sizeof(double) * P, hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemcpy(dg.p, g.data(), sizeof(double) * g.size(), hipMemcpyHostToDevice);
+  EEA_HIP(dx.reserve(sizeof(double) * P));
+  EEA_HIP(dy.reserve(sizeof(double) * P));
+  EEA_HIP(dg.reserve(sizeof(double) * g.size()));
+  EEA_HIP(dphi.reserve(sizeof(double) * P));
+  EEA_HIP(dsum.reserve(sizeof(double) * (static_cast<size_t>(blocks) + 1)));
+  EEA_HIP(hipMemcpy(dx.p, xs.data(), sizeof(double) * P, hipMemcpyHostToDevice));
+  EEA_HIP(hipMemcpy(dy.p, ys.data(), sizeof(double) * P, hipMemcpyHostToDevice));
+  EEA_HIP(hipMemcpy(dg.p, g.data(), sizeof(double) * g.size(), hipMemcpyHostToDevice));
   int n_partials = 0;
-  double* const d_partials = dsum.p ? static_cast<double*>(dsum.p) + 1 : nullptr;
-  if (err == hipSuccess) {
-    err = eea::launch_target_fill_points<double>(static_cast<const double*>(dx.p), static_cast<const double*>(dy.p), P,
-                                                 static_cast<const double*>(dg.p), static_cast<int>(n_gauss),
-                                                 static_cast<double*>(dphi.p), d_partials, &n_partials, nullptr);
-  }
-  if (err == hipSuccess) err = eea::launch_reduce_sum<double>(d_partials, n_partials, static_cast<double*>(dsum.p), nullptr);
-  if (err == hipSuccess) err = eea::launch_scale_by_inv<double>(static_cast<double*>(dphi.p), P, static_cast<const double*>(dsum.p), nullptr);
-  if (err == hipSuccess) err = hipMemcpy(h_phi_vals, dphi.p, sizeof(double) * P, hipMemcpyDeviceToHost);
-  dx.release();
-  dy.release();
-  dg.release();
-  dphi.release();
-  dsum.release();
-  if (err != hipSuccess) return fail(EEA_ERR_HIP, std::string("target fill: ") + hipGetErrorString(err));
+  double* const d_mass = as<double>(dsum.p);
+  double* const d_partials = d_mass + 1;
+  EEA_HIP(eea::launch_target_fill_points<double>(as<double>(dx.p), as<double>(dy.p), P, as<double>(dg.p),
+                                                 static_cast<int>(n_gauss), as<double>(dphi.p), d_partials, &n_partials,
+                                                 nullptr));
+  EEA_HIP(eea::launch_reduce_sum<double>(d_partials, n_partials, d_mass, nullptr));
+  EEA_HIP(eea::launch_scale_by_inv<double>(as<double>(dphi.p), P, d_mass, nullptr));
+  EEA_HIP(hipMemcpy(h_phi_vals, dphi.p, sizeof(double) * P, hipMemcpyDeviceToHost));
   return EEA_OK;
 }
 
@@ -1924,7 +1878,8 @@ void eea_release_collision_caches(void) { eea::release_collision_caches(); }
 eea_status eea_tick_batch(eea_engine* e, unsigned B, const eea_batch_io* io, const eea_tick_io* tick,
                           const eea_collision_cfg* ccfg, const eea_dwa_cfg* dcfg, void* stream)
 {
-  if (check_engine(e) != EEA_OK) return EEA_ERR_INVALID_ARGUMENT;
+  // (refusals of several kinds, B == 0 and the parameter blocks come before the device is touched: no shared prologue)
+  if (e == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null engine");
   if (io == nullptr || tick == nullptr || dcfg == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
   if (e->f32) return fail(EEA_ERR_UNSUPPORTED, "eea_tick_batch takes fp64 engines (poses and twists are doubles)");
   if (io->d_pose == nullptr || io->d_ut == nullptr || tick->d_follow_dwa == nullptr || tick->d_dwa_count == nullptr ||

@@ -372,3 +372,113 @@ def test_random_grid_shapes(seed):
     eng.set_target_occupancy(nx, ny, torch.as_tensor(occ).cuda(), lx, ly)
     assert np.abs(eng.phik() - ref_o).max() < 1e-11
     eng.close()
+
+
+# ---- the domain of a call is the call's own; the engine's changes only with its phi_k ----------------------------------------
+_PRECISIONS = [pytest.param(capi.PREC_F64, id="fp64"), pytest.param(capi.PREC_F32, id="fp32")]
+
+
+def _real(precision):
+    return (np.float32, torch.float32) if precision == capi.PREC_F32 else (np.float64, torch.float64)
+
+
+def _domain_engine(precision, domain=True):
+    """K = 5, resolution 0.1, the two-Gaussian target; on MAP_BOUNDS unless domain is False (an engine without a domain)"""
+    eng = _engine(5, 0.1, precision)
+    eng.set_target_gaussians(MEANS, SIGMAS)
+    if domain:
+        assert eng.config_domain(MAP_BOUNDS) is True
+    return eng
+
+
+def _u0_of_seeded_batch(eng, precision):
+    """u0 of one control_batch of B = 4 seeded poses on a fresh zero ut"""
+    ndt, tdt = _real(precision)
+    B = 4
+    rng = np.random.default_rng(21)
+    poses = np.stack([rng.uniform(0.0, 10.0, B), rng.uniform(0.0, 4.0, B), rng.uniform(-3.0, 3.0, B)], 1).astype(ndt)
+    d_ut = torch.zeros((B, eng.T, 3), dtype=tdt, device="cuda")
+    d_u0 = torch.empty((B, 3), dtype=tdt, device="cuda")
+    eng.control_batch(B, torch.as_tensor(poses).cuda(), d_ut, d_u0)
+    torch.cuda.synchronize()
+    return d_u0.cpu().numpy()
+
+
+@pytest.mark.parametrize("precision", _PRECISIONS)
+def test_tile_calls_take_their_own_domain(precision):
+    """eea_spatial_coeff_rows / eea_spatial_coeff_occupancy_rows on a grid and domain that are not the engine's: the results
+    are those of an engine that never had a domain, and the engine's domain, phi_k, grid size and controls are untouched.
+    Tolerance of the tile sum against the oracle, phi summing to 1 as in test_row_tiles_sum_to_full_grid: its 1e-13 in fp64;
+    in fp32 the phi_k bound this file holds fp32 engines to (2e-5, test_phik_f32 on 256 x 256 points at K = 20) -- this grid
+    has fewer points (561), fewer modes and smaller cosine arguments (<= 4 pi, whose fp32 rounding, 1e-6 per axis, is the
+    largest term here), so nothing wider is needed."""
+    ndt, tdt = _real(precision)
+    K, K2 = 5, 25
+    nx, ny, lx, ly, row0, nrows = 33, 17, 3.2, 1.6, 5, 7
+    eng = _domain_engine(precision)
+    pk0, size0, u0 = eng.phik(), eng.target_grid_size, _u0_of_seeded_batch(eng, precision)
+
+    rng = np.random.default_rng(33)
+    phi = rng.random(nx * ny)
+    phi /= phi.sum()
+    d_phi = torch.as_tensor(phi.astype(ndt)).cuda()
+    occ = rng.choice(np.array([0, 100, -1, 17, 50], dtype=np.int8), size=(ny, nx))
+    d_occ = torch.as_tensor(occ).cuda()
+
+    def tiles(e, lx_, r0=row0, n=nrows):
+        a = torch.empty(K2, dtype=tdt, device="cuda")
+        b = torch.empty(K2, dtype=tdt, device="cuda")
+        e.spatial_coeff_rows(nx, ny, r0, n, d_phi[r0 * nx:(r0 + n) * nx], lx_, ly, a)
+        e.spatial_coeff_occupancy_rows(nx, ny, r0, n, d_occ[r0:r0 + n], lx_, ly, b)
+        torch.cuda.synchronize()
+        return a.cpu().numpy(), b.cpu().numpy()
+
+    fresh = _engine(K, 0.1, precision)  # never had a target or a domain
+    want = tiles(fresh, lx)
+    got = tiles(eng, lx)
+    assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+    assert np.isfinite(got[0]).all() and np.isfinite(got[1]).all()
+    total = sum(tiles(eng, lx, r0, n)[0].astype(np.float64) for r0, n in ((0, 5), (5, 7), (12, 5)))
+    ref = po.spatial_coeff(lx, ly, K, phi, po.phi_grid(nx, ny, 0.1))
+    err = np.abs(total - ref).max()
+    print("tile sum against the oracle: %.3g" % err)
+    assert err < (2e-5 if precision == capi.PREC_F32 else 1e-13)
+    # another domain in between evicts the tables; back on the first one the results are the first ones
+    first, other, third = tiles(eng, lx), tiles(eng, 2 * lx), tiles(eng, lx)
+    assert np.array_equal(first[0], third[0]) and np.array_equal(first[1], third[1])
+    assert np.array_equal(first[0], want[0]) and not np.array_equal(other[0], first[0])
+
+    assert eng.config_domain(MAP_BOUNDS) is False
+    assert np.array_equal(eng.phik(), pk0) and eng.target_grid_size == size0
+    assert np.array_equal(_u0_of_seeded_batch(eng, precision), u0)
+    assert np.isfinite(u0).all() and np.abs(u0).max() > 0.0
+    eng.close()
+    fresh.close()
+
+
+@pytest.mark.parametrize("precision", _PRECISIONS)
+def test_refused_rebuild_keeps_the_domain(precision):
+    """A rebuild the size check refuses (1 000 001^2 grid points: nothing is allocated or launched) leaves the engine on the
+    domain of the phi_k it holds: the next call on that domain does not rebuild.  An engine without a domain still has
+    none, and no phi_k."""
+    huge = (-1.0, 99999.0, -1.0, 99999.0)
+    eng = _domain_engine(precision)
+    pk0, u0 = eng.phik(), _u0_of_seeded_batch(eng, precision)
+    with pytest.raises(capi.EngineError) as ei:
+        eng.config_domain(huge)
+    assert ei.value.status == capi.ERR_UNSUPPORTED and "out of range" in str(ei.value)
+    assert eng.config_domain(MAP_BOUNDS) is False
+    assert np.array_equal(eng.phik(), pk0)
+    assert np.array_equal(_u0_of_seeded_batch(eng, precision), u0)
+    eng.close()
+
+    eng = _domain_engine(precision, domain=False)
+    with pytest.raises(capi.EngineError) as ei:
+        eng.config_domain(huge)
+    assert ei.value.status == capi.ERR_UNSUPPORTED and "out of range" in str(ei.value)
+    with pytest.raises(capi.EngineError) as ei:
+        _u0_of_seeded_batch(eng, precision)
+    assert ei.value.status == capi.ERR_NO_TARGET
+    assert eng.config_domain(MAP_BOUNDS) is True
+    assert np.array_equal(eng.phik(), pk0)
+    eng.close()

@@ -12,7 +12,7 @@ hipError_t launch_control_timing(const ControlParams<double>& p, unsigned B, int
 extern "C" eea_status eea_debug_phase_timing(eea_engine* e, unsigned B, const eea_batch_io* io, void* stream,
                                              long long* d_stamps)
 {
-  if (check_engine(e) != EEA_OK) return EEA_ERR_INVALID_ARGUMENT;
+  if (e == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null engine");
   if (io == nullptr || io->d_pose == nullptr || io->d_ut == nullptr || io->d_u0 == nullptr || d_stamps == nullptr) {
     return fail(EEA_ERR_INVALID_ARGUMENT, "d_pose, d_ut, d_u0 and d_stamps are required");
   }
