@@ -217,6 +217,11 @@ def lib():
         L.eea_records_metric.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.eea_records_field.argtypes = [C.c_void_p, C.c_int, C.c_uint, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_uint,
                                         C.c_void_p, C.c_void_p]
+        L.eea_sense_ray_count.restype = C.c_uint
+        L.eea_sense_ray_count.argtypes = [C.c_uint]
+        L.eea_sense_reveal_batch.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p]
+        L.eea_grid_census.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -588,6 +593,25 @@ def integrate_twist_batch(x0, u, dt, out=None, normalize_heading=False, stream=N
     check(lib().eea_integrate_twist_batch(device, _ptr(x0), _ptr(u), float(dt), int(x0.shape[0]), _ptr(out),
                                           1 if normalize_heading else 0, C.c_void_p(stream or 0)))
     return out
+
+
+def sense_ray_count(range_cells):
+    """eea_sense_ray_count: rays per robot of eea_sense_reveal_batch, 8 * range_cells"""
+    return int(lib().eea_sense_ray_count(int(range_cells)))
+
+
+def sense_reveal_batch(cfg, range_cells, truth, known, pose, ranges=None, mask=None, device=0, stream=None):
+    """eea_sense_reveal_batch: the P robots of pose [P][3] cast 8 * range_cells rays through the int8 grid truth; the cells
+    they cross are copied into known (in place); ranges [P][8 * range_cells] int32 (optional) receives the step at which a ray
+    met a blocking cell or -1; mask [P] int32 (optional): robots with 0 are left out.  Device tensors; asynchronous"""
+    check(lib().eea_sense_reveal_batch(device, C.byref(cfg), int(range_cells), _ptr(truth), _ptr(known), _ptr(pose), _ptr(mask),
+                                       int(pose.shape[0]), _ptr(ranges), C.c_void_p(stream or 0)))
+
+
+def grid_census(cfg, grid, counts, device=0, stream=None):
+    """eea_grid_census: counts [3] (device, 64-bit integers) = unknown cells (< 0), known cells below the occupied threshold,
+    blocking cells of the int8 device grid; asynchronous"""
+    check(lib().eea_grid_census(device, C.byref(cfg), _ptr(grid), _ptr(counts), C.c_void_p(stream or 0)))
 
 
 def stream_wait_flag(flag, seq, timeouts=None, stream=None):

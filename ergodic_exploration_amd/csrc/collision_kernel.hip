@@ -19,20 +19,12 @@
 
 #include "../../include/ergodic_amd.h"
 #include "common.hpp"
+#include "grid_cell.hpp"  // cast_u32_x86, world_to_grid (grid.cpp:143-159): shared with sense_kernel.hip
 
 namespace eea
 {
 namespace
 {
-// static_cast<unsigned>(double) as x86-64 gcc compiles it (cvttsd2si r64, low 32 bits):
-// negative and > 2^32 values wrap mod 2^32, out-of-range / NaN give 0.  The GPU's own
-// double->u32 conversion saturates, so it is not used.
-__device__ __forceinline__ unsigned cast_u32_x86(double v)
-{
-  if (!(v > -9.2233720368547758e18 && v < 9.2233720368547758e18)) return 0u;
-  return static_cast<unsigned>(static_cast<unsigned long long>(static_cast<long long>(v)));
-}
-
 struct RingState
 {
   int cx, cy, sqrd_obs;
@@ -81,10 +73,8 @@ __device__ __forceinline__ bool bresenham_circle(const CollisionParams& c,
 __device__ __forceinline__ bool collision_check(const CollisionParams& c,
                                                 const int8_t* __restrict__ grid, double px, double py)
 {
-  unsigned j = cast_u32_x86(floor((px - c.xmin) / c.resolution));
-  unsigned i = cast_u32_x86(floor((py - c.ymin) / c.resolution));
-  if (j == c.xsize) j--;
-  if (i == c.ysize) i--;
+  unsigned j, i;
+  world_to_grid(c, px, py, j, i);
   RingState st;
   st.cx = static_cast<int>(j);
   st.cy = static_cast<int>(i);
@@ -107,10 +97,8 @@ struct HitMap
 // grid cell of a world point as collisionCheck derives it (grid.cpp:143-159), as signed ints
 __device__ __forceinline__ void centre_of(const CollisionParams& c, double px, double py, int& cx, int& cy)
 {
-  unsigned j = cast_u32_x86(floor((px - c.xmin) / c.resolution));
-  unsigned i = cast_u32_x86(floor((py - c.ymin) / c.resolution));
-  if (j == c.xsize) j--;
-  if (i == c.ysize) i--;
+  unsigned j, i;
+  world_to_grid(c, px, py, j, i);
   cx = static_cast<int>(j);
   cy = static_cast<int>(i);
 }

@@ -314,6 +314,14 @@ hipError_t launch_validate_and_dwa_fleet(const CollisionParams& c, const DwaPara
 // frees the cached ring offsets and inflated-map buffers of every device
 void release_collision_caches();
 
+// ---- range sensing of a simulated fleet (sense_kernel.hip) -------------------------------
+// every robot's 8 * range_cells rays through d_truth: the cells they cross are copied into d_known, d_ranges [P][8R]
+// (optional) = the step at which a ray met a blocking cell or -1; c: the geometry and occupied_threshold (radii unused)
+hipError_t launch_sense_reveal(const CollisionParams& c, unsigned range_cells, const int8_t* d_truth, int8_t* d_known,
+                               const double* d_pose, const int* d_mask, unsigned P, int* d_ranges, hipStream_t s);
+// d_counts[3] = cells < 0, cells >= 0 below the occupied threshold, blocking cells of d_grid [ysize][xsize]
+hipError_t launch_grid_census(const CollisionParams& c, const int8_t* d_grid, unsigned long long* d_counts, hipStream_t s);
+
 // ======================================================================================
 // device helpers
 // ======================================================================================

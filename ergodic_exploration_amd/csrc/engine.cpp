@@ -1874,6 +1874,56 @@ eea_status eea_integrate_twist_batch(int device, const double* d_x0, const doubl
 
 void eea_release_collision_caches(void) { eea::release_collision_caches(); }
 
+// ---- range sensing of a simulated fleet ------------------------------------------------------
+// the geometry of an eea_collision_cfg without Collision::Collision's checks of the radii, which the sensor does not read
+static eea_status make_sense_params(const eea_collision_cfg* cfg, eea::CollisionParams& c)
+{
+  if (cfg->xsize == 0 || cfg->ysize == 0) return fail(EEA_ERR_INVALID_ARGUMENT, "the grid's xsize and ysize must be positive");
+  if (!(cfg->resolution > 0.0)) return fail(EEA_ERR_INVALID_ARGUMENT, "the grid's resolution must be positive");
+  c.xmin = cfg->xmin;
+  c.ymin = cfg->ymin;
+  c.resolution = cfg->resolution;
+  c.xsize = cfg->xsize;
+  c.ysize = cfg->ysize;
+  c.r_bnd = c.r_col = c.r_max = 0;
+  c.occupied_threshold = cfg->occupied_threshold;
+  return EEA_OK;
+}
+
+unsigned eea_sense_ray_count(unsigned range_cells) { return 8u * range_cells; }
+
+eea_status eea_sense_reveal_batch(int device, const eea_collision_cfg* cfg, unsigned range_cells, const int8_t* d_truth,
+                                  int8_t* d_known, const double* d_pose, const int* d_mask, unsigned P, int* d_ranges,
+                                  void* stream)
+{
+  if (cfg == nullptr || d_truth == nullptr || d_known == nullptr || d_pose == nullptr) {
+    return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  }
+  if (d_truth == d_known) return fail(EEA_ERR_INVALID_ARGUMENT, "d_truth and d_known must be different grids");
+  eea::CollisionParams c;
+  const eea_status st = make_sense_params(cfg, c);
+  if (st != EEA_OK) return st;
+  if (range_cells == 0) return fail(EEA_ERR_INVALID_ARGUMENT, "range_cells must be positive");
+  if (range_cells > 1024u) return fail(EEA_ERR_UNSUPPORTED, "range_cells above 1024");
+  if (P == 0) return EEA_OK;
+  EEA_HIP(hipSetDevice(device));
+  EEA_HIP(eea::launch_sense_reveal(c, range_cells, d_truth, d_known, d_pose, d_mask, P, d_ranges,
+                                   static_cast<hipStream_t>(stream)));
+  return EEA_OK;
+}
+
+eea_status eea_grid_census(int device, const eea_collision_cfg* cfg, const int8_t* d_grid, unsigned long long* d_counts,
+                           void* stream)
+{
+  if (cfg == nullptr || d_grid == nullptr || d_counts == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  eea::CollisionParams c;
+  const eea_status st = make_sense_params(cfg, c);
+  if (st != EEA_OK) return st;
+  EEA_HIP(hipSetDevice(device));
+  EEA_HIP(eea::launch_grid_census(c, d_grid, d_counts, static_cast<hipStream_t>(stream)));
+  return EEA_OK;
+}
+
 // One tick of Exploration<ModelT>::control's loop body for B robots (exploration.hpp:220-279): see ergodic_amd.h
 eea_status eea_tick_batch(eea_engine* e, unsigned B, const eea_batch_io* io, const eea_tick_io* tick,
                           const eea_collision_cfg* ccfg, const eea_dwa_cfg* dcfg, void* stream)

@@ -1,0 +1,273 @@
+// Range sensing of a simulated fleet (include/ergodic_amd.h, eea_sense_reveal_batch / eea_grid_census): every robot casts 8R
+// rays through a ground-truth occupancy grid and the cells the rays cross become known -- the counterpart of
+// integrate_twist_kernel (the simulated fleet's motion).  The reference has the consumer of such a map (entropy(),
+// numerics.hpp:164-179: an unknown cell is worth 0.7, a known one 1e-3) and describes the sensor in words (README.md:74-76,
+// "simulating a 360 degree range finder"); its OccupancyMapper (mapping.cpp) fuses real scans and is NOT what this is.
+//
+//  - integers only: the robot's cell is world2Grid of grid_cell.hpp (the collision kernels' definition), a ray's step s sits
+//    at sgn(m) ((2 s |m| + R) div 2R) per axis -- formed here by adding 2|m| per step to a remainder that starts at R and
+//    wraps at 2R, which is that quotient exactly (2|m| <= 2R: at most one wrap per step) --, and "blocks a ray" is
+//    cell >= cutoff, cutoff = the smallest int8 value v with !(v / 100.0 < occupied_threshold) found on the host (the
+//    quotient is monotone in v: checkCell's test, collision.cpp:216-243 with grid.cpp:177-184, is a threshold on the cell);
+//  - every write to a cell of `known` stores that cell of `truth`, whoever makes it: robots, rays and calls may overlap in
+//    any order, no atomics, byte (vector) stores only;
+//  - one workgroup of 256 threads per robot, a thread per ray (8R rays: ceil(8R / 256) rounds, the last one ragged).
+//    R <= 127: the robot's (2R + 1)^2 window is staged in LDS as one byte per cell (bit 0: blocks; rows read coalesced, one
+//    wavefront per row), the rays march in LDS and set bit 1 of the cells they cross (every writer of a byte writes the
+//    same value, bit 0 is never changed), then the marked cells are copied truth -> known row by row.  The overlap of the
+//    rays near the robot costs LDS cycles only; global memory sees each window byte at most twice, in rows.  The window's
+//    rows are 2R + 1 bytes, an odd count: the cells of a column sit in different banks.
+//    R > 127 (the window passes 64 KB): the rays march in global memory, a dependent byte load and a byte store per step.
+//    Both compute the contract bit for bit (tests/test_gpu_sense.py holds each to tests/sense_restatement.py).
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "common.hpp"
+#include "grid_cell.hpp"
+
+namespace eea
+{
+namespace
+{
+constexpr int kSenseBlock = 256;
+constexpr unsigned kSenseMaxBlocks = 1u << 16;  // workgroups per launch; they stride over the robots past that
+constexpr unsigned kSenseLdsMaxR = 127;         // (2R + 1)^2 bytes <= 64 KB
+
+struct SenseParams
+{
+  CollisionParams c;  // the geometry (the radii are not read)
+  int R;
+  int cutoff;  // a cell blocks a ray iff cell >= cutoff (128: no cell does)
+  const int8_t* truth;
+  int8_t* known;
+  const double* pose;  // [P][3]
+  const int* mask;     // [P] or null
+  int* ranges;         // [P][8R] or null
+  unsigned P;
+};
+
+// what a robot at (i0, j0) can touch: offsets [xlo, xhi] x [ylo, yhi] of [-R, R]^2 that fall on the grid
+struct Clip
+{
+  int xlo, xhi, ylo, yhi;
+};
+__device__ __forceinline__ Clip clip_of(const CollisionParams& c, unsigned i0, unsigned j0, int R)
+{
+  Clip w;
+  const unsigned uR = static_cast<unsigned>(R), rx = c.xsize - 1u - j0, ry = c.ysize - 1u - i0;
+  w.xlo = j0 < uR ? -static_cast<int>(j0) : -R;
+  w.xhi = rx < uR ? static_cast<int>(rx) : R;
+  w.ylo = i0 < uR ? -static_cast<int>(i0) : -R;
+  w.yhi = ry < uR ? static_cast<int>(ry) : R;
+  return w;
+}
+
+// ray q of a robot: steps s = 1 .. R until the ray leaves the disc or the grid, or visit(dx, dy) says the cell blocks;
+// returns the range s of the blocking cell or -1
+template <typename Visit>
+__device__ __forceinline__ int march(int q, int R, const Clip& w, Visit visit)
+{
+  const int side = q / (2 * R), k = q - side * 2 * R;
+  const int tx = side == 0 ? R : side == 1 ? R - k : side == 2 ? -R : -R + k;
+  const int ty = side == 0 ? -R + k : side == 1 ? R : side == 2 ? R - k : -R;
+  const int ax2 = 2 * (tx < 0 ? -tx : tx), ay2 = 2 * (ty < 0 ? -ty : ty);
+  const int sx = tx > 0 ? 1 : tx < 0 ? -1 : 0, sy = ty > 0 ? 1 : ty < 0 ? -1 : 0;
+  int remx = R, remy = R, dx = 0, dy = 0;  // (2 s |m| + R) = (2R) (|d|) + rem
+  for (int s = 1; s <= R; ++s) {
+    remx += ax2;
+    if (remx >= 2 * R) {
+      remx -= 2 * R;
+      dx += sx;
+    }
+    remy += ay2;
+    if (remy >= 2 * R) {
+      remy -= 2 * R;
+      dy += sy;
+    }
+    if (dx * dx + dy * dy > R * R) break;
+    if (dx < w.xlo || dx > w.xhi || dy < w.ylo || dy > w.yhi) break;
+    if (visit(dx, dy)) return s;
+  }
+  return -1;
+}
+
+__device__ __forceinline__ size_t cell_index(const CollisionParams& c, unsigned i0, unsigned j0, int dx, int dy)
+{
+  return (static_cast<size_t>(i0) + static_cast<size_t>(static_cast<long long>(dy))) * c.xsize +
+         (static_cast<size_t>(j0) + static_cast<size_t>(static_cast<long long>(dx)));
+}
+
+// the robot of this workgroup's turn: false when the mask leaves it out or its cell is off the grid (mapping.cpp:81-86's
+// rule; its row of ranges is then -1)
+__device__ __forceinline__ bool robot_cell(const SenseParams& p, unsigned b, unsigned& i0, unsigned& j0)
+{
+  if (p.mask != nullptr && p.mask[b] == 0) return false;
+  world_to_grid(p.c, p.pose[3 * static_cast<size_t>(b)], p.pose[3 * static_cast<size_t>(b) + 1], j0, i0);
+  if ((i0 <= p.c.ysize - 1u) && (j0 <= p.c.xsize - 1u)) return true;
+  if (p.ranges != nullptr) {
+    int* const row = p.ranges + static_cast<size_t>(b) * 8u * p.R;
+    for (int q = threadIdx.x; q < 8 * p.R; q += kSenseBlock) row[q] = -1;
+  }
+  return false;
+}
+
+__global__ __launch_bounds__(kSenseBlock) void sense_reveal_lds_kernel(const SenseParams p)
+{
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_cell[];  // [2R + 1][2R + 1]: bit 0 blocks, bit 1 revealed
+  const int R = p.R, W = 2 * R + 1, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (unsigned b = blockIdx.x; b < p.P; b += gridDim.x) {
+    __syncthreads();  // the robot before has read the window
+    unsigned i0, j0;
+    if (!robot_cell(p, b, i0, j0)) continue;  // (uniform over the workgroup)
+    const Clip w = clip_of(p.c, i0, j0, R);
+    for (int dy = w.ylo + wave; dy <= w.yhi; dy += kSenseBlock / 64) {
+      const int8_t* const trow = p.truth + cell_index(p.c, i0, j0, 0, dy);
+      unsigned char* const srow = s_cell + (dy + R) * W + R;
+      for (int dx = w.xlo + lane; dx <= w.xhi; dx += 64) srow[dx] = trow[dx] >= p.cutoff ? 1 : 0;
+    }
+    __syncthreads();
+    if (tid == 0) s_cell[R * W + R] |= 2;  // the robot's own cell (no ray visits offset (0, 0))
+    for (int q = tid; q < 8 * R; q += kSenseBlock) {
+      const int range = march(q, R, w, [&](int dx, int dy) {
+        unsigned char* const cell = s_cell + (dy + R) * W + (dx + R);
+        const unsigned char v = *cell;
+        if (v < 2) *cell = v | 2;
+        return (v & 1) != 0;
+      });
+      if (p.ranges != nullptr) p.ranges[static_cast<size_t>(b) * 8u * R + q] = range;
+    }
+    __syncthreads();
+    for (int dy = w.ylo + wave; dy <= w.yhi; dy += kSenseBlock / 64) {
+      const size_t g0 = cell_index(p.c, i0, j0, 0, dy);
+      const unsigned char* const srow = s_cell + (dy + R) * W + R;
+      for (int dx = w.xlo + lane; dx <= w.xhi; dx += 64) {
+        if (srow[dx] & 2) p.known[g0 + dx] = p.truth[g0 + dx];
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(kSenseBlock) void sense_reveal_global_kernel(const SenseParams p)
+{
+  const int R = p.R, tid = threadIdx.x;
+  for (unsigned b = blockIdx.x; b < p.P; b += gridDim.x) {
+    unsigned i0, j0;
+    if (!robot_cell(p, b, i0, j0)) continue;
+    const Clip w = clip_of(p.c, i0, j0, R);
+    if (tid == 0) {
+      const size_t g = cell_index(p.c, i0, j0, 0, 0);
+      p.known[g] = p.truth[g];
+    }
+    for (int q = tid; q < 8 * R; q += kSenseBlock) {
+      const int range = march(q, R, w, [&](int dx, int dy) {
+        const size_t g = cell_index(p.c, i0, j0, dx, dy);
+        const int8_t t = p.truth[g];
+        p.known[g] = t;
+        return t >= p.cutoff;
+      });
+      if (p.ranges != nullptr) p.ranges[static_cast<size_t>(b) * 8u * R + q] = range;
+    }
+  }
+}
+
+// ---- census ----------------------------------------------------------------------------------
+struct Census
+{
+  unsigned unknown, below, blocking;
+};
+__device__ __forceinline__ void count_cell(Census& n, int cell, int cutoff)
+{
+  n.unknown += cell < 0 ? 1u : 0u;
+  n.below += (cell >= 0 && cell < cutoff) ? 1u : 0u;
+  n.blocking += cell >= cutoff ? 1u : 0u;
+}
+
+// 16 bytes per load from the grid's first 16-byte boundary on; the bytes in front of it and behind the last whole load one
+// by one (at most 15 each: the first threads of the launch take them).  d_counts was zeroed on the stream.
+__global__ __launch_bounds__(kSenseBlock) void grid_census_kernel(const int8_t* __restrict__ grid, size_t n, int cutoff,
+                                                                  unsigned long long* __restrict__ counts)
+{
+  __shared__ unsigned s_part[kSenseBlock / 64][3];
+  size_t head = (16u - (reinterpret_cast<uintptr_t>(grid) & 15u)) & 15u;
+  if (head > n) head = n;
+  const size_t chunks = (n - head) / 16u, tail0 = head + chunks * 16u;
+  const size_t t = static_cast<size_t>(blockIdx.x) * kSenseBlock + threadIdx.x, stride = static_cast<size_t>(gridDim.x) * kSenseBlock;
+  Census cnt{ 0u, 0u, 0u };
+  const uint4* const body = reinterpret_cast<const uint4*>(grid + head);
+  for (size_t ch = t; ch < chunks; ch += stride) {
+    const uint4 v = body[ch];
+    const unsigned word[4] = { v.x, v.y, v.z, v.w };
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) count_cell(cnt, static_cast<int8_t>((word[a] >> (8 * k)) & 0xffu), cutoff);
+  }
+  if (t < head) count_cell(cnt, grid[t], cutoff);
+  if (t < n - tail0) count_cell(cnt, grid[tail0 + t], cutoff);
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    cnt.unknown += __shfl_down(cnt.unknown, d, 64);
+    cnt.below += __shfl_down(cnt.below, d, 64);
+    cnt.blocking += __shfl_down(cnt.blocking, d, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    s_part[threadIdx.x >> 6][0] = cnt.unknown;
+    s_part[threadIdx.x >> 6][1] = cnt.below;
+    s_part[threadIdx.x >> 6][2] = cnt.blocking;
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    unsigned long long sum = 0;
+    for (int wv = 0; wv < kSenseBlock / 64; ++wv) sum += s_part[wv][threadIdx.x];
+    if (sum != 0) atomicAdd(counts + threadIdx.x, sum);  // integers: any order of the workgroups gives the same sums
+  }
+}
+}  // namespace
+
+int blocking_cutoff(double occupied_threshold)
+{
+  // checkCell's test on getCell (collision.cpp:216-243, grid.cpp:177-184), cell by cell; v / 100.0 is monotone in v
+  for (int v = -128; v <= 127; ++v) {
+    const double cell = static_cast<double>(static_cast<int8_t>(v)) / 100.0;
+    if (!(cell < occupied_threshold)) return v;
+  }
+  return 128;
+}
+
+hipError_t launch_sense_reveal(const CollisionParams& c, unsigned range_cells, const int8_t* d_truth, int8_t* d_known,
+                               const double* d_pose, const int* d_mask, unsigned P, int* d_ranges, hipStream_t s)
+{
+  if (P == 0) return hipSuccess;
+  SenseParams p;
+  p.c = c;
+  p.R = static_cast<int>(range_cells);
+  p.cutoff = blocking_cutoff(c.occupied_threshold);
+  p.truth = d_truth;
+  p.known = d_known;
+  p.pose = d_pose;
+  p.mask = d_mask;
+  p.ranges = d_ranges;
+  p.P = P;
+  const unsigned blocks = P < kSenseMaxBlocks ? P : kSenseMaxBlocks;
+  if (range_cells <= kSenseLdsMaxR) {
+    const size_t W = 2 * static_cast<size_t>(range_cells) + 1;
+    hipLaunchKernelGGL(sense_reveal_lds_kernel, dim3(blocks), dim3(kSenseBlock), W * W, s, p);
+  } else {
+    hipLaunchKernelGGL(sense_reveal_global_kernel, dim3(blocks), dim3(kSenseBlock), 0, s, p);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_grid_census(const CollisionParams& c, const int8_t* d_grid, unsigned long long* d_counts, hipStream_t s)
+{
+  const size_t n = static_cast<size_t>(c.xsize) * c.ysize;
+  hipError_t e = hipMemsetAsync(d_counts, 0, 3 * sizeof(unsigned long long), s);
+  if (e != hipSuccess) return e;
+  const size_t want = (n / 16u + kSenseBlock - 1) / kSenseBlock + 1;  // (+ 1: the head and tail bytes when there is no whole load)
+  const unsigned blocks = want < 2048u ? static_cast<unsigned>(want) : 2048u;
+  hipLaunchKernelGGL(grid_census_kernel, dim3(blocks), dim3(kSenseBlock), 0, s, d_grid, n, blocking_cutoff(c.occupied_threshold),
+                     d_counts);
+  return hipGetLastError();
+}
+}  // namespace eea

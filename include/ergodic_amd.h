@@ -701,6 +701,46 @@ typedef enum { EEA_FIELD_DENSITY = 0, EEA_FIELD_DEFICIT = 1, EEA_FIELD_POTENTIAL
 eea_status eea_records_field(eea_engine* e, int kind, unsigned n_rec, const void* d_rec, unsigned nx, unsigned ny_total,
                              unsigned row0, unsigned nrows, void* d_field, void* stream);
 
+/* ---- range sensing of a simulated fleet (additive to ABI 6: detect these entries by symbol) ----------------------------------
+ * The sensor of a simulated fleet, as eea_integrate_twist_batch is its motion: every robot casts rays through a ground-truth
+ * occupancy grid and the cells the rays cross become known.  The reference states the loop in words (README.md:74-76,
+ * "simulating a 360 degree range finder ... after the robot has fully explored the space, the mutual information is zero") and
+ * has the map's consumer -- entropy() (numerics.hpp:164-179): an unknown cell (-1) is worth 0.7, a known one 1e-3, which is the
+ * target eea_set_target_occupancy builds from the known grid.  This is NOT OccupancyMapper (mapping.cpp), which fuses laser
+ * scans from outside in the order they arrive: here every write to a cell stores that cell's true value, so the result does
+ * not depend on the order of robots, rays or calls, is exact in integers and needs no atomics.
+ * d_truth (read only) and d_known (updated in place; the caller initialises it, normally to -1) are int8 grids of cfg's
+ * geometry, row-major [ysize][xsize]; cfg's radii are not read and not checked.  R = range_cells.
+ *   the robot's cell (i0, j0) = GridMap::world2Grid(x, y) (grid.cpp:143-159, with the x86-64 wrap, as the collision calls); a
+ *     robot whose cell fails gridBounds (grid.cpp:96-100) reveals nothing and hits nothing (the rule of mapping.cpp:81-86); the
+ *     heading is not used (360 degrees);
+ *   8R rays: with side, k = divmod(q, 2R), ray q aims at the offset (tx, ty) = (R, -R + k), (R - k, R), (-R, R - k),
+ *     (-R + k, -R) for side 0 .. 3 -- the perimeter of the square [-R, R]^2;
+ *   step s = 1 .. R of a ray sits at (dx, dy) = (d(tx, s), d(ty, s)), d(m, s) = sgn(m) ((2 s |m| + R) div 2R): the major axis
+ *     moves a cell per step, the minor one is s |m| / R rounded half away from zero -- a closed form in s, no running error;
+ *   a ray, for s = 1, 2, ..: it ends without a hit where dx^2 + dy^2 > R^2 or where (i0 + dy, j0 + dx) is off the grid;
+ *     otherwise known[i][j] = truth[i][j], and if !(truth[i][j] / 100.0 < occupied_threshold) -- checkCell's test on getCell
+ *     (collision.cpp:216-243, grid.cpp:177-184), so a truth cell of -1 lets the ray through and stays -1 -- the ray's range
+ *     is s and it ends; a ray that ends without a hit has range -1;
+ *   known[i0][j0] = truth[i0][j0]; the robot's own cell never blocks its rays.
+ * In an obstacle-free grid the rays reach every cell of the disc dx^2 + dy^2 <= R^2 and none outside it.
+ * d_pose [P][3] doubles; d_mask [P] (optional): a robot with d_mask[b] == 0 is left out -- nothing of it is read or written,
+ * its row of d_ranges included; d_ranges [P][eea_sense_ray_count(R)] ints (optional): the rays' ranges, a row of -1 for a robot
+ * off the grid.  Every output is a pure function of (truth, known before, poses, mask, cfg, R).
+ * eea_grid_census overwrites d_counts[3] with, over the xsize * ysize cells of d_grid: the cells < 0 (unknown); the cells >= 0
+ * with cell / 100.0 < occupied_threshold; the blocking cells (!(cell / 100.0 < occupied_threshold)) -- a loop's progress
+ * measure without reading the grid back (integers: no summation order enters).
+ * Both calls are asynchronous on `stream`, read nothing on the host, allocate nothing and make no synchronising call; P == 0
+ * is EEA_OK with nothing launched.  Before any HIP call -- EEA_ERR_INVALID_ARGUMENT: cfg, d_truth, d_known, d_pose, d_grid or
+ * d_counts null; d_truth == d_known; xsize or ysize 0; resolution <= 0; range_cells == 0.  EEA_ERR_UNSUPPORTED: range_cells >
+ * 1024 (up to there 2 s |m| + R stays far inside 32 bits).  eea_abi_version() stays 6. */
+unsigned eea_sense_ray_count(unsigned range_cells); /* 8 * range_cells */
+eea_status eea_sense_reveal_batch(int device, const eea_collision_cfg* cfg, unsigned range_cells, const int8_t* d_truth,
+                                  int8_t* d_known, const double* d_pose, const int* d_mask, unsigned P, int* d_ranges,
+                                  void* stream);
+eea_status eea_grid_census(int device, const eea_collision_cfg* cfg, const int8_t* d_grid, unsigned long long* d_counts,
+                           void* stream);
+
 /* The collision / DWA / tick calls keep small device caches between calls (the ring offsets per radii, one
  * inflated-map buffer per (device, stream)).  A long-running process that changes streams or map sizes
  * can drop them; synchronises the devices involved.  No reference counterpart. */
