@@ -222,6 +222,9 @@ def lib():
         L.eea_sense_reveal_batch.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p]
         L.eea_grid_census.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.eea_sense_gain_field.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.eea_set_target_gain.argtypes = [C.c_void_p, C.POINTER(CollisionCfg), C.c_uint, C.c_uint, C.c_void_p, C.c_double,
+                                          C.c_double, C.c_double, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -307,6 +310,13 @@ class Engine:
         on_device = 1 if (hasattr(occ, "is_cuda") and occ.is_cuda) else 0
         check(lib().eea_set_target_occupancy(self.h, nx, ny, _ptr(occ), on_device, lx, ly,
                                              C.c_void_p(stream or 0)))
+
+    def set_target_gain(self, cfg, range_cells, stride, known, lx, ly, floor=0.0, gain=None, stream=None):
+        """eea_set_target_gain: the information-gain field of the int8 device grid `known` (eea_sense_gain_field) + floor on
+        the candidates -> phi_k, all on `stream` without a host wait; gain (optional, device uint32 [ysize][xsize]) receives
+        the integer field"""
+        check(lib().eea_set_target_gain(self.h, C.byref(cfg), int(range_cells), int(stride), _ptr(known), float(floor), lx, ly,
+                                        _ptr(gain), C.c_void_p(stream or 0)))
 
     def spatial_coeff_occupancy_rows(self, nx, ny_total, row0, nrows, occ_rows, lx, ly, out_sums, stream=None):
         """un-normalised coefficient sums of the occupancy rows [row0, row0+nrows) (device int8 tensor)"""
@@ -612,6 +622,14 @@ def grid_census(cfg, grid, counts, device=0, stream=None):
     """eea_grid_census: counts [3] (device, 64-bit integers) = unknown cells (< 0), known cells below the occupied threshold,
     blocking cells of the int8 device grid; asynchronous"""
     check(lib().eea_grid_census(device, C.byref(cfg), _ptr(grid), _ptr(counts), C.c_void_p(stream or 0)))
+
+
+def sense_gain_field(cfg, range_cells, stride, known, gain, device=0, stream=None):
+    """eea_sense_gain_field: gain (device uint32 [ysize][xsize], every element overwritten) = per candidate cell (both indices
+    multiples of stride, the cell not blocking) the unknown cells the sensor's 8 * range_cells rays would cross from there
+    through the int8 device grid `known`, counted per beam, + 1 for an unknown own cell; 0 elsewhere; asynchronous"""
+    check(lib().eea_sense_gain_field(device, C.byref(cfg), int(range_cells), int(stride), _ptr(known), _ptr(gain),
+                                     C.c_void_p(stream or 0)))
 
 
 def stream_wait_flag(flag, seq, timeouts=None, stream=None):

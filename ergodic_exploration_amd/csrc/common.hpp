@@ -321,6 +321,18 @@ hipError_t launch_sense_reveal(const CollisionParams& c, unsigned range_cells, c
                                const double* d_pose, const int* d_mask, unsigned P, int* d_ranges, hipStream_t s);
 // d_counts[3] = cells < 0, cells >= 0 below the occupied threshold, blocking cells of d_grid [ysize][xsize]
 hipError_t launch_grid_census(const CollisionParams& c, const int8_t* d_grid, unsigned long long* d_counts, hipStream_t s);
+// the smallest int8 value v with !(v / 100.0 < occupied_threshold) (128: none): a cell blocks a ray iff cell >= that
+int blocking_cutoff(double occupied_threshold);
+
+// ---- information-gain field of a known grid (gain_kernel.hip) -----------------------------
+// d_gain [ysize][xsize] = per candidate cell (both indices multiples of stride, the cell not blocking) the unknown cells the
+// sensor's 8 * range_cells rays would cross from there through d_known, per beam, + 1 for an unknown own cell; 0 elsewhere
+hipError_t launch_gain_field(const CollisionParams& c, unsigned range_cells, unsigned stride, const int8_t* d_known, unsigned* d_gain,
+                             hipStream_t s);
+// d_values [ysize][xsize] = (R)((double)gain + floor) on the candidates whose cell does not block, 0 elsewhere
+template <typename R>
+hipError_t launch_gain_values(const CollisionParams& c, unsigned stride, const int8_t* d_known, const unsigned* d_gain, double floor,
+                              R* d_values, hipStream_t s);
 
 // ======================================================================================
 // device helpers

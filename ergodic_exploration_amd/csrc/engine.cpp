@@ -191,6 +191,7 @@ struct eea_engine
   hipStream_t rebuild_stream = nullptr;
   bool rebuild_pending = false;
   DevBuf d_lut, d_raw, d_occ;  // occupancy targets: decode table, un-normalised sums, staged cells
+  DevBuf d_gain, d_gain_val;   // eea_set_target_gain: the integer field (when the caller passes no buffer), its value grid
 
   // eea_records_field's OWN tables, apart from the phi_k path's: a field on another grid never evicts tab / d_work and adds no
   // wait to a rebuild
@@ -1921,6 +1922,76 @@ eea_status eea_grid_census(int device, const eea_collision_cfg* cfg, const int8_
   if (st != EEA_OK) return st;
   EEA_HIP(hipSetDevice(device));
   EEA_HIP(eea::launch_grid_census(c, d_grid, d_counts, static_cast<hipStream_t>(stream)));
+  return EEA_OK;
+}
+
+// ---- information-gain target ------------------------------------------------------------------
+// the argument checks eea_sense_gain_field and eea_set_target_gain share (after their null checks), before any HIP call
+static eea_status make_gain_params(const eea_collision_cfg* cfg, unsigned range_cells, unsigned stride, eea::CollisionParams& c)
+{
+  const eea_status st = make_sense_params(cfg, c);
+  if (st != EEA_OK) return st;
+  if (range_cells == 0) return fail(EEA_ERR_INVALID_ARGUMENT, "range_cells must be positive");
+  if (stride == 0) return fail(EEA_ERR_INVALID_ARGUMENT, "stride must be positive");
+  if (range_cells > 1024u) return fail(EEA_ERR_UNSUPPORTED, "range_cells above 1024");
+  return EEA_OK;
+}
+
+eea_status eea_sense_gain_field(int device, const eea_collision_cfg* cfg, unsigned range_cells, unsigned stride,
+                                const int8_t* d_known, unsigned* d_gain, void* stream)
+{
+  if (cfg == nullptr || d_known == nullptr || d_gain == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  eea::CollisionParams c;
+  const eea_status st = make_gain_params(cfg, range_cells, stride, c);
+  if (st != EEA_OK) return st;
+  EEA_HIP(hipSetDevice(device));
+  EEA_HIP(eea::launch_gain_field(c, range_cells, stride, d_known, d_gain, static_cast<hipStream_t>(stream)));
+  return EEA_OK;
+}
+
+eea_status eea_set_target_gain(eea_engine* e, const eea_collision_cfg* cfg, unsigned range_cells, unsigned stride,
+                               const int8_t* d_known, double floor, double lx, double ly, unsigned* d_gain, void* stream)
+{
+  if (e == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null engine");
+  if (cfg == nullptr || d_known == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  eea::CollisionParams c;
+  eea_status st = make_gain_params(cfg, range_cells, stride, c);
+  if (st != EEA_OK) return st;
+  if (!(floor >= 0.0) || !std::isfinite(floor)) return fail(EEA_ERR_INVALID_ARGUMENT, "floor must be finite and >= 0");
+  if (!(lx > 0.0 && ly > 0.0)) return fail(EEA_ERR_INVALID_ARGUMENT, "bad gain target domain");
+  const size_t P = static_cast<size_t>(c.xsize) * c.ysize;
+  if (P > (static_cast<size_t>(1) << 31)) return fail(EEA_ERR_UNSUPPORTED, "a gain target of more than 2^31 cells");
+  st = enter_target(e, nullptr);
+  if (st != EEA_OK) return st;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // the engine's workspaces: a first call, or a growing one, waits for the device before it replaces them
+  const size_t need_gain = d_gain != nullptr ? 0 : sizeof(unsigned) * P, need_val = e->rs * P, need_raw = e->rs * e->K2;
+  if (need_gain > e->d_gain.cap || need_val > e->d_gain_val.cap || need_raw > e->d_raw.cap) {
+    EEA_HIP(hipDeviceSynchronize());
+    EEA_HIP(e->d_gain.reserve(need_gain));
+    EEA_HIP(e->d_gain_val.reserve(need_val));
+    EEA_HIP(e->d_raw.reserve(need_raw));
+  }
+  unsigned* const gain = d_gain != nullptr ? d_gain : static_cast<unsigned*>(e->d_gain.p);
+  e->nx = c.xsize;
+  e->ny = c.ysize;
+  e->have_fill_grid = false;
+  // gain -> value grid -> the launches of eea_spatial_coeff_rows (whole grid) and eea_set_phik_from_sums: the same bits
+  st = by_precision(e, [&](auto r) {
+    using R = decltype(r);
+    eea_status st2 = upload_axes_and_tables<R>(e, c.xsize, c.ysize, lx, ly, s);
+    if (st2 != EEA_OK) return st2;
+    st2 = reserve_tile_work<R>(e, c.xsize, c.ysize, c.ysize);
+    if (st2 != EEA_OK) return st2;
+    EEA_HIP(eea::launch_gain_field(c, range_cells, stride, d_known, gain, s));
+    EEA_HIP(eea::launch_gain_values<R>(c, stride, d_known, gain, floor, as<R>(e->d_gain_val.p), s));
+    EEA_HIP(eea::launch_spatial_coeff<R>(as<R>(e->d_gain_val.p), c.xsize, c.ysize, e->K, as<R>(e->tab.cx.p), as<R>(e->tab.cy.p),
+                                         as<R>(e->d_work.p), as<R>(e->d_raw.p), s));
+    EEA_HIP(eea::launch_normalise_by_first<R>(as<R>(e->d_raw.p), e->K2, as<R>(e->d_phik.p), s));
+    return EEA_OK;
+  });
+  if (st != EEA_OK) return st;
+  commit_phik(e, lx, ly);
   return EEA_OK;
 }
 

@@ -1,0 +1,237 @@
+// Information-gain field of a known grid (include/ergodic_amd.h, eea_sense_gain_field / eea_set_target_gain): for every
+// candidate cell -- the lattice i0 % stride == 0 && j0 % stride == 0 --, how many unknown cells the 8R rays of the range sensor
+// (sense_rays.hpp: the reveal's rays, steps, disc and blocking rule) would cross when cast from there through `known` itself,
+// counted per beam, plus one if the cell itself is unknown.  Integers only, no atomics, every element of d_gain written once.
+//
+//  - a workgroup of 256 threads owns a tile of 32 x 8 candidates, A LANE IS A CANDIDATE: the ray geometry (q, s, dx, dy and
+//    the remainder recurrence) does not depend on the lane and stays in scalar registers; per step a lane reads one cell at its
+//    own base plus a uniform offset, adds `alive & unknown` and clears `alive` on a cell that ends the ray.  A ray ends for the
+//    wavefront where it leaves the disc or no lane is alive.  No cross-lane reduction.
+//  - LDS form: the union of the tile's windows, (31 stride + 1 + 2R) x (7 stride + 1 + 2R) cells, is staged as one byte per
+//    cell -- bit 0 blocks, bit 1 unknown, bit 2 off the grid -- with coalesced row reads; the R cells of padding on every side
+//    are off-grid bytes, so the march has no bounds test and no LDS write.  Taken when the window fits the 64 KB a launch may
+//    ask for without opting in (stride 1: R <= 118; 2: R <= 109; 4: R <= 91; 8: R <= 60).
+//  - global form (everything else, up to R = 1024 and any stride): the same tile, every lane marches its own rays through
+//    `known` in global memory with march() and the clip of its cell.  Correct, and slow by the chain of dependent byte loads.
+//  Both forms zero the cells of their tile's footprint that are off the lattice (stride > 1) and store the lattice cells
+//  from the lane that owns them: no cell has two writers.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "common.hpp"
+#include "sense_rays.hpp"
+
+namespace eea
+{
+namespace
+{
+constexpr int kGainBlock = 256, kGainTX = 32, kGainTY = 8;  // a 32-lane LDS group is one row of 32 candidates
+constexpr unsigned kGainMaxBlocks = 1u << 16;                // workgroups per launch; they stride over the tiles past that
+constexpr size_t kGainLdsMax = 64u * 1024u;
+constexpr int kGainChunk = 4;  // steps of a ray whose cells are read before the first is used
+static_assert(kGainTX * kGainTY == kGainBlock, "a lane per candidate");
+
+struct GainParams
+{
+  CollisionParams c;  // the geometry (the radii are not read)
+  int R;
+  int cutoff;  // a cell blocks a ray iff cell >= cutoff (128: no cell does)
+  unsigned stride;
+  const int8_t* known;
+  unsigned* gain;
+  unsigned ncx, ncy;  // candidate columns and rows: ceil(xsize / stride), ceil(ysize / stride)
+  unsigned tiles_x;
+  unsigned long long tiles;
+  int W, H;  // the LDS window (LDS form)
+};
+
+struct Tile
+{
+  unsigned long long cx0, cy0;  // first candidate column / row
+  bool in;                      // this lane's candidate exists
+  unsigned i0, j0;              // ... its cell
+};
+__device__ __forceinline__ Tile tile_of(const GainParams& p, unsigned long long t)
+{
+  Tile k;
+  k.cx0 = (t % p.tiles_x) * kGainTX;
+  k.cy0 = (t / p.tiles_x) * kGainTY;
+  const unsigned long long cx = k.cx0 + (threadIdx.x % kGainTX), cy = k.cy0 + (threadIdx.x / kGainTX);
+  k.in = cx < p.ncx && cy < p.ncy;
+  k.j0 = k.in ? static_cast<unsigned>(cx * p.stride) : 0u;
+  k.i0 = k.in ? static_cast<unsigned>(cy * p.stride) : 0u;
+  return k;
+}
+
+// zeroes the cells of the tile's footprint that are no candidates; the candidates are stored by their lanes
+__device__ __forceinline__ void zero_off_lattice(const GainParams& p, const Tile& k)
+{
+  if (p.stride == 1u) return;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned long long x0 = k.cx0 * p.stride, y0 = k.cy0 * p.stride;  // (on the grid: the tile has a candidate)
+  unsigned long long w = static_cast<unsigned long long>(kGainTX) * p.stride, h = static_cast<unsigned long long>(kGainTY) * p.stride;
+  if (w > p.c.xsize - x0) w = p.c.xsize - x0;
+  if (h > p.c.ysize - y0) h = p.c.ysize - y0;
+  for (unsigned long long ry = wave; ry < h; ry += kGainBlock / 64) {
+    const bool lattice_row = static_cast<unsigned>(ry) % p.stride == 0u;
+    unsigned* const row = p.gain + (y0 + ry) * p.c.xsize + x0;
+    for (unsigned long long rx = lane; rx < w; rx += 64) {
+      if (!(lattice_row && static_cast<unsigned>(rx) % p.stride == 0u)) row[rx] = 0u;
+    }
+  }
+}
+
+__global__ __launch_bounds__(kGainBlock) void gain_field_lds_kernel(const GainParams p)
+{
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_win[];  // [H][W]: bit 0 blocks, bit 1 unknown, bit 2 off-grid
+  const int R = p.R, W = p.W, H = p.H, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int st = static_cast<int>(p.stride);  // (small: the window fits 64 KB)
+  const int base = ((tid / kGainTX) * st + R) * W + (tid % kGainTX) * st + R;
+  for (unsigned long long t = blockIdx.x; t < p.tiles; t += gridDim.x) {
+    __syncthreads();  // the tile before has read the window
+    const Tile k = tile_of(p, t);
+    const long long wx0 = static_cast<long long>(k.cx0 * p.stride) - R, wy0 = static_cast<long long>(k.cy0 * p.stride) - R;
+    for (int wy = wave; wy < H; wy += kGainBlock / 64) {
+      const long long gy = wy0 + wy;
+      const bool row_in = gy >= 0 && gy < static_cast<long long>(p.c.ysize);
+      const int8_t* const krow = p.known + (row_in ? static_cast<size_t>(gy) * p.c.xsize : 0);
+      unsigned char* const srow = s_win + wy * W;
+      for (int wx = lane; wx < W; wx += 64) {
+        const long long gx = wx0 + wx;
+        unsigned char b = 4;
+        if (row_in && gx >= 0 && gx < static_cast<long long>(p.c.xsize)) {
+          const int v = krow[gx];
+          b = (v >= p.cutoff ? 1 : 0) | (v < 0 ? 2 : 0);
+        }
+        srow[wx] = b;
+      }
+    }
+    zero_off_lattice(p, k);
+    __syncthreads();
+    const unsigned own = s_win[base];  // (inside the window for every lane, candidate or not)
+    const bool cand = k.in && (own & 5u) == 0u;  // a robot cannot stand in a blocking cell
+    unsigned count = cand ? (own >> 1) & 1u : 0u;
+    if (__builtin_amdgcn_ballot_w64(cand) != 0) {
+      for (int q = 0; q < 8 * R; ++q) {
+        Ray ray(q, R);  // (the same in every lane: scalar registers)
+        unsigned alive = cand ? 1u : 0u;
+        // kGainChunk steps at a time: their offsets are formed and their cells read before the first one is used, so a
+        // wavefront has that many LDS reads in flight instead of one dependent read per step
+        for (int s0 = 1; s0 <= R; s0 += kGainChunk) {
+          unsigned v[kGainChunk];
+          bool in[kGainChunk];
+#pragma unroll
+          for (int u = 0; u < kGainChunk; ++u) {
+            ray.step(R);
+            in[u] = s0 + u <= R && ray.in_disc(R);
+            // |dx|, |dy| <= R while s <= R: inside the padded window; a step that does not count reads the lane's own cell
+            v[u] = s_win[base + (in[u] ? ray.dy * W + ray.dx : 0)];
+          }
+#pragma unroll
+          for (int u = 0; u < kGainChunk; ++u) {
+            alive = in[u] ? alive : 0u;  // (uniform) past the disc or step R the ray has ended for every lane
+            count += alive & (v[u] >> 1);  // (alive is 0 / 1: bit 0 of v >> 1 is "unknown")
+            alive = (v[u] & 5u) != 0u ? 0u : alive;  // a blocking cell is counted, then ends the ray; so does the grid's edge
+          }
+          if (__builtin_amdgcn_ballot_w64(alive != 0u) == 0) break;
+        }
+      }
+    }
+    if (k.in) p.gain[static_cast<size_t>(k.i0) * p.c.xsize + k.j0] = count;
+  }
+}
+
+__global__ __launch_bounds__(kGainBlock) void gain_field_global_kernel(const GainParams p)
+{
+  const int R = p.R;
+  for (unsigned long long t = blockIdx.x; t < p.tiles; t += gridDim.x) {
+    const Tile k = tile_of(p, t);
+    zero_off_lattice(p, k);
+    if (!k.in) continue;
+    const size_t g0 = static_cast<size_t>(k.i0) * p.c.xsize + k.j0;
+    const int own = p.known[g0];
+    unsigned count = 0u;
+    if (own < p.cutoff) {
+      count = own < 0 ? 1u : 0u;
+      const Clip w = clip_of(p.c, k.i0, k.j0, R);
+      for (int q = 0; q < 8 * R; ++q) {
+        (void)march(q, R, w, [&](int dx, int dy) {
+          const int v = p.known[cell_index(p.c, k.i0, k.j0, dx, dy)];
+          count += v < 0 ? 1u : 0u;
+          return v >= p.cutoff;
+        });
+      }
+    }
+    p.gain[g0] = count;
+  }
+}
+
+// the value grid of eea_set_target_gain: (real)((double)gain + floor) on the candidates whose cell does not block, 0 elsewhere
+template <typename R>
+__global__ __launch_bounds__(kGainBlock) void gain_values_kernel(const int8_t* __restrict__ known, const unsigned* __restrict__ gain,
+                                                                 unsigned xsize, unsigned ysize, unsigned stride, int cutoff,
+                                                                 double floor, R* __restrict__ out)
+{
+  const unsigned long long x = static_cast<unsigned long long>(blockIdx.x) * kGainBlock + threadIdx.x;
+  if (x >= xsize) return;
+  const bool lattice_col = static_cast<unsigned>(x) % stride == 0u;
+  for (unsigned y = blockIdx.y; y < ysize; y += gridDim.y) {
+    const size_t g = static_cast<size_t>(y) * xsize + x;
+    const bool cand = lattice_col && y % stride == 0u && known[g] < cutoff;
+    out[g] = cand ? static_cast<R>(static_cast<double>(gain[g]) + floor) : R(0);
+  }
+}
+
+// whether the tile's window fits the LDS a launch may ask for (*bytes: its size); otherwise the march runs in global memory
+bool window_fits_lds(unsigned range_cells, unsigned stride, size_t* bytes)
+{
+  const unsigned long long W = static_cast<unsigned long long>(kGainTX - 1) * stride + 1u + 2ull * range_cells;
+  const unsigned long long H = static_cast<unsigned long long>(kGainTY - 1) * stride + 1u + 2ull * range_cells;
+  if (stride > kGainLdsMax || W * H > kGainLdsMax) return false;
+  *bytes = static_cast<size_t>(W * H);
+  return true;
+}
+}  // namespace
+
+hipError_t launch_gain_field(const CollisionParams& c, unsigned range_cells, unsigned stride, const int8_t* d_known, unsigned* d_gain,
+                             hipStream_t s)
+{
+  GainParams p;
+  p.c = c;
+  p.R = static_cast<int>(range_cells);
+  p.cutoff = blocking_cutoff(c.occupied_threshold);
+  p.stride = stride;
+  p.known = d_known;
+  p.gain = d_gain;
+  p.ncx = (c.xsize - 1u) / stride + 1u;
+  p.ncy = (c.ysize - 1u) / stride + 1u;
+  p.tiles_x = (p.ncx - 1u) / kGainTX + 1u;
+  p.tiles = static_cast<unsigned long long>(p.tiles_x) * ((p.ncy - 1u) / kGainTY + 1u);
+  p.W = p.H = 0;
+  const unsigned blocks = p.tiles < kGainMaxBlocks ? static_cast<unsigned>(p.tiles) : kGainMaxBlocks;
+  size_t lds = 0;
+  if (window_fits_lds(range_cells, stride, &lds)) {
+    p.W = (kGainTX - 1) * static_cast<int>(stride) + 1 + 2 * p.R;
+    p.H = (kGainTY - 1) * static_cast<int>(stride) + 1 + 2 * p.R;
+    hipLaunchKernelGGL(gain_field_lds_kernel, dim3(blocks), dim3(kGainBlock), lds, s, p);
+  } else {
+    hipLaunchKernelGGL(gain_field_global_kernel, dim3(blocks), dim3(kGainBlock), 0, s, p);
+  }
+  return hipGetLastError();
+}
+
+template <typename R>
+hipError_t launch_gain_values(const CollisionParams& c, unsigned stride, const int8_t* d_known, const unsigned* d_gain, double floor,
+                              R* d_values, hipStream_t s)
+{
+  const unsigned bx = (c.xsize - 1u) / kGainBlock + 1u, by = c.ysize < 65535u ? c.ysize : 65535u;
+  hipLaunchKernelGGL(gain_values_kernel<R>, dim3(bx, by), dim3(kGainBlock), 0, s, d_known, d_gain, c.xsize, c.ysize, stride,
+                     blocking_cutoff(c.occupied_threshold), floor, d_values);
+  return hipGetLastError();
+}
+template hipError_t launch_gain_values<double>(const CollisionParams&, unsigned, const int8_t*, const unsigned*, double, double*,
+                                               hipStream_t);
+template hipError_t launch_gain_values<float>(const CollisionParams&, unsigned, const int8_t*, const unsigned*, double, float*,
+                                              hipStream_t);
+}  // namespace eea

@@ -25,6 +25,7 @@
 
 #include "common.hpp"
 #include "grid_cell.hpp"
+#include "sense_rays.hpp"  // Clip, clip_of, march: shared with gain_kernel.hip
 
 namespace eea
 {
@@ -46,57 +47,6 @@ struct SenseParams
   int* ranges;         // [P][8R] or null
   unsigned P;
 };
-
-// what a robot at (i0, j0) can touch: offsets [xlo, xhi] x [ylo, yhi] of [-R, R]^2 that fall on the grid
-struct Clip
-{
-  int xlo, xhi, ylo, yhi;
-};
-__device__ __forceinline__ Clip clip_of(const CollisionParams& c, unsigned i0, unsigned j0, int R)
-{
-  Clip w;
-  const unsigned uR = static_cast<unsigned>(R), rx = c.xsize - 1u - j0, ry = c.ysize - 1u - i0;
-  w.xlo = j0 < uR ? -static_cast<int>(j0) : -R;
-  w.xhi = rx < uR ? static_cast<int>(rx) : R;
-  w.ylo = i0 < uR ? -static_cast<int>(i0) : -R;
-  w.yhi = ry < uR ? static_cast<int>(ry) : R;
-  return w;
-}
-
-// ray q of a robot: steps s = 1 .. R until the ray leaves the disc or the grid, or visit(dx, dy) says the cell blocks;
-// returns the range s of the blocking cell or -1
-template <typename Visit>
-__device__ __forceinline__ int march(int q, int R, const Clip& w, Visit visit)
-{
-  const int side = q / (2 * R), k = q - side * 2 * R;
-  const int tx = side == 0 ? R : side == 1 ? R - k : side == 2 ? -R : -R + k;
-  const int ty = side == 0 ? -R + k : side == 1 ? R : side == 2 ? R - k : -R;
-  const int ax2 = 2 * (tx < 0 ? -tx : tx), ay2 = 2 * (ty < 0 ? -ty : ty);
-  const int sx = tx > 0 ? 1 : tx < 0 ? -1 : 0, sy = ty > 0 ? 1 : ty < 0 ? -1 : 0;
-  int remx = R, remy = R, dx = 0, dy = 0;  // (2 s |m| + R) = (2R) (|d|) + rem
-  for (int s = 1; s <= R; ++s) {
-    remx += ax2;
-    if (remx >= 2 * R) {
-      remx -= 2 * R;
-      dx += sx;
-    }
-    remy += ay2;
-    if (remy >= 2 * R) {
-      remy -= 2 * R;
-      dy += sy;
-    }
-    if (dx * dx + dy * dy > R * R) break;
-    if (dx < w.xlo || dx > w.xhi || dy < w.ylo || dy > w.yhi) break;
-    if (visit(dx, dy)) return s;
-  }
-  return -1;
-}
-
-__device__ __forceinline__ size_t cell_index(const CollisionParams& c, unsigned i0, unsigned j0, int dx, int dy)
-{
-  return (static_cast<size_t>(i0) + static_cast<size_t>(static_cast<long long>(dy))) * c.xsize +
-         (static_cast<size_t>(j0) + static_cast<size_t>(static_cast<long long>(dx)));
-}
 
 // the robot of this workgroup's turn: false when the mask leaves it out or its cell is off the grid (mapping.cpp:81-86's
 // rule; its row of ranges is then -1)

@@ -3,7 +3,10 @@
 // With it the loop of a fleet that explores a map it has not seen,
 //     senseReveal(cfg, R, d_truth, d_known, d_pose, n, ..); gridCensus(cfg, d_known, d_counts, ..);
 //     appendSample(..); eea_tick_batch(.. d_grid = d_known ..); eea_integrate_twist_batch(..);
-// stays on one stream; the known grid becomes the target through eea_set_target_occupancy (entropy(), numerics.hpp:164-179).
+// stays on one stream.  The known grid becomes the target either through eea_set_target_occupancy (entropy(),
+// numerics.hpp:164-179: every unknown cell 0.7, every known one 1e-3; it waits for its stream) or through
+//     setTargetGain(engine, cfg, R, stride, d_known, floor, lx, ly, ..);
+// -- what a scan from each cell would reveal (senseGainField), which is zero where nothing is left to see and needs no host wait.
 // This is the simulated counterpart of a 360 degree range finder (reference README.md:74-76), not OccupancyMapper (mapping.hpp).
 #pragma once
 
@@ -33,5 +36,24 @@ inline void gridCensus(const eea_collision_cfg& cfg, const std::int8_t* d_grid, 
                        void* stream = nullptr)
 {
   throw_on_error(eea_grid_census(device_ordinal(), &cfg, d_grid, d_counts, stream));
+}
+
+// d_gain [ysize][xsize] (every element overwritten) = for every candidate cell -- both indices multiples of stride, the cell
+// itself not blocking -- the unknown cells the sensor's 8 * range_cells rays would cross from there through d_known, counted
+// per beam, + 1 for an unknown own cell; 0 elsewhere.  Integers; asynchronous
+inline void senseGainField(const eea_collision_cfg& cfg, unsigned int range_cells, unsigned int stride, const std::int8_t* d_known,
+                           unsigned int* d_gain, void* stream = nullptr)
+{
+  throw_on_error(eea_sense_gain_field(device_ordinal(), &cfg, range_cells, stride, d_known, d_gain, stream));
+}
+
+// that field + floor on the candidates -> the engine's phi_k on the domain (lx, ly), all on `stream` and without a host wait
+// on a repeated call; d_gain (optional) receives the integer field.  floor > 0 keeps the target finite (uniform over the free
+// candidates) once nothing is left to see
+inline void setTargetGain(eea_engine* engine, const eea_collision_cfg& cfg, unsigned int range_cells, unsigned int stride,
+                          const std::int8_t* d_known, double floor, double lx, double ly, unsigned int* d_gain = nullptr,
+                          void* stream = nullptr)
+{
+  throw_on_error(eea_set_target_gain(engine, &cfg, range_cells, stride, d_known, floor, lx, ly, d_gain, stream));
 }
 }  // namespace ergodic_exploration

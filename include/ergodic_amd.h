@@ -741,6 +741,46 @@ eea_status eea_sense_reveal_batch(int device, const eea_collision_cfg* cfg, unsi
 eea_status eea_grid_census(int device, const eea_collision_cfg* cfg, const int8_t* d_grid, unsigned long long* d_counts,
                            void* stream);
 
+/* ---- information-gain target of an exploring fleet (additive to ABI 6: detect these entries by symbol) -------------------------
+ * What a scan from each cell of the KNOWN grid would reveal, as the target phi_k: the exact, integer form of the reference's
+ * description (README.md:74-76: information obtained by "simulating a 360 degree range finder", "zero after the robot has fully
+ * explored the space") with the sensor eea_sense_reveal_batch defines.  It is not FCMI (no noise model, no expectation over
+ * measurements): a count of the unknown cells the sensor's beams would cross.  Against the entropy() surrogate of
+ * eea_set_target_occupancy: an unknown cell no ray can reach attracts nobody, the field is zero once nothing is left to see,
+ * and the re-target needs no host wait.
+ * eea_sense_gain_field: d_known (int8 [ysize][xsize], read only) -> d_gain (uint32 [ysize][xsize], EVERY element overwritten).
+ * With R = range_cells and the rays, step offsets d(m, s), disc test, grid test and
+ * blocks(cell) = !(cell / 100.0 < occupied_threshold) exactly as eea_sense_reveal_batch defines them above:
+ *   a cell (i0, j0) with i0 % stride == 0 && j0 % stride == 0 is a candidate; every other cell gets 0;
+ *   a candidate whose own cell blocks gets 0 (a robot cannot stand there);
+ *   any other candidate gets [known[i0][j0] < 0] + sum over the 8R rays q, over the steps s ray q makes from (i0, j0) when it is
+ *     cast through `known` itself, of [known[i][j] < 0]: the ray ends where it leaves the disc or the grid; it also ends on the
+ *     first blocking cell, which is visited -- and counted if it is negative -- before it ends the ray; unknown cells let the
+ *     ray through, as they do in the reveal.
+ * The sum is PER BEAM: a cell that several rays cross counts once per ray, as beam-based mutual-information estimators count
+ * (near the candidate the rays overlap about 2.5-fold); it is not the number of distinct cells a reveal would change (which,
+ * for a truth that is free wherever `known` is unknown, it bounds from above and shares its zero set with).  The largest value is 8 R^2 + 1 <= 2^23 + 1: exact in fp32 too.
+ * Integers only, no atomics across workgroups, a pure function of (known, cfg, R, stride).  Asynchronous on `stream`: reads
+ * nothing on the host, allocates nothing and makes no synchronising call.  Before any HIP call -- EEA_ERR_INVALID_ARGUMENT: cfg,
+ * d_known or d_gain null; xsize or ysize 0; resolution <= 0; range_cells == 0; stride == 0.  EEA_ERR_UNSUPPORTED: range_cells >
+ * 1024.
+ * eea_set_target_gain: that field -> phi_k of engine e, all on `stream`.  The value grid is nx = xsize, ny = ysize in the
+ * engine's real: v[i][j] = (real)((double)gain[i][j] + floor) on the candidates whose cell does not block, 0 elsewhere -- with
+ * floor > 0 the target of a fully explored map degrades to uniform over the free candidates.  phi_k is BITWISE what
+ * eea_spatial_coeff_rows (whole grid: row0 = 0, nrows = ny) followed by eea_set_phik_from_sums give for v: the same launches.
+ * d_gain (optional) receives the integer field.  The field and value workspaces belong to the engine: a first call, or a
+ * growing one, may wait for the device to allocate; a repeated call reads nothing on the host, allocates nothing and makes no
+ * synchronising call, and control calls enqueued on `stream` afterwards use the new phi_k.  The engine's bookkeeping is left as
+ * eea_set_target_occupancy leaves it (the grid's nx / ny, no Target::fill grid to read back, an in-flight
+ * eea_config_domain_async rebuild is waited for first).  With floor == 0 and zero total gain phi_k is non-finite (0 / 0), exactly
+ * as an all-zero grid is through those two entries: a caller stops on eea_grid_census or passes a floor.
+ * Before any launch -- the field call's errors (d_gain may be null), and EEA_ERR_INVALID_ARGUMENT: e null; floor negative or not
+ * finite; lx or ly <= 0.  EEA_ERR_UNSUPPORTED: xsize * ysize > 2^31.  eea_abi_version() stays 6. */
+eea_status eea_sense_gain_field(int device, const eea_collision_cfg* cfg, unsigned range_cells, unsigned stride,
+                                const int8_t* d_known, unsigned* d_gain, void* stream);
+eea_status eea_set_target_gain(eea_engine* e, const eea_collision_cfg* cfg, unsigned range_cells, unsigned stride,
+                               const int8_t* d_known, double floor, double lx, double ly, unsigned* d_gain, void* stream);
+
 /* The collision / DWA / tick calls keep small device caches between calls (the ring offsets per radii, one
  * inflated-map buffer per (device, stream)).  A long-running process that changes streams or map sizes
  * can drop them; synchronises the devices involved.  No reference counterpart. */
