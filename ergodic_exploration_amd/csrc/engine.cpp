@@ -886,6 +886,28 @@ eea_status make_dwa_params(const eea_dwa_cfg* dcfg, eea::DwaParams& d)
   return EEA_OK;
 }
 
+// The trajectory objective (dynamic_window.cpp:258-286) reads column round((n_ref - 1) t / tf) of the reference at every
+// rollout step, tf = n_ref dt_ref; the reference's xt_ref.col(j) (:277) is bounds-checked and throws.  The kernel's own
+// expression with t accumulated by repeated += dt, on the host: the call is refused when a step would read outside
+// [0, n_ref - 1] (for robot r that is robot r + 1's trajectory, or memory behind the buffer) or when tf is not positive
+// (dt_ref = 0: the index is NaN).
+eea_status check_reference_index(const eea::DwaParams& d, unsigned n_ref, double dt_ref)
+{
+  const double tf = static_cast<double>(n_ref) * dt_ref;
+  if (!(tf > 0.0)) return fail(EEA_ERR_INVALID_ARGUMENT, "the reference trajectory needs n_ref * dt_ref > 0");
+  const double last = static_cast<double>(n_ref - 1);
+  double t = 0.0;
+  for (unsigned st = 0; st < d.steps; ++st) {
+    const double jj = std::round(last * t / tf);
+    if (!(jj >= 0.0 && jj <= last)) {
+      return fail(EEA_ERR_INVALID_ARGUMENT, "the DWA rollout runs past the reference trajectory (step " + std::to_string(st) +
+                                                " reads column " + std::to_string(jj) + " of " + std::to_string(n_ref) + ")");
+    }
+    t += d.dt;
+  }
+  return EEA_OK;
+}
+
 // ---- resident single-robot workgroup (control_kernel_impl.hpp control_resident_kernel) --------------------------------------
 // idle time of a resident workgroup in ticks of the constant 100 MHz clock (EEA_OPT_RESIDENT_IDLE_MS, default 250 ms: a 10 Hz
 // loop keeps it alive)
@@ -2018,6 +2040,9 @@ eea_status eea_tick_batch(eea_engine* e, unsigned B, const eea_batch_io* io, con
   eea::DwaParams d;
   st = make_dwa_params(dcfg, d);
   if (st != EEA_OK) return st;
+  // the dynamic window tracks optTraj(): T columns every cfg.dt (before step 1: a refused tick leaves follow_dwa / i alone)
+  st = check_reference_index(d, static_cast<unsigned>(e->T), e->cfg.dt);
+  if (st != EEA_OK) return st;
   if (!e->have_phik) return fail(EEA_ERR_NO_TARGET, "no target set");
   st = use_device(e);
   if (st != EEA_OK) return st;
@@ -2067,6 +2092,10 @@ eea_status eea_dwa_control_batch(int device, const eea_collision_cfg* ccfg, cons
   eea::DwaParams d;
   st = make_dwa_params(dcfg, d);
   if (st != EEA_OK) return st;
+  if (d_xt_ref != nullptr) {
+    st = check_reference_index(d, n_ref, dt_ref);
+    if (st != EEA_OK) return st;
+  }
   EEA_HIP(hipSetDevice(device));
   EEA_HIP(eea::launch_dwa_control(c, d, d_grid, d_x0, d_vb, d_vref, d_xt_ref, n_ref, dt_ref, P, d_u_opt,
                                   d_found, static_cast<hipStream_t>(stream)));

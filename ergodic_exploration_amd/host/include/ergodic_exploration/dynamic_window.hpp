@@ -49,7 +49,9 @@ public:
     return run(grid, x0, vb, &vref, nullptr, 0.0);
   }
 
-  // best twist for following the reference trajectory xt_ref (3 x n), sampled every dt_ref
+  // best twist for following the reference trajectory xt_ref (3 x n), sampled every dt_ref; throws std::invalid_argument
+  // (a std::logic_error, like the reference's bounds-checked xt_ref.col(j), dynamic_window.cpp:277) when a rollout step
+  // would read a column past the last one or n * dt_ref is not positive -- eea_dwa_control_batch refuses such a call
   std::tuple<bool, vec> control(const GridMap& grid, const vec& x0, const vec& vb, const mat& xt_ref,
                                 double dt_ref) const
   {

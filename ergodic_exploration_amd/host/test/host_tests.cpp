@@ -317,6 +317,26 @@ static void test_device_ops()
     CHECK(u(0) > 0.0);
     CHECK_NEAR(u(2), 0.0, 1e-12);
   }
+  {
+    // a reference the rollout runs past (10 steps of 0.1 on 8 columns: the last step reads column 8): the reference's
+    // xt_ref.col(j) throws std::logic_error (dynamic_window.cpp:277), and so does the mirror
+    mat ref(3, 8);
+    for (int i = 0; i < 8; ++i) ref(0, i) = 3.5 + 0.02 * (i + 1);
+    bool threw = false;
+    try {
+      (void)dwa.control(g, vec{ 3.5, 1.5, 0.0 }, vec{ 0.2, 0.0, 0.0 }, ref, 0.1);
+    } catch (const std::logic_error&) {
+      threw = true;
+    }
+    CHECK(threw);
+    threw = false;
+    try {
+      (void)dwa.control(g, vec{ 3.5, 1.5, 0.0 }, vec{ 0.2, 0.0, 0.0 }, ref, 0.0);   // dt_ref = 0: no column at all
+    } catch (const std::logic_error&) {
+      threw = true;
+    }
+    CHECK(threw);
+  }
 }
 
 // closed loop of SURVEY.md 8(c): free 12 x 6 m map at 0.05 m, origin (-1,-1), two yaml Gaussians,

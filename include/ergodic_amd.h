@@ -527,7 +527,12 @@ eea_status eea_integrate_twist_batch(int device, const double* d_x0, const doubl
  *   mode "vref"  (d_xt_ref == NULL): cost = |vref - u|^2,            d_vref [P][3]
  *   mode "traj"  (d_xt_ref != NULL): cost = distance to the reference trajectory
  *                                     d_xt_ref [P][n_ref][3], time step dt_ref
- * d_u_opt [P][3] out, d_found [P] out (0 = "DWA Failed! Not even 1 solution found"). */
+ * d_u_opt [P][3] out, d_found [P] out (0 = "DWA Failed! Not even 1 solution found").
+ * Mode "traj" reads column round((n_ref - 1) t / (n_ref dt_ref)) of the reference at every rollout step, t = 0, dt, 2 dt, ...
+ * by repeated += over the (unsigned)|horizon / dt| steps.  The reference's xt_ref.col(j) (:277) throws past the last column;
+ * here the call returns EEA_ERR_INVALID_ARGUMENT before anything is launched (d_u_opt / d_found untouched) when
+ * !(n_ref * dt_ref > 0) or when a step's column lies outside [0, n_ref - 1] -- e.g. dt = dt_ref = 0.1, horizon 2.0 needs
+ * n_ref >= 19.  More than 8192 samples: EEA_ERR_UNSUPPORTED (the costs of one robot's samples live in 64 KiB of LDS). */
 typedef struct {
   double dt, horizon, acc_dt, acc_lim_x, acc_lim_y, acc_lim_th;
   double max_vel_x, min_vel_x, max_vel_y, min_vel_y, max_rot_vel, min_rot_vel;
@@ -553,7 +558,10 @@ eea_status eea_dwa_control_batch(int device, const eea_collision_cfg* ccfg, cons
  * d_dwa_count, d_u.  addStateMemory (:209) and sampleMemory come in front of the tick: io->d_mem_cols / d_n_mem as for eea_control_batch, filled on
  * the same stream by eea_replay_append_sample (the fleet's replay memory in device memory, below) or by the caller.
  * io->d_u0, d_traj, d_skip are ignored (the tick supplies its own); everything else of io is passed to the control call.
- * fp64 engines only (poses and twists are the doubles the collision / DWA kernels take). */
+ * fp64 engines only (poses and twists are the doubles the collision / DWA kernels take).
+ * Step 4 tracks optTraj(): T = eea_steps(e) columns every cfg.dt.  A dynamic-window rollout that would read past them (the
+ * rule of eea_dwa_control_batch with n_ref = T, dt_ref = cfg.dt: e.g. an engine horizon of 1.0 under a DWA horizon of 2.0) is
+ * refused with EEA_ERR_INVALID_ARGUMENT before step 1: nothing is launched, the state and the outputs stay as they were. */
 typedef struct {
   int* d_follow_dwa;      /* [B]       in/out: follow_dwa (:191)                                                 */
   unsigned* d_dwa_count;  /* [B]       in/out: i (:194)                                                          */

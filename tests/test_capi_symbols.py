@@ -85,6 +85,23 @@ def test_argument_errors_do_not_need_a_device():
     assert L.eea_comm_create(0, 2, 0, None, C.byref(h)) == capi.ERR_INVALID_ARGUMENT  # nranks > 1 needs an id
     assert L.eea_comm_get_unique_id(None) == capi.ERR_INVALID_ARGUMENT
     assert L.eea_comm_nranks(None) == 1 and L.eea_comm_rank(None) == 0
+    # dynamic window: a reference trajectory the rollout would read past, dt_ref = 0 and too many samples are refused before
+    # the device is selected (the buffers are host arrays nothing may touch)
+    ccfg = capi.make_collision_cfg(-2.0, -1.0, 0.1, 80, 60, 0.7, 1.0, 0.2, 0.8)
+    omni = (0.1, 2.0, 0.2, 1.0, 1.0, 1.0, 1.0, -1.0, 1.0, -1.0, 2.0, -2.0, 3, 8, 5)
+    grid, x0, vb, xt = np.zeros(80 * 60, dtype=np.int8), np.zeros((2, 3)), np.zeros((2, 3)), np.zeros((2, 20, 3))
+    u, found = np.full((2, 3), 7.0), np.full(2, 7, dtype=np.int32)
+    p = lambda a: C.c_void_p(a.ctypes.data)
+
+    def dwa(cfg, n_ref, dt_ref):
+        return L.eea_dwa_control_batch(0, C.byref(ccfg), C.byref(capi.DwaCfg(*cfg)), p(grid), p(x0), p(vb), None, p(xt), n_ref, dt_ref,
+                                       2, p(u), p(found), None)
+    assert dwa(omni, 18, 0.1) == capi.ERR_INVALID_ARGUMENT      # dt = dt_ref = 0.1, horizon 2.0: column 18 of 18
+    assert b"reference" in L.eea_last_error()
+    assert dwa(omni, 20, 0.0) == capi.ERR_INVALID_ARGUMENT      # tf = 0: a NaN index
+    assert dwa(omni, 0, 0.1) == capi.ERR_INVALID_ARGUMENT
+    assert dwa(omni[:12] + (17, 17, 29), 20, 0.1) == capi.ERR_UNSUPPORTED
+    assert (u == 7.0).all() and (found == 7).all()
 
 
 def test_options_need_no_device_and_reject_bad_values():

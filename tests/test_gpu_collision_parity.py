@@ -202,3 +202,103 @@ def test_integrate_twist_batch_matches_the_oracle():
     capi.integrate_twist_batch(d_x, d_u, 0.1)
     torch.cuda.synchronize()
     assert torch.equal(d_x, out)
+
+
+# ---- the heading seam and un-normalised headings (where the fast rollout trig leaves the literal form) -----------
+
+PI = float(np.pi)
+
+
+def _near_cell_edge(g_res, xmin, ymin, x0, u, dt, steps, tol=1e-12):
+    """True when a position of the ORACLE's own rollout of (x0, u) lies within tol metres of a cell edge"""
+    x = np.array(x0, dtype=np.float64)
+    for _ in range(steps):
+        x = po.integrate_twist(x, u, dt)
+        x[2] = po.normalize_angle_PI(x[2])
+        for v, lo in ((x[0], xmin), (x[1], ymin)):
+            c = (v - lo) / g_res
+            if abs(c - np.round(c)) * g_res <= tol:
+                return True
+    return False
+
+
+def test_validate_control_on_the_heading_seam():
+    """validate_control's rollout wraps the heading every step (numerics.hpp:325); the kernel's wrap multiplies by 1 / (2 pi)
+    and its sin / cos reduce theta / pi.  Start headings ON the seam (+-pi, one ulp inside, +-3 pi, +-0) and far outside
+    [-pi, pi) (the first step's sin / cos see them un-normalised), and for a quarter of the poses a turn rate that carries
+    theta across +-pi inside the five steps.  No verdict may differ from the oracle's; a pose may be dropped only where the
+    oracle's own rollout passes within 1e-12 m of a cell edge (at most 0.1 %; with this seed the oracle shows none)."""
+    g, cfg, data = _grid()
+    rng = np.random.default_rng(23)
+    P, dt, horizon = 2000, 0.1, 0.5
+    seam = np.array([PI, -PI, np.nextafter(PI, 0.0), np.nextafter(-PI, 0.0), 3.0 * PI, -3.0 * PI, 0.0, -0.0])
+    x0 = np.empty((P, 3))
+    x0[:, 0] = rng.uniform(-0.5, 3.5, P)
+    x0[:, 1] = rng.uniform(-1.5, 1.5, P)
+    x0[:, 2] = rng.uniform(-50.0, 50.0, P)
+    x0[::2, 2] = seam[np.arange(P // 2) % len(seam)]
+    u = np.stack([rng.uniform(-1, 1, P), rng.uniform(-1, 1, P), rng.uniform(-2, 2, P)], 1)
+    u[::7, 2] = 0.0
+    # every fourth pose: the wrapped heading reaches the nearer seam after 0.5 .. 4.5 of the 5 steps
+    cross = np.arange(1, P, 4)
+    thw = np.array([po.normalize_angle_PI(t) for t in x0[cross, 2]])
+    u[cross, 2] = np.where(thw >= 0.0, PI - thw, -PI - thw) / (dt * rng.uniform(0.5, 4.5, len(cross)))
+    crossed = 0
+    for i in cross:
+        th, seen = x0[i, 2], False
+        for _ in range(5):
+            nxt = po.normalize_angle_PI(th) + u[i, 2] * dt
+            seen = seen or abs(nxt) >= PI
+            th = nxt
+        crossed += seen
+    assert crossed >= len(cross) - len(seam)      # (all but the starts that sit on the seam already and turn away from it)
+    ref = np.array([po.validate_control(COLL, g, x0[i], u[i], dt, horizon) for i in range(P)], dtype=np.int32)
+    d_valid = torch.full((P,), -1, dtype=torch.int32, device="cuda")
+    capi.validate_control_batch(cfg, torch.as_tensor(data).cuda(), torch.as_tensor(x0).cuda(), torch.as_tensor(u).cuda(), dt,
+                                horizon, d_valid)
+    torch.cuda.synchronize()
+    got = d_valid.cpu().numpy()
+    differ = np.nonzero(got != ref)[0]
+    print("validate_control on the seam: %d of %d verdicts differ %s" % (len(differ), P, differ[:10]))
+    for i in differ:
+        assert _near_cell_edge(0.1, -1.0, -2.0, x0[i], u[i], dt, 5), (i, x0[i], u[i], got[i], ref[i])
+    assert len(differ) <= P // 1000
+    assert 0 < ref.sum() < P
+
+
+def test_integrate_twist_normalised_heading_on_the_seam():
+    """eea_integrate_twist_batch(normalize_heading): theta + d2 swept over the wrap's seam -- +-pi and 1 .. 4 ulp either side,
+    +-3 pi, +-(2 pi - 1e-15) -- with d2 = 0 (the straight-line branch: theta IS the sum) and d2 = +-0.05.  The output lies in
+    [-pi, pi) and within 4 ulp(pi) of the oracle's normalize_angle_PI in CIRCULAR distance (the reference can return +pi where
+    the engine returns -pi: the convention pinned in test_integrate_twist_batch_matches_the_oracle)."""
+    targets = []
+    for s in (1.0, -1.0):
+        v = s * PI
+        targets.append(v)
+        up, dn = v, v
+        for _ in range(4):
+            up, dn = float(np.nextafter(up, np.inf)), float(np.nextafter(dn, -np.inf))
+            targets += [up, dn]
+        targets += [s * 3.0 * PI, s * (2.0 * PI - 1e-15)]
+    targets = np.array(targets)
+    dt = 0.1
+    x, u = [], []
+    for w in (0.0, 0.5, -0.5):
+        for t in targets:
+            x.append([1.0, -2.0, t - w * dt])
+            u.append([0.3, -0.2, w])
+    x, u = np.array(x), np.array(u)
+    P = len(x)
+    assert np.array_equal(x[:len(targets), 2] + u[:len(targets), 2] * dt, targets)
+    wrapped = torch.empty((P, 3), dtype=torch.float64, device="cuda")
+    capi.integrate_twist_batch(torch.as_tensor(x).cuda(), torch.as_tensor(u).cuda(), dt, out=wrapped, normalize_heading=True)
+    torch.cuda.synchronize()
+    gw = wrapped.cpu().numpy()[:, 2]
+    ref = np.array([po.normalize_angle_PI(po.integrate_twist(x[i], u[i], dt)[2]) for i in range(P)])
+    d = np.abs(gw - ref)
+    circ = np.minimum(d, 2.0 * PI - d)
+    print("wrapped heading on the seam: max circular distance %.3g (4 ulp(pi) = %.3g), range [%.17g, %.17g]"
+          % (circ.max(), 4 * np.spacing(PI), gw.min(), gw.max()))
+    assert (gw >= -PI).all() and (gw < PI).all(), gw[(gw < -PI) | (gw >= PI)]
+    assert (circ <= 4 * np.spacing(PI)).all(), (x[circ.argmax()], gw[circ.argmax()], ref[circ.argmax()])
+    assert (ref < 0).any() and (ref > 0).any()

@@ -174,3 +174,47 @@ def test_tick_argument_errors():
                        args["valid"], args["skip"], ccfg, capi.DwaCfg(*DWA["omni"]), 0.1, 0.5)
     assert ei.value.status == capi.ERR_UNSUPPORTED
     e32.close()
+
+
+def test_tick_is_refused_when_the_dynamic_window_outruns_opt_traj():
+    """Step 4 tracks optTraj(): T columns every dt.  An engine horizon of 1.0 (T = 10) under the cart's DWA horizon of 2.0
+    would read column 17 of 10 -- the next robot's trajectory, memory behind the buffer for the last robot -- where the
+    reference's xt_ref.col(j) throws (dynamic_window.cpp:277).  The tick is refused before its first launch: followers do
+    not count a step, no output is written.  The same tick on the 5.0 horizon of the yaml files is accepted."""
+    lim = np.array([1.0, 0.0, 2.0])
+    B = 6
+    ccfg = capi.make_collision_cfg(-1.0, -1.0, 0.05, 240, 120, *COLL)
+    dcfg = capi.DwaCfg(*DWA["simple_cart"])
+    rng = np.random.default_rng(2)
+    for horizon, refused in ((1.0, True), (5.0, False)):
+        eng = capi.Engine(capi.make_config(capi.MODEL_SIMPLE_CART, 0.1, horizon, 0.1, 1.0, 10, np.diag([1.0, 0.0, 2.0]), -lim, lim))
+        eng.set_target_gaussians([[2.5, 2.5], [8.5, 2.5]], [[1.5, 1.5], [1.5, 1.5]])
+        eng.config_domain((-1.0, 11.0, -1.0, 5.0))
+        T = eng.T
+        assert T == (10 if refused else 50)
+        state = dict(pose=torch.as_tensor(np.stack([rng.uniform(1, 9, B), rng.uniform(0, 4, B), rng.uniform(-1, 1, B)], 1)).cuda(),
+                     ut=torch.as_tensor(rng.uniform(-0.5, 0.5, (B, T, 3))).cuda(),
+                     follow=torch.tensor([1, 0, 1, 0, 1, 0], dtype=torch.int32, device="cuda"),
+                     count=torch.tensor([3, 0, 7, 0, 19, 0], dtype=torch.int32, device="cuda"),
+                     u=torch.as_tensor(rng.uniform(-0.5, 0.5, (B, 3))).cuda(), vb=torch.zeros((B, 3), dtype=torch.float64, device="cuda"),
+                     grid=torch.zeros((120, 240), dtype=torch.int8, device="cuda"),
+                     traj=torch.full((B, T, 3), -7.0, dtype=torch.float64, device="cuda"),
+                     valid=torch.full((B,), -7, dtype=torch.int32, device="cuda"), skip=torch.full((B,), -7, dtype=torch.int32, device="cuda"),
+                     source=torch.full((B,), -7, dtype=torch.int32, device="cuda"))
+        before = {k: v.clone() for k, v in state.items()}
+        tick = lambda: eng.tick_batch(B, state["pose"], state["ut"], state["follow"], state["count"], state["u"], state["vb"],
+                                      state["grid"], state["traj"], state["valid"], state["skip"], ccfg, dcfg, 0.1, 0.5,
+                                      source=state["source"])
+        if refused:
+            with pytest.raises(capi.EngineError) as ei:
+                tick()
+            assert ei.value.status == capi.ERR_INVALID_ARGUMENT and "reference" in str(ei.value)
+            torch.cuda.synchronize()
+            for k in state:
+                assert torch.equal(state[k], before[k]), k
+        else:
+            tick()
+            torch.cuda.synchronize()
+            assert state["count"].tolist() == [4, 0, 8, 0, 20, 0]      # the followers counted a step (the last one replans)
+            assert (state["valid"] >= 0).all() and (state["source"] >= 0).all()
+        eng.close()
