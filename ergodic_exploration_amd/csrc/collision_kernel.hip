@@ -10,16 +10,16 @@
 // the occupied cells scatter a 1 to every centre that would see them, and a collision check becomes
 // one byte lookup (a robot centred inside a small obstacle still reports no collision: cells closer
 // than r_bnd are not in the set, as in the reference).
-#include <algorithm>
 #include <cstdint>
 #include <cstdlib>
 #include <mutex>
-#include <utility>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/ergodic_amd.h"
 #include "common.hpp"
-#include "grid_cell.hpp"  // cast_u32_x86, world_to_grid (grid.cpp:143-159): shared with sense_kernel.hip
+#include "grid_cell.hpp"      // cast_u32_x86, world_to_grid (grid.cpp:143-159): shared with sense_kernel.hip
+#include "hit_map_table.hpp"  // ring_offsets, HitMapTable: the host-side policy of the inflated map
 
 namespace eea
 {
@@ -89,9 +89,9 @@ __device__ __forceinline__ bool collision_check(const CollisionParams& c,
 // hit map over the centres [-R, xsize + R) x [-R, ysize + R), R = r_col, row-major
 struct HitMap
 {
-  const uint8_t* cells;
-  int R, w, h;    // w = xsize + 2R, h = ysize + 2R
-  uint8_t stamp;  // a cell is marked iff it holds this build's stamp (older stamps are stale, no clear)
+  const uint8_t* cells = nullptr;  // (all zero: the ring-search instances take a map they never read)
+  int R = 0, w = 0, h = 0;         // w = xsize + 2R, h = ysize + 2R
+  uint8_t stamp = 0;               // a cell is marked iff it holds this build's stamp (older stamps are stale, no clear)
 };
 
 // grid cell of a world point as collisionCheck derives it (grid.cpp:143-159), as signed ints
@@ -209,6 +209,41 @@ __device__ __forceinline__ bool pose_collides(const CollisionParams& c, const in
   return collision_check(c, grid, px, py);
 }
 
+// The steps of a constant-twist rollout, written ONCE: this translation unit is compiled without FMA contraction and the sums
+// keep the reference's order and parentheses, so every caller gets the same bits.  FAST: sin / cos by tick_sincos (the
+// rollouts), otherwise by the device library (integrate_twist_kernel).
+
+// body-frame displacement of one step of the twist (u0, u1, u2) (numerics.hpp:273-297): the same every step
+template <bool FAST>
+__device__ __forceinline__ void body_displacement(double u0, double u1, double u2, double dt, double& d0, double& d1, double& d2)
+{
+  if (fabs(u2 - 0.0) < 1.0e-12) {
+    d0 = u0 * dt;
+    d1 = u1 * dt;
+    d2 = 0.0;
+  } else {
+    const double vb0 = u0 * dt, vb1 = u1 * dt, vb2 = u2 * dt;
+    double s, cc;
+    if constexpr (FAST) tick_sincos(vb2, &s, &cc);
+    else sincos(vb2, &s, &cc);
+    d0 = (vb0 * s + vb1 * (cc - 1.0)) / vb2;
+    d1 = (vb1 * s + vb0 * (1.0 - cc)) / vb2;
+    d2 = vb2;
+  }
+}
+
+// x + Rot(theta) d; the heading wrapped to [-pi, pi) (validate_control, numerics.hpp:325) or left as it is
+template <bool FAST>
+__device__ __forceinline__ void advance_pose(double& x, double& y, double& th, double d0, double d1, double d2, bool wrap)
+{
+  double s, cc;
+  if constexpr (FAST) tick_sincos(th, &s, &cc);
+  else sincos(th, &s, &cc);
+  x = x + (cc * d0 + (-s) * d1);
+  y = y + (s * d0 + cc * d1);
+  th = wrap ? wrap_pi_d(th + d2) : th + d2;
+}
+
 // numerics.hpp:273-330
 template <bool MAP>
 __global__ __launch_bounds__(kBlock) void validate_control_kernel(const CollisionParams c, const HitMap m,
@@ -224,27 +259,11 @@ __global__ __launch_bounds__(kBlock) void validate_control_kernel(const Collisio
          th = x0[3 * static_cast<size_t>(q) + 2];
   const double u0 = u[3 * static_cast<size_t>(q)], u1 = u[3 * static_cast<size_t>(q) + 1],
                u2 = u[3 * static_cast<size_t>(q) + 2];
-  // body-frame displacement of one step is the same every step (constant twist)
   double d0, d1, d2;
-  if (fabs(u2 - 0.0) < 1.0e-12) {
-    d0 = u0 * dt;
-    d1 = u1 * dt;
-    d2 = 0.0;
-  } else {
-    const double vb0 = u0 * dt, vb1 = u1 * dt, vb2 = u2 * dt;
-    double s, cc;
-    tick_sincos(vb2, &s, &cc);
-    d0 = (vb0 * s + vb1 * (cc - 1.0)) / vb2;
-    d1 = (vb1 * s + vb0 * (1.0 - cc)) / vb2;
-    d2 = vb2;
-  }
+  body_displacement<true>(u0, u1, u2, dt, d0, d1, d2);
   int ok = 1;
   for (unsigned i = 0; i < steps; ++i) {
-    double s, cc;
-    tick_sincos(th, &s, &cc);
-    x = x + (cc * d0 + (-s) * d1);
-    y = y + (s * d0 + cc * d1);
-    th = wrap_pi_d(th + d2);
+    advance_pose<true>(x, y, th, d0, d1, d2, true);
     if (pose_collides<MAP>(c, grid, m, x, y)) {
       ok = 0;
       break;
@@ -252,6 +271,19 @@ __global__ __launch_bounds__(kBlock) void validate_control_kernel(const Collisio
   }
   valid[q] = ok;
 }
+// velocity sample sidx = (i, j, k) in the reference's loop order; values by repeated += like the reference
+__device__ __forceinline__ void sample_twist(const DwaParams& d, const double (&lower)[3], const double (&delta)[3], unsigned sidx,
+                                             double& u0, double& u1, double& u2)
+{
+  const unsigned k = sidx % d.ns[2], j = (sidx / d.ns[2]) % d.ns[1], i = sidx / (d.ns[2] * d.ns[1]);
+  u0 = lower[0];
+  u1 = lower[1];
+  u2 = lower[2];
+  for (unsigned q = 0; q < i; ++q) u0 += delta[0];
+  for (unsigned q = 0; q < j; ++q) u1 += delta[1];
+  for (unsigned q = 0; q < k; ++q) u2 += delta[2];
+}
+
 // DynamicWindow::control (dynamic_window.cpp:92-286): one workgroup per robot, one lane per
 // velocity sample; lane 0 then takes the first strict minimum in the reference's loop order.
 constexpr int kDwaBlock = 128;
@@ -311,36 +343,14 @@ __global__ __launch_bounds__(kDwaBlock) void dwa_control_kernel(const CollisionP
   const double* const xr = (xt_refs != nullptr) ? xt_refs + 3 * static_cast<size_t>(n_ref) * r : nullptr;
 
   for (unsigned sidx = threadIdx.x; sidx < nsamp; sidx += blockDim.x) {
-    // sample (i, j, k) in the reference's loop order; values by repeated += like the reference
-    const unsigned k = sidx % d.ns[2], j = (sidx / d.ns[2]) % d.ns[1], i = sidx / (d.ns[2] * d.ns[1]);
-    double u0 = lower[0], u1 = lower[1], u2 = lower[2];
-    for (unsigned q = 0; q < i; ++q) u0 += delta[0];
-    for (unsigned q = 0; q < j; ++q) u1 += delta[1];
-    for (unsigned q = 0; q < k; ++q) u2 += delta[2];
-
-    // constant-twist displacement in the body frame (numerics.hpp:273-297)
-    double d0, d1, d2;
-    if (fabs(u2 - 0.0) < 1.0e-12) {
-      d0 = u0 * d.dt;
-      d1 = u1 * d.dt;
-      d2 = 0.0;
-    } else {
-      const double vb0 = u0 * d.dt, vb1 = u1 * d.dt, vb2 = u2 * d.dt;
-      double sn, cs;
-      tick_sincos(vb2, &sn, &cs);
-      d0 = (vb0 * sn + vb1 * (cs - 1.0)) / vb2;
-      d1 = (vb1 * sn + vb0 * (1.0 - cs)) / vb2;
-      d2 = vb2;
-    }
+    double u0, u1, u2, d0, d1, d2;
+    sample_twist(d, lower, delta, sidx, u0, u1, u2);
+    body_displacement<true>(u0, u1, u2, d.dt, d0, d1, d2);
     double x = x0[0], y = x0[1], th = x0[2];
     double cost = 0.0, t = 0.0;
     bool hit = false;
     for (unsigned st = 0; st < d.steps; ++st) {
-      double sn, cs;
-      tick_sincos(th, &sn, &cs);
-      x = x + (cs * d0 + (-sn) * d1);
-      y = y + (sn * d0 + cs * d1);
-      th = wrap_pi_d(th + d2);
+      advance_pose<true>(x, y, th, d0, d1, d2, true);
       if (pose_collides<MAP>(c, grid, m, x, y)) {
         hit = true;
         break;
@@ -375,15 +385,7 @@ __global__ __launch_bounds__(kDwaBlock) void dwa_control_kernel(const CollisionP
     }
     const bool ok = !(fabs(best - kMax) < 1.0e-12);
     double o0 = 0.0, o1 = 0.0, o2 = 0.0;  // u_opt stays zero when nothing beat the initial maximum
-    if (best < kMax) {
-      const unsigned k = arg % d.ns[2], j = (arg / d.ns[2]) % d.ns[1], i = arg / (d.ns[2] * d.ns[1]);
-      o0 = lower[0];
-      o1 = lower[1];
-      o2 = lower[2];
-      for (unsigned q = 0; q < i; ++q) o0 += delta[0];
-      for (unsigned q = 0; q < j; ++q) o1 += delta[1];
-      for (unsigned q = 0; q < k; ++q) o2 += delta[2];
-    }
+    if (best < kMax) sample_twist(d, lower, delta, arg, o0, o1, o2);
     u_opt[3 * static_cast<size_t>(r) + 0] = o0;
     u_opt[3 * static_cast<size_t>(r) + 1] = o1;
     u_opt[3 * static_cast<size_t>(r) + 2] = o2;
@@ -421,43 +423,6 @@ __global__ __launch_bounds__(256) void tick_begin_kernel(int* __restrict__ follo
 
 namespace
 {
-// offsets (cell - centre) the ring search r_bnd..r_max can report a collision at: the walk of
-// collision.cpp:166-214, keeping the cells within r_col (collision.cpp:239)
-std::vector<short2> ring_offsets(const CollisionParams& c)
-{
-  std::vector<std::pair<int, int>> pts;
-  for (int r0 = c.r_bnd; r0 <= c.r_max; ++r0) {
-    int r = r0, x = -r0, y = 0, err = 2 - 2 * r0;
-    while (x < 0) {
-      pts.emplace_back(-x, y);
-      pts.emplace_back(-y, -x);
-      pts.emplace_back(x, -y);
-      pts.emplace_back(y, x);
-      r = err;
-      if (r <= y) {
-        y++;
-        err += 2 * y + 1;
-      }
-      if (r > x || err > y) {
-        x++;
-        err += 2 * x + 1;
-      }
-    }
-  }
-  std::sort(pts.begin(), pts.end());
-  pts.erase(std::unique(pts.begin(), pts.end()), pts.end());
-  std::vector<short2> out;
-  for (const auto& p : pts) {
-    if (p.first * p.first + p.second * p.second <= c.r_col * c.r_col) {
-      short2 o;
-      o.x = static_cast<short>(p.first);
-      o.y = static_cast<short>(p.second);
-      out.push_back(o);
-    }
-  }
-  return out;
-}
-
 // The offset list depends on three small integers only: built once per (device, radii) and kept for
 // the life of the process (a few KB), so that building a map needs no host synchronisation.
 struct OffsetEntry
@@ -468,11 +433,8 @@ struct OffsetEntry
 std::mutex g_offsets_mutex;
 std::vector<OffsetEntry> g_offsets;
 
-hipError_t device_offsets(const CollisionParams& c, const short2** d_out, int* n_out)
+hipError_t device_offsets(int device, const CollisionParams& c, const short2** d_out, int* n_out)
 {
-  int device = 0;
-  hipError_t e = hipGetDevice(&device);
-  if (e != hipSuccess) return e;
   std::lock_guard<std::mutex> lock(g_offsets_mutex);
   for (const OffsetEntry& o : g_offsets) {
     if (o.device == device && o.r_bnd == c.r_bnd && o.r_col == c.r_col && o.r_max == c.r_max) {
@@ -481,10 +443,10 @@ hipError_t device_offsets(const CollisionParams& c, const short2** d_out, int* n
       return hipSuccess;
     }
   }
-  const std::vector<short2> off = ring_offsets(c);
+  const std::vector<short2> off = ring_offsets(c.r_bnd, c.r_col, c.r_max);
   OffsetEntry ent{ device, c.r_bnd, c.r_col, c.r_max, static_cast<int>(off.size()), nullptr };
   if (!off.empty()) {
-    e = hipMalloc(reinterpret_cast<void**>(&ent.d_offsets), off.size() * sizeof(short2));
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&ent.d_offsets), off.size() * sizeof(short2));
     if (e != hipSuccess) return e;
     e = hipMemcpy(ent.d_offsets, off.data(), off.size() * sizeof(short2), hipMemcpyHostToDevice);
     if (e != hipSuccess) return e;
@@ -495,139 +457,55 @@ hipError_t device_offsets(const CollisionParams& c, const short2** d_out, int* n
   return hipSuccess;
 }
 
-// The map buffer of a (device, stream) pair is kept between calls: launches on one stream are
-// ordered, so a buffer is never written while an earlier call still reads it.  Every build marks
-// with a fresh stamp (1..255), which makes the marks of earlier builds stale without clearing the
-// buffer; it is cleared when the stamps wrap.  A build is then a single scatter kernel.
-struct MapBuffer
-{
-  int device;
-  hipStream_t stream;
-  uint8_t* cells;
-  size_t cap;
-  unsigned stamp;
-  // what the current stamp was built from (eea_tick_io::grid_epoch != 0: a later build of the same map is skipped)
-  const int8_t* built_grid = nullptr;
-  unsigned long long built_epoch = 0;
-  CollisionParams built_params{};
-};
+// the map buffers kept between calls: the policy is HitMapTable's (hit_map_table.hpp), the effects are build_hit_map's
 std::mutex g_maps_mutex;
-std::vector<MapBuffer> g_maps;
-constexpr size_t kMaxMapBuffers = 64;
-
-struct MapScratch
-{
-  void* async_cells = nullptr;  // stream-ordered allocation (only when the buffer table is full)
-  HitMap map{ nullptr, 0, 0, 0, 0 };
-};
-
-bool same_params(const CollisionParams& a, const CollisionParams& b)
-{
-  return a.xmin == b.xmin && a.ymin == b.ymin && a.resolution == b.resolution && a.xsize == b.xsize && a.ysize == b.ysize &&
-         a.r_bnd == b.r_bnd && a.r_col == b.r_col && a.r_max == b.r_max && a.occupied_threshold == b.occupied_threshold;
-}
+HitMapTable g_maps;
 
 // epoch != 0: the caller vouches that (d_grid, epoch) names one content -- the inflated map of the last build on this
-// stream is reused when it was built from the same (grid, epoch, parameters)
-hipError_t build_hit_map(const CollisionParams& c, const int8_t* d_grid, MapScratch& sc, hipStream_t s,
-                         unsigned long long epoch = 0)
+// stream is reused when it was built from the same (grid, epoch, parameters).  async_cells: a stream-ordered allocation (only
+// when the buffer table is full) that the caller frees behind the map's readers, whatever is returned
+hipError_t build_hit_map(const CollisionParams& c, const int8_t* d_grid, hipStream_t s, unsigned long long epoch, HitMap& map,
+                         void*& async_cells)
 {
   if (c.r_col < 0 || c.r_col > 8192 || c.r_max < c.r_bnd) return hipErrorInvalidValue;
+  int device = 0, n_off = 0;
   const short2* d_off = nullptr;
-  int n_off = 0;
-  hipError_t e = device_offsets(c, &d_off, &n_off);
+  hipError_t e = hipGetDevice(&device);
+  if (e == hipSuccess) e = device_offsets(device, c, &d_off, &n_off);
   if (e != hipSuccess) return e;
   const int R = c.r_col;
   const int w = static_cast<int>(c.xsize) + 2 * R, h = static_cast<int>(c.ysize) + 2 * R;
   const size_t bytes = static_cast<size_t>(w) * h;
-  int device = 0;
-  e = hipGetDevice(&device);
-  if (e != hipSuccess) return e;
 
-  uint8_t* cells = nullptr;
-  unsigned stamp = 1;
-  bool from_table = false;  // the map lives in a per-stream buffer of the table (its cache key is recorded after the launch)
-  {
-    std::lock_guard<std::mutex> lock(g_maps_mutex);
-    MapBuffer* buf = nullptr;
-    for (MapBuffer& b : g_maps) {
-      if (b.device == device && b.stream == s) buf = &b;
-    }
-    if (buf == nullptr && g_maps.size() < kMaxMapBuffers) {
-      g_maps.push_back(MapBuffer{ device, s, nullptr, 0, 0 });
-      buf = &g_maps.back();
-    }
-    if (buf != nullptr) {
-      if (buf->cap < bytes) {
-        if (buf->cells) (void)hipFree(buf->cells);  // waits for the kernels that still use it
-        buf->cells = nullptr;
-        buf->cap = 0;
-        e = hipMalloc(reinterpret_cast<void**>(&buf->cells), bytes);
-        if (e != hipSuccess) return e;
-        buf->cap = bytes;
-        buf->stamp = 0;
-        e = hipMemsetAsync(buf->cells, 0, bytes, s);
-        if (e != hipSuccess) return e;
-      }
-      if (epoch != 0 && buf->stamp != 0 && buf->built_grid == d_grid && buf->built_epoch == epoch &&
-          same_params(buf->built_params, c)) {
-        sc.map.cells = buf->cells;
-        sc.map.R = R;
-        sc.map.w = w;
-        sc.map.h = h;
-        sc.map.stamp = static_cast<uint8_t>(buf->stamp);
-        return hipSuccess;
-      }
-      if (++buf->stamp > 255u) {
-        e = hipMemsetAsync(buf->cells, 0, buf->cap, s);
-        if (e != hipSuccess) return e;
-        buf->stamp = 1;
-      }
-      // (the cache key is recorded only once the dilation launch below has succeeded -- ADVICE r05: after a failed launch the
-      // next tick with the same (grid, epoch) must not validate against a map that was never stamped)
-      buf->built_grid = nullptr;
-      buf->built_epoch = 0;
-      cells = buf->cells;
-      stamp = buf->stamp;
-      from_table = true;
-    }
-  }
-  if (cells == nullptr) {
-    e = hipMallocAsync(&sc.async_cells, bytes, s);
+  std::lock_guard<std::mutex> lock(g_maps_mutex);
+  const HitMapPlan p = g_maps.plan(device, s, bytes, d_grid, epoch, c);
+  void* cells = p.cells;
+  if (p.slot < 0) {
+    e = hipMallocAsync(&async_cells, bytes, s);
     if (e != hipSuccess) return e;
-    e = hipMemsetAsync(sc.async_cells, 0, bytes, s);
+    cells = async_cells;
+  } else if (p.reallocate) {
+    if (p.cells) (void)hipFree(p.cells);  // waits for the kernels that still use it
+    e = hipMalloc(&cells, bytes);
     if (e != hipSuccess) return e;
-    cells = static_cast<uint8_t*>(sc.async_cells);
+    g_maps.allocated(p.slot, cells, bytes);
   }
-  if (n_off > 0) {
-    const size_t n = static_cast<size_t>(c.xsize) * c.ysize;
-    hipLaunchKernelGGL(inflate_kernel, dim3(static_cast<unsigned>((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, c,
-                       d_grid, d_off, n_off, cells, R, w, static_cast<uint8_t>(stamp));
-    e = hipGetLastError();
+  if (p.clear) {
+    e = hipMemsetAsync(cells, 0, p.cap, s);
     if (e != hipSuccess) return e;
   }
-  if (from_table && epoch != 0) {  // valid for work ordered behind this launch (the caller's stream contract)
-    std::lock_guard<std::mutex> lock(g_maps_mutex);  // (the table may have grown: look the buffer up again)
-    for (MapBuffer& b : g_maps) {
-      if (b.device == device && b.stream == s && b.cells == cells) {
-        b.built_grid = d_grid;
-        b.built_epoch = epoch;
-        b.built_params = c;
-      }
+  if (!p.reuse) {
+    if (n_off > 0) {
+      const size_t n = static_cast<size_t>(c.xsize) * c.ysize;
+      hipLaunchKernelGGL(inflate_kernel, dim3(static_cast<unsigned>((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, c,
+                         d_grid, d_off, n_off, static_cast<uint8_t*>(cells), R, w, static_cast<uint8_t>(p.stamp));
+      e = hipGetLastError();
+      if (e != hipSuccess) return e;
     }
+    if (p.slot >= 0) g_maps.built(p, d_grid, epoch, c);
   }
-  sc.map.cells = cells;
-  sc.map.R = R;
-  sc.map.w = w;
-  sc.map.h = h;
-  sc.map.stamp = static_cast<uint8_t>(stamp);
+  map = HitMap{ static_cast<const uint8_t*>(cells), R, w, h, static_cast<uint8_t>(p.stamp) };
   return hipSuccess;
-}
-
-void release_hit_map(MapScratch& sc, hipStream_t s)
-{
-  if (sc.async_cells) (void)hipFreeAsync(sc.async_cells, s);
-  sc.async_cells = nullptr;
 }
 
 // Inflated map or ring search?  A ring search is a chain of ~200 dependent byte loads per pose
@@ -643,6 +521,41 @@ bool use_hit_map(size_t poses, unsigned sequential_steps, const CollisionParams&
   const double t_map_us = 25.0 + 2.0e-6 * cells, t_ring_us = 40.0 * (sequential_steps ? sequential_steps : 1u);
   return t_map_us < t_ring_us;
 }
+
+// One call's collision lookups: launch(map, std::true_type) behind a build of the inflated map when the cost model takes it
+// for `poses` lookups in chains of `sequential_steps`, launch(HitMap{}, std::false_type) -- the ring search -- otherwise.
+// `launch` enqueues the caller's kernels on s; the launch error is taken here, once, behind them.
+template <typename Launch>
+hipError_t with_map_or_ring(size_t poses, unsigned sequential_steps, const CollisionParams& c, const int8_t* d_grid,
+                            unsigned long long epoch, hipStream_t s, Launch launch)
+{
+  if (!use_hit_map(poses, sequential_steps, c)) {
+    launch(HitMap{}, std::false_type{});
+    return hipGetLastError();
+  }
+  HitMap map;
+  void* async_cells = nullptr;
+  hipError_t e = build_hit_map(c, d_grid, s, epoch, map, async_cells);
+  if (e == hipSuccess) {
+    launch(map, std::true_type{});
+    e = hipGetLastError();
+  }
+  if (async_cells) (void)hipFreeAsync(async_cells, s);
+  return e;
+}
+
+// launch geometry of dwa_control_kernel: one lane per velocity sample -- a single wavefront when the window has at most 64
+// samples -- and one cost per sample in LDS
+struct DwaGeometry
+{
+  size_t nsamp, lds;
+  unsigned block;
+  explicit DwaGeometry(const DwaParams& d)
+    : nsamp(static_cast<size_t>(d.ns[0]) * d.ns[1] * d.ns[2]), lds(sizeof(double) * nsamp), block(nsamp <= 64 ? 64 : kDwaBlock)
+  {
+  }
+  bool fits() const { return lds <= 64 * 1024; }  // a larger window is refused
+};
 }  // namespace
 
 void release_collision_caches()
@@ -651,10 +564,9 @@ void release_collision_caches()
   const bool have_device = hipGetDevice(&current) == hipSuccess;
   {
     std::lock_guard<std::mutex> lock(g_maps_mutex);
-    for (MapBuffer& b : g_maps) {
-      if (b.cells != nullptr && hipSetDevice(b.device) == hipSuccess) (void)hipFree(b.cells);  // waits for its users
-    }
-    g_maps.clear();
+    g_maps.release([](int device, void* cells) {
+      if (hipSetDevice(device) == hipSuccess) (void)hipFree(cells);  // waits for its users
+    });
   }
   {
     std::lock_guard<std::mutex> lock(g_offsets_mutex);
@@ -672,25 +584,12 @@ hipError_t launch_dwa_control(const CollisionParams& c, const DwaParams& d, cons
                               double* d_u_opt, int* d_found, hipStream_t s)
 {
   if (P == 0) return hipSuccess;
-  const size_t nsamp = static_cast<size_t>(d.ns[0]) * d.ns[1] * d.ns[2];
-  const size_t lds = sizeof(double) * nsamp;
-  if (lds > 64 * 1024) return hipErrorInvalidValue;
-  // one lane per velocity sample: a single wavefront when the window has at most 64 samples
-  const unsigned block = nsamp <= 64 ? 64 : kDwaBlock;
-  if (use_hit_map(static_cast<size_t>(P) * nsamp * d.steps, d.steps, c)) {
-    MapScratch sc;
-    hipError_t e = build_hit_map(c, d_grid, sc, s);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL((dwa_control_kernel<true, false>), dim3(P), dim3(block), lds, s, c, d, sc.map, d_grid, d_x0, d_vb,
-                         d_vref, d_xt_ref, n_ref, dt_ref, d_u_opt, d_found, FleetTick{});
-      e = hipGetLastError();
-    }
-    release_hit_map(sc, s);
-    return e;
-  }
-  hipLaunchKernelGGL((dwa_control_kernel<false, false>), dim3(P), dim3(block), lds, s, c, d, HitMap{ nullptr, 0, 0, 0, 0 },
-                     d_grid, d_x0, d_vb, d_vref, d_xt_ref, n_ref, dt_ref, d_u_opt, d_found, FleetTick{});
-  return hipGetLastError();
+  const DwaGeometry g(d);
+  if (!g.fits()) return hipErrorInvalidValue;
+  return with_map_or_ring(static_cast<size_t>(P) * g.nsamp * d.steps, d.steps, c, d_grid, 0, s, [&](const HitMap& m, auto map) {
+    hipLaunchKernelGGL((dwa_control_kernel<decltype(map)::value, false>), dim3(P), dim3(g.block), g.lds, s, c, d, m, d_grid, d_x0,
+                       d_vb, d_vref, d_xt_ref, n_ref, dt_ref, d_u_opt, d_found, FleetTick{});
+  });
 }
 
 hipError_t launch_tick_begin(int* d_follow, unsigned* d_count, int* d_skip, unsigned dwa_steps, unsigned P, hipStream_t s)
@@ -711,32 +610,17 @@ hipError_t launch_validate_and_dwa_fleet(const CollisionParams& c, const DwaPara
                                          hipStream_t s)
 {
   if (P == 0) return hipSuccess;
-  const size_t nsamp = static_cast<size_t>(d.ns[0]) * d.ns[1] * d.ns[2];
-  const size_t lds = sizeof(double) * nsamp;
-  if (lds > 64 * 1024) return hipErrorInvalidValue;
-  const unsigned block = nsamp <= 64 ? 64 : kDwaBlock;
+  const DwaGeometry g(d);
+  if (!g.fits()) return hipErrorInvalidValue;
   const FleetTick ft{ d_valid, d_follow, d_count, d_u, d_source };
-  const dim3 vgrid((P + kBlock - 1) / kBlock);
-  if (use_hit_map(static_cast<size_t>(P) * (val_steps + nsamp * d.steps), d.steps, c)) {
-    MapScratch sc;
-    hipError_t e = build_hit_map(c, d_grid, sc, s, grid_epoch);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(validate_control_kernel<true>, vgrid, dim3(kBlock), 0, s, c, sc.map, d_grid, d_x0, d_u, val_dt,
-                         val_steps, P, d_valid);
-      hipLaunchKernelGGL((dwa_control_kernel<true, true>), dim3(P), dim3(block), lds, s, c, d, sc.map, d_grid, d_x0, d_vb,
-                         static_cast<const double*>(nullptr), d_traj, n_ref, dt_ref, static_cast<double*>(nullptr),
-                         static_cast<int*>(nullptr), ft);
-      e = hipGetLastError();
-    }
-    release_hit_map(sc, s);
-    return e;
-  }
-  hipLaunchKernelGGL(validate_control_kernel<false>, vgrid, dim3(kBlock), 0, s, c, HitMap{ nullptr, 0, 0, 0, 0 }, d_grid, d_x0,
-                     d_u, val_dt, val_steps, P, d_valid);
-  hipLaunchKernelGGL((dwa_control_kernel<false, true>), dim3(P), dim3(block), lds, s, c, d, HitMap{ nullptr, 0, 0, 0, 0 },
-                     d_grid, d_x0, d_vb, static_cast<const double*>(nullptr), d_traj, n_ref, dt_ref,
-                     static_cast<double*>(nullptr), static_cast<int*>(nullptr), ft);
-  return hipGetLastError();
+  return with_map_or_ring(static_cast<size_t>(P) * (val_steps + g.nsamp * d.steps), d.steps, c, d_grid, grid_epoch, s,
+                          [&](const HitMap& m, auto map) {
+    hipLaunchKernelGGL(validate_control_kernel<decltype(map)::value>, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, s, c, m,
+                       d_grid, d_x0, d_u, val_dt, val_steps, P, d_valid);
+    hipLaunchKernelGGL((dwa_control_kernel<decltype(map)::value, true>), dim3(P), dim3(g.block), g.lds, s, c, d, m, d_grid, d_x0,
+                       d_vb, static_cast<const double*>(nullptr), d_traj, n_ref, dt_ref, static_cast<double*>(nullptr),
+                       static_cast<int*>(nullptr), ft);
+  });
 }
 
 hipError_t launch_collision_check(const CollisionParams& c, const int8_t* d_grid,
@@ -744,18 +628,13 @@ hipError_t launch_collision_check(const CollisionParams& c, const int8_t* d_grid
 {
   if (P == 0) return hipSuccess;
   const dim3 grid((P + kBlock - 1) / kBlock);
-  if (use_hit_map(P, 1, c)) {
-    MapScratch sc;
-    hipError_t e = build_hit_map(c, d_grid, sc, s);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(collision_check_map_kernel, grid, dim3(kBlock), 0, s, c, sc.map, d_pose, P, d_hit);
-      e = hipGetLastError();
+  return with_map_or_ring(P, 1, c, d_grid, 0, s, [&](const HitMap& m, auto map) {
+    if constexpr (decltype(map)::value) {
+      hipLaunchKernelGGL(collision_check_map_kernel, grid, dim3(kBlock), 0, s, c, m, d_pose, P, d_hit);
+    } else {
+      hipLaunchKernelGGL(collision_check_kernel, grid, dim3(kBlock), 0, s, c, d_grid, d_pose, P, d_hit);
     }
-    release_hit_map(sc, s);
-    return e;
-  }
-  hipLaunchKernelGGL(collision_check_kernel, grid, dim3(kBlock), 0, s, c, d_grid, d_pose, P, d_hit);
-  return hipGetLastError();
+  });
 }
 
 // integrate_twist (numerics.hpp:273-297) for P poses: x + Rot(theta) dq_b, the heading NOT wrapped (the reference's callers
@@ -766,26 +645,15 @@ __global__ __launch_bounds__(kBlock) void integrate_twist_kernel(const double* _
 {
   const unsigned q = blockIdx.x * kBlock + threadIdx.x;
   if (q >= P) return;
-  const double x = x0[3 * static_cast<size_t>(q)], y = x0[3 * static_cast<size_t>(q) + 1], th = x0[3 * static_cast<size_t>(q) + 2];
+  double x = x0[3 * static_cast<size_t>(q)], y = x0[3 * static_cast<size_t>(q) + 1], th = x0[3 * static_cast<size_t>(q) + 2];
   const double u0 = u[3 * static_cast<size_t>(q)], u1 = u[3 * static_cast<size_t>(q) + 1], u2 = u[3 * static_cast<size_t>(q) + 2];
+  // <false>: the device library's sincos -- one call per robot and tick, kept closest to libm
   double d0, d1, d2;
-  if (fabs(u2 - 0.0) < 1.0e-12) {
-    d0 = u0 * dt;
-    d1 = u1 * dt;
-    d2 = 0.0;
-  } else {
-    const double vb0 = u0 * dt, vb1 = u1 * dt, vb2 = u2 * dt;
-    double s, cc;
-    sincos(vb2, &s, &cc);  // (the device library's: one call per robot and tick, kept closest to libm)
-    d0 = (vb0 * s + vb1 * (cc - 1.0)) / vb2;
-    d1 = (vb1 * s + vb0 * (1.0 - cc)) / vb2;
-    d2 = vb2;
-  }
-  double s, cc;
-  sincos(th, &s, &cc);
-  out[3 * static_cast<size_t>(q)] = x + (cc * d0 + (-s) * d1);
-  out[3 * static_cast<size_t>(q) + 1] = y + (s * d0 + cc * d1);
-  out[3 * static_cast<size_t>(q) + 2] = wrap ? wrap_pi_d(th + d2) : th + d2;
+  body_displacement<false>(u0, u1, u2, dt, d0, d1, d2);
+  advance_pose<false>(x, y, th, d0, d1, d2, wrap != 0);
+  out[3 * static_cast<size_t>(q)] = x;
+  out[3 * static_cast<size_t>(q) + 1] = y;
+  out[3 * static_cast<size_t>(q) + 2] = th;
 }
 
 hipError_t launch_integrate_twist(const double* d_x0, const double* d_u, double dt, unsigned P, double* d_out, bool wrap, hipStream_t s)
@@ -800,20 +668,9 @@ hipError_t launch_validate_control(const CollisionParams& c, const int8_t* d_gri
                                    unsigned P, int* d_valid, hipStream_t s)
 {
   if (P == 0) return hipSuccess;
-  const dim3 grid((P + kBlock - 1) / kBlock);
-  if (use_hit_map(static_cast<size_t>(P) * steps, steps, c)) {
-    MapScratch sc;
-    hipError_t e = build_hit_map(c, d_grid, sc, s);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(validate_control_kernel<true>, grid, dim3(kBlock), 0, s, c, sc.map, d_grid, d_x0, d_u, dt,
-                         steps, P, d_valid);
-      e = hipGetLastError();
-    }
-    release_hit_map(sc, s);
-    return e;
-  }
-  hipLaunchKernelGGL(validate_control_kernel<false>, grid, dim3(kBlock), 0, s, c, HitMap{ nullptr, 0, 0, 0, 0 }, d_grid,
-                     d_x0, d_u, dt, steps, P, d_valid);
-  return hipGetLastError();
+  return with_map_or_ring(static_cast<size_t>(P) * steps, steps, c, d_grid, 0, s, [&](const HitMap& m, auto map) {
+    hipLaunchKernelGGL(validate_control_kernel<decltype(map)::value>, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, s, c, m,
+                       d_grid, d_x0, d_u, dt, steps, P, d_valid);
+  });
 }
 }  // namespace eea

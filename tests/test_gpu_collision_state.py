@@ -1,8 +1,10 @@
-"""The state the inflated collision map keeps BETWEEN calls (csrc/collision_kernel.hip build_hit_map): one buffer per
+"""The state the inflated collision map keeps BETWEEN calls (the policy: csrc/hit_map_table.hpp HitMapTable; its effects:
+csrc/collision_kernel.hip build_hit_map): one buffer per
 (device, stream); a stamp 1..255 per build, the buffer cleared when the stamps wrap; the buffer reallocated for a larger map
 and reused as it is for a smaller one with another row pitch; the ring-offset table cached by radii; stream-ordered
 allocations once 64 streams hold a buffer; a tick's grid_epoch cache, which any other build on the stream must drop.
-A mistake in any of these shows as obstacles of an EARLIER map, hundreds of calls later.
+A mistake in any of these shows as obstacles of an EARLIER map, hundreds of calls later (tests/test_hit_map_table.py asks
+the table itself, without a GPU).
 
 Every call has >= 4096 poses, so the cost model picks the inflated map by itself (the file is skipped when an implementation
 is forced).  References: the CPU oracle, once per (grid, radii).  Results are compared on the device, on the call's own

@@ -442,6 +442,14 @@ comm = capi.Comm(0, 1, 0, None)
 streams = [torch.cuda.Stream() for _ in range(G)]
 gb = [0, B // 2, B]
 torch.cuda.synchronize()
+# (a runtime library that widened the mask while it loaded, and the threads it started since, go back to the one CPU:
+# the loop itself then runs pinned on such a host too)
+one_cpu = {sorted(os.sched_getaffinity(0))[0]}
+for tid in os.listdir("/proc/self/task"):
+    try:
+        os.sched_setaffinity(int(tid), one_cpu)
+    except ProcessLookupError:
+        pass
 t0 = time.perf_counter()
 for i in range(passes):
     seq, slot = i + 1, i %% NB
