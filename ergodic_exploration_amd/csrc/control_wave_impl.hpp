@@ -925,7 +925,7 @@ __global__ __launch_bounds__(WPB* kWave, waves_per_simd(KC, sizeof(R))) void con
       }
     }
     // the matrix instructions of one 16-row group with the staging of `dst` (kPairs stores) spread between them
-    auto mma4_group_staging = [&](int q, Tab1& u, R* dst) {
+    auto mma4_group_staging = [&](int q, Tab1& u, R* dst, bool store = true) {
       constexpr int kEvery = (NB * NB + kPairs - 1) / kPairs;  // a store after every kEvery-th instruction
       int done = 0;
 #pragma unroll
@@ -935,7 +935,7 @@ __global__ __launch_bounds__(WPB* kWave, waves_per_simd(KC, sizeof(R))) void con
           cacc[I][J] = mfma4(qa[q][I], qb[q][J], cacc[I][J]);
           const int n = I * NB + J + 1;
           if (n % kEvery == 0 && done < kPairs) {
-            tab1_store(u, dst, 2 * done);
+            if (store) tab1_store(u, dst, 2 * done);  // wavefront-uniform
             tab1_step(u);
             ++done;
           }
@@ -945,7 +945,7 @@ __global__ __launch_bounds__(WPB* kWave, waves_per_simd(KC, sizeof(R))) void con
 #pragma unroll
       for (int q2 = 0; q2 < kPairs; ++q2) {  // (none left when kPairs * kEvery <= NB * NB)
         if (q2 >= done) {
-          tab1_store(u, dst, 2 * q2);
+          if (store) tab1_store(u, dst, 2 * q2);
           tab1_step(u);
         }
       }
@@ -960,9 +960,13 @@ __global__ __launch_bounds__(WPB* kWave, waves_per_simd(KC, sizeof(R))) void con
         {
           Tab1 u = tab1_init(cu, j < cnt_of(row + 32));
           operands4_ready();
-          mma4_group_staging(0, u, st_upper);
+          mma4_group_staging(0, u, st_upper, nl > 32);  // (no point in lanes 32..63: no upper half-pass, below, and no tile for it)
           if (nl > 16) mma4_group(1);
         }
+        // A last slot with no point in lanes 32..63 (wavefront-uniform: slot 3 of T = 193 .. 200) has no upper half-pass:
+        // its tile is all-zero rows that no matrix instruction multiplies, and the tile it would stage is that of a slot
+        // that does not exist -- no operand reads, no exchange, no stores, no fences
+        if (nl > 32 || j + 1 < S) {
         lds_fence();
         read_operands4();  // rows of lanes 32..63, step j
         lds_fence();
@@ -981,6 +985,7 @@ __global__ __launch_bounds__(WPB* kWave, waves_per_simd(KC, sizeof(R))) void con
               tab1_step(u);
             }
           }
+        }
         }
       }
     }
