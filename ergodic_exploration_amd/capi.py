@@ -225,6 +225,16 @@ def lib():
         L.eea_sense_gain_field.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
         L.eea_set_target_gain.argtypes = [C.c_void_p, C.POINTER(CollisionCfg), C.c_uint, C.c_uint, C.c_void_p, C.c_double,
                                           C.c_double, C.c_double, C.c_void_p, C.c_void_p]
+        if hasattr(L, "eea_fleet_layer_create"):   # additive to ABI 6: found by symbol (an older library has none of them)
+            L.eea_fleet_layer_create.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_int, C.c_uint, C.POINTER(C.c_void_p)]
+            L.eea_fleet_layer_destroy.argtypes = [C.c_void_p]
+            L.eea_fleet_layer_destroy.restype = None
+            L.eea_fleet_layer_update.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.eea_fleet_layer_reach.argtypes = [C.c_void_p]
+            L.eea_fleet_layer_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+            L.eea_fleet_collision_check_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p]
+            L.eea_tick_batch_fleet.argtypes = [C.c_void_p, C.c_uint, C.POINTER(BatchIO), C.POINTER(TickIO), C.POINTER(CollisionCfg),
+                                               C.POINTER(DwaCfg), C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -463,10 +473,9 @@ class Engine:
         io.d_pose, io.d_ut, io.d_u0, io.d_ck = _ptr(pose), _ptr(ut), _ptr(u0), _ptr(ck)
         check(lib().eea_debug_phase_timing(self.h, B, C.byref(io), C.c_void_p(stream or 0), _ptr(stamps)))
 
-    def tick_batch(self, B, pose, ut, follow, count, u, vb, grid, traj, valid, skip, coll, dwa, val_dt, val_horizon,
-                   source=None, mem_cols=None, n_mem=None, mem_stride=0, status=None, stream=None, grid_epoch=0):
-        """eea_tick_batch: one iteration of Exploration::control's loop body (exploration.hpp:220-279) for B robots.
-        coll / dwa: collision_cfg(...) / dwa_cfg(...)"""
+    @staticmethod
+    def _tick_io(pose, ut, follow, count, u, vb, grid, traj, valid, skip, val_dt, val_horizon, source, mem_cols, n_mem,
+                 mem_stride, status, grid_epoch):
         io = BatchIO()
         io.d_pose, io.d_ut = _ptr(pose), _ptr(ut)
         io.d_mem_cols, io.d_n_mem, io.mem_stride, io.d_status = _ptr(mem_cols), _ptr(n_mem), mem_stride, _ptr(status)
@@ -474,7 +483,24 @@ class Engine:
         t.d_follow_dwa, t.d_dwa_count, t.d_u, t.d_vb, t.d_grid = _ptr(follow), _ptr(count), _ptr(u), _ptr(vb), _ptr(grid)
         t.d_traj, t.d_valid, t.d_skip, t.d_source = _ptr(traj), _ptr(valid), _ptr(skip), _ptr(source)
         t.val_dt, t.val_horizon, t.grid_epoch = val_dt, val_horizon, grid_epoch
+        return io, t
+
+    def tick_batch(self, B, pose, ut, follow, count, u, vb, grid, traj, valid, skip, coll, dwa, val_dt, val_horizon,
+                   source=None, mem_cols=None, n_mem=None, mem_stride=0, status=None, stream=None, grid_epoch=0):
+        """eea_tick_batch: one iteration of Exploration::control's loop body (exploration.hpp:220-279) for B robots.
+        coll / dwa: collision_cfg(...) / dwa_cfg(...)"""
+        io, t = self._tick_io(pose, ut, follow, count, u, vb, grid, traj, valid, skip, val_dt, val_horizon, source, mem_cols,
+                              n_mem, mem_stride, status, grid_epoch)
         check(lib().eea_tick_batch(self.h, B, C.byref(io), C.byref(t), C.byref(coll), C.byref(dwa), C.c_void_p(stream or 0)))
+
+    def tick_batch_fleet(self, layer, B, pose, ut, follow, count, u, vb, grid, traj, valid, skip, coll, dwa, val_dt, val_horizon,
+                         source=None, mem_cols=None, n_mem=None, mem_stride=0, status=None, stream=None, grid_epoch=0):
+        """eea_tick_batch_fleet: tick_batch with the FleetLayer `layer` in validate_control and the dynamic window -- the other
+        robots' bodies are obstacles; robot r of the tick is robot r of the layer (updated on the same stream before)"""
+        io, t = self._tick_io(pose, ut, follow, count, u, vb, grid, traj, valid, skip, val_dt, val_horizon, source, mem_cols,
+                              n_mem, mem_stride, status, grid_epoch)
+        check(lib().eea_tick_batch_fleet(self.h, B, C.byref(io), C.byref(t), C.byref(coll), C.byref(dwa),
+                                         layer.h if layer is not None else None, C.c_void_p(stream or 0)))
 
     def rollout_batch(self, B, pose, ut, traj, status=None, stream=None):
         check(lib().eea_rollout_batch(self.h, B, _ptr(pose), _ptr(ut), _ptr(traj), _ptr(status),
@@ -648,6 +674,48 @@ def prepared_stream_wait_flag(flag, timeouts=None, stream=None):
 
 def get_option(option):
     return lib().eea_get_option(option)
+
+
+class FleetLayer:
+    """eea_fleet_layer: the B robots of a fleet as obstacles to one another (include/ergodic_amd.h states the rule).  cfg: the
+    make_collision_cfg(...) of the ticks that use it; body_cells: the body radius in cells (the natural value is the boundary
+    radius in cells).  update() builds the layer from the poses on the stream; Engine.tick_batch_fleet / collision_check read it."""
+    NOT_STAMPED = -2 ** 31
+
+    def __init__(self, cfg, body_cells, B, device=0):
+        self.h = C.c_void_p()
+        check(lib().eea_fleet_layer_create(device, C.byref(cfg) if cfg is not None else None, int(body_cells), int(B), C.byref(self.h)))
+        self.cfg, self.body_cells, self.B = cfg, int(body_cells), int(B)
+        self.reach = int(lib().eea_fleet_layer_reach(self.h))
+        self.shape = (cfg.ysize + 2 * self.reach, cfg.xsize + 2 * self.reach)   # of the counts: centres [-R', size + R')
+
+    def update(self, pose, mask=None, stream=None):
+        """pose [B][3] float64, mask [B] int32 or None: device tensors; asynchronous"""
+        check(lib().eea_fleet_layer_update(self.h, _ptr(pose), _ptr(mask), C.c_void_p(stream or 0)))
+
+    def read(self):
+        """(counts [ysize + 2R'][xsize + 2R'], cells [B][2] as (x, y)) as numpy int32 arrays; synchronises"""
+        import numpy as np
+        count, cell = np.empty(self.shape, dtype=np.int32), np.empty((self.B, 2), dtype=np.int32)
+        check(lib().eea_fleet_layer_read(self.h, _ptr(count), _ptr(cell)))
+        return count, cell
+
+    def collision_check(self, grid, pose, hit, self_index=None, stream=None):
+        """eea_fleet_collision_check_batch: hit [P] int32 = collisionCheck of pose [P][3] on grid (None: robots only) OR a
+        collision with a robot other than self_index [P] int32 (-1 / None: nobody's pose)"""
+        check(lib().eea_fleet_collision_check_batch(self.h, _ptr(grid), _ptr(pose), _ptr(self_index), int(pose.shape[0]),
+                                                    _ptr(hit), C.c_void_p(stream or 0)))
+
+    def close(self):
+        if self.h:
+            lib().eea_fleet_layer_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class ReplayMemory:

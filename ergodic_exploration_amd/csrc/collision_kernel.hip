@@ -20,6 +20,7 @@
 #include "common.hpp"
 #include "grid_cell.hpp"      // cast_u32_x86, world_to_grid (grid.cpp:143-159): shared with sense_kernel.hip
 #include "hit_map_table.hpp"  // ring_offsets, HitMapTable: the host-side policy of the inflated map
+#include "fleet_spans.hpp"    // FleetSpan: the row spans of the fleet layer's offset set
 
 namespace eea
 {
@@ -111,6 +112,48 @@ __device__ __forceinline__ bool hit_lookup(const HitMap& m, int cx, int cy)
   if (hx < 0 || hy < 0 || hx >= m.w || hy >= m.h) return false;
   return m.cells[static_cast<size_t>(hy) * m.w + hx] == m.stamp;
 }
+
+// ---- fleet layer (fleet_layer_kernel.hip): the other robots' bodies ------------------------------------
+// The robot a pose belongs to: its cell at the layer's last update, x = kFleetNotStamped when it is no obstacle (or the pose is
+// nobody's)
+struct FleetSelf
+{
+  int x = kFleetNotStamped, y = kFleetNotStamped;
+};
+__device__ __forceinline__ FleetSelf fleet_self(const FleetView& f, int robot)
+{
+  FleetSelf own;
+  if (static_cast<unsigned>(robot) < f.B) {  // (-1: none)
+    own.x = f.cell[2 * static_cast<size_t>(robot)];
+    own.y = f.cell[2 * static_cast<size_t>(robot) + 1];
+  }
+  return own;
+}
+
+// "the pose centred at (cx, cy) collides with a robot other than its own": count[c] robots reach c through F; the pose's own
+// robot is one of them iff it was stamped and (c - own) in F (one or two spans per row: fleet_spans.hpp)
+__device__ __forceinline__ bool fleet_lookup(const FleetView& f, const FleetSelf& own, int cx, int cy)
+{
+  const int hx = cx + f.R, hy = cy + f.R;
+  if (hx < 0 || hy < 0 || hx >= f.w || hy >= f.h) return false;  // centres outside the map see nothing: F lies within R
+  int n = f.count[static_cast<size_t>(hy) * f.w + hx];
+  if (n > 0 && own.x != kFleetNotStamped) {
+    // (cx, cy is inside the map and own inside the grid: the differences cannot overflow)
+    const int dx = cx - own.x, dy = cy - own.y;
+    if (dy >= -f.R && dy <= f.R) {
+      for (int k = f.row_start[dy + f.R]; k < f.row_start[dy + f.R + 1]; ++k) {
+        if (f.spans[k].x0 <= dx && dx <= f.spans[k].x1) {
+          n -= 1;
+          break;
+        }
+      }
+    }
+  }
+  return n > 0;
+}
+struct NoFleetLayer
+{
+};
 
 // occupied cells mark every centre that reaches them through one of the ring offsets
 __global__ __launch_bounds__(kBlock) void inflate_kernel(const CollisionParams c, const int8_t* __restrict__ grid,
@@ -209,6 +252,26 @@ __device__ __forceinline__ bool pose_collides(const CollisionParams& c, const in
   return collision_check(c, grid, px, py);
 }
 
+// ... OR a collision with another robot's body when Layer is the FleetView of a fleet layer (NoFleetLayer: the static
+// verdict alone, the code of the instances without a layer)
+template <bool LAYER>
+using LayerArg = std::conditional_t<LAYER, FleetView, NoFleetLayer>;  // (the last kernel argument; empty without a layer)
+template <typename Layer>
+constexpr bool kWithLayer = std::is_same<Layer, FleetView>::value;
+template <bool MAP, typename Layer>
+__device__ __forceinline__ bool pose_collides(const CollisionParams& c, const int8_t* __restrict__ grid, const HitMap& m,
+                                              const Layer& layer, const FleetSelf& own, double px, double py)
+{
+  if constexpr (kWithLayer<Layer>) {
+    int cx, cy;
+    centre_of(c, px, py, cx, cy);
+    const bool hit = MAP ? hit_lookup(m, cx, cy) : collision_check(c, grid, px, py);
+    return hit || fleet_lookup(layer, own, cx, cy);
+  } else {
+    return pose_collides<MAP>(c, grid, m, px, py);
+  }
+}
+
 // The steps of a constant-twist rollout, written ONCE: this translation unit is compiled without FMA contraction and the sums
 // keep the reference's order and parentheses, so every caller gets the same bits.  FAST: sin / cos by tick_sincos (the
 // rollouts), otherwise by the device library (integrate_twist_kernel).
@@ -244,14 +307,14 @@ __device__ __forceinline__ void advance_pose(double& x, double& y, double& th, d
   th = wrap ? wrap_pi_d(th + d2) : th + d2;
 }
 
-// numerics.hpp:273-330
-template <bool MAP>
+// numerics.hpp:273-330; LAYER: with a fleet layer, pose q is robot q's
+template <bool MAP, bool LAYER = false>
 __global__ __launch_bounds__(kBlock) void validate_control_kernel(const CollisionParams c, const HitMap m,
                                                                   const int8_t* __restrict__ grid,
                                                                   const double* __restrict__ x0,
                                                                   const double* __restrict__ u,
                                                                   double dt, unsigned steps, unsigned P,
-                                                                  int* __restrict__ valid)
+                                                                  int* __restrict__ valid, const LayerArg<LAYER> layer)
 {
   const unsigned q = blockIdx.x * kBlock + threadIdx.x;
   if (q >= P) return;
@@ -259,17 +322,42 @@ __global__ __launch_bounds__(kBlock) void validate_control_kernel(const Collisio
          th = x0[3 * static_cast<size_t>(q) + 2];
   const double u0 = u[3 * static_cast<size_t>(q)], u1 = u[3 * static_cast<size_t>(q) + 1],
                u2 = u[3 * static_cast<size_t>(q) + 2];
+  FleetSelf own;
+  if constexpr (LAYER) own = fleet_self(layer, static_cast<int>(q));
   double d0, d1, d2;
   body_displacement<true>(u0, u1, u2, dt, d0, d1, d2);
   int ok = 1;
   for (unsigned i = 0; i < steps; ++i) {
     advance_pose<true>(x, y, th, d0, d1, d2, true);
-    if (pose_collides<MAP>(c, grid, m, x, y)) {
+    if (pose_collides<MAP>(c, grid, m, layer, own, x, y)) {
       ok = 0;
       break;
     }
   }
   valid[q] = ok;
+}
+
+// collisionCheck of P poses with a fleet layer: the static verdict (grid == null: none) OR another robot's body
+template <bool MAP>
+__global__ __launch_bounds__(kBlock) void fleet_collision_check_kernel(const CollisionParams c, const HitMap m, const FleetView f,
+                                                                       const int8_t* __restrict__ grid,
+                                                                       const double* __restrict__ pose,
+                                                                       const int* __restrict__ self, unsigned P,
+                                                                       int* __restrict__ hit)
+{
+  const unsigned q = blockIdx.x * kBlock + threadIdx.x;
+  if (q >= P) return;
+  const double px = pose[3 * static_cast<size_t>(q)], py = pose[3 * static_cast<size_t>(q) + 1];
+  const FleetSelf own = fleet_self(f, self != nullptr ? self[q] : -1);
+  bool h;
+  if (grid != nullptr) {
+    h = pose_collides<MAP>(c, grid, m, f, own, px, py);
+  } else {
+    int cx, cy;
+    centre_of(c, px, py, cx, cy);
+    h = fleet_lookup(f, own, cx, cy);
+  }
+  hit[q] = h ? 1 : 0;
 }
 // velocity sample sidx = (i, j, k) in the reference's loop order; values by repeated += like the reference
 __device__ __forceinline__ void sample_twist(const DwaParams& d, const double (&lower)[3], const double (&delta)[3], unsigned sidx,
@@ -298,7 +386,8 @@ struct FleetTick
   double* u;
   int* source;
 };
-template <bool MAP, bool FLEET>
+// LAYER: with a fleet layer; robot r of the launch is robot r of the layer
+template <bool MAP, bool FLEET, bool LAYER = false>
 __global__ __launch_bounds__(kDwaBlock) void dwa_control_kernel(const CollisionParams c, const DwaParams d,
                                                                const HitMap m,
                                                                const int8_t* __restrict__ grid,
@@ -308,11 +397,14 @@ __global__ __launch_bounds__(kDwaBlock) void dwa_control_kernel(const CollisionP
                                                                const double* __restrict__ xt_refs,
                                                                unsigned n_ref, double dt_ref,
                                                                double* __restrict__ u_opt,
-                                                               int* __restrict__ found, const FleetTick ft)
+                                                               int* __restrict__ found, const FleetTick ft,
+                                                               const LayerArg<LAYER> layer)
 {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   double* const s_cost = reinterpret_cast<double*>(smem_raw);
   const unsigned r = blockIdx.x;
+  FleetSelf own;
+  if constexpr (LAYER) own = fleet_self(layer, static_cast<int>(r));
   bool following = false;
   if (FLEET) {
     following = ft.follow[r] != 0;  // (after step 1 of the tick)
@@ -351,7 +443,7 @@ __global__ __launch_bounds__(kDwaBlock) void dwa_control_kernel(const CollisionP
     bool hit = false;
     for (unsigned st = 0; st < d.steps; ++st) {
       advance_pose<true>(x, y, th, d0, d1, d2, true);
-      if (pose_collides<MAP>(c, grid, m, x, y)) {
+      if (pose_collides<MAP>(c, grid, m, layer, own, x, y)) {
         hit = true;
         break;
       }
@@ -588,7 +680,7 @@ hipError_t launch_dwa_control(const CollisionParams& c, const DwaParams& d, cons
   if (!g.fits()) return hipErrorInvalidValue;
   return with_map_or_ring(static_cast<size_t>(P) * g.nsamp * d.steps, d.steps, c, d_grid, 0, s, [&](const HitMap& m, auto map) {
     hipLaunchKernelGGL((dwa_control_kernel<decltype(map)::value, false>), dim3(P), dim3(g.block), g.lds, s, c, d, m, d_grid, d_x0,
-                       d_vb, d_vref, d_xt_ref, n_ref, dt_ref, d_u_opt, d_found, FleetTick{});
+                       d_vb, d_vref, d_xt_ref, n_ref, dt_ref, d_u_opt, d_found, FleetTick{}, NoFleetLayer{});
   });
 }
 
@@ -616,10 +708,47 @@ hipError_t launch_validate_and_dwa_fleet(const CollisionParams& c, const DwaPara
   return with_map_or_ring(static_cast<size_t>(P) * (val_steps + g.nsamp * d.steps), d.steps, c, d_grid, grid_epoch, s,
                           [&](const HitMap& m, auto map) {
     hipLaunchKernelGGL(validate_control_kernel<decltype(map)::value>, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, s, c, m,
-                       d_grid, d_x0, d_u, val_dt, val_steps, P, d_valid);
+                       d_grid, d_x0, d_u, val_dt, val_steps, P, d_valid, NoFleetLayer{});
     hipLaunchKernelGGL((dwa_control_kernel<decltype(map)::value, true>), dim3(P), dim3(g.block), g.lds, s, c, d, m, d_grid, d_x0,
                        d_vb, static_cast<const double*>(nullptr), d_traj, n_ref, dt_ref, static_cast<double*>(nullptr),
-                       static_cast<int*>(nullptr), ft);
+                       static_cast<int*>(nullptr), ft, NoFleetLayer{});
+  });
+}
+
+// ... with a fleet layer in every collision test of both launches (eea_tick_batch_fleet)
+hipError_t launch_validate_and_dwa_fleet_layer(const CollisionParams& c, const DwaParams& d, const FleetView& v, const int8_t* d_grid,
+                                               unsigned long long grid_epoch, const double* d_x0, const double* d_vb,
+                                               const double* d_traj, unsigned n_ref, double dt_ref, double val_dt,
+                                               unsigned val_steps, int* d_valid, int* d_follow, unsigned* d_count, double* d_u,
+                                               int* d_source, unsigned P, hipStream_t s)
+{
+  if (P == 0) return hipSuccess;
+  const DwaGeometry g(d);
+  if (!g.fits()) return hipErrorInvalidValue;
+  const FleetTick ft{ d_valid, d_follow, d_count, d_u, d_source };
+  return with_map_or_ring(static_cast<size_t>(P) * (val_steps + g.nsamp * d.steps), d.steps, c, d_grid, grid_epoch, s,
+                          [&](const HitMap& m, auto map) {
+    hipLaunchKernelGGL((validate_control_kernel<decltype(map)::value, true>), dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, s,
+                       c, m, d_grid, d_x0, d_u, val_dt, val_steps, P, d_valid, v);
+    hipLaunchKernelGGL((dwa_control_kernel<decltype(map)::value, true, true>), dim3(P), dim3(g.block), g.lds, s, c, d, m, d_grid,
+                       d_x0, d_vb, static_cast<const double*>(nullptr), d_traj, n_ref, dt_ref, static_cast<double*>(nullptr),
+                       static_cast<int*>(nullptr), ft, v);
+  });
+}
+
+hipError_t launch_fleet_collision_check(const CollisionParams& c, const FleetView& v, const int8_t* d_grid, const double* d_pose,
+                                        const int* d_self, unsigned P, int* d_hit, hipStream_t s)
+{
+  if (P == 0) return hipSuccess;
+  const dim3 grid((P + kBlock - 1) / kBlock);
+  if (d_grid == nullptr) {  // robots only: no static part, no inflated map
+    hipLaunchKernelGGL(fleet_collision_check_kernel<false>, grid, dim3(kBlock), 0, s, c, HitMap{}, v, d_grid, d_pose, d_self, P,
+                       d_hit);
+    return hipGetLastError();
+  }
+  return with_map_or_ring(P, 1, c, d_grid, 0, s, [&](const HitMap& m, auto map) {
+    hipLaunchKernelGGL(fleet_collision_check_kernel<decltype(map)::value>, grid, dim3(kBlock), 0, s, c, m, v, d_grid, d_pose, d_self,
+                       P, d_hit);
   });
 }
 
@@ -670,7 +799,7 @@ hipError_t launch_validate_control(const CollisionParams& c, const int8_t* d_gri
   if (P == 0) return hipSuccess;
   return with_map_or_ring(static_cast<size_t>(P) * steps, steps, c, d_grid, 0, s, [&](const HitMap& m, auto map) {
     hipLaunchKernelGGL(validate_control_kernel<decltype(map)::value>, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, s, c, m,
-                       d_grid, d_x0, d_u, dt, steps, P, d_valid);
+                       d_grid, d_x0, d_u, dt, steps, P, d_valid, NoFleetLayer{});
   });
 }
 }  // namespace eea

@@ -314,6 +314,42 @@ hipError_t launch_validate_and_dwa_fleet(const CollisionParams& c, const DwaPara
 // frees the cached ring offsets and inflated-map buffers of every device
 void release_collision_caches();
 
+// ---- fleet layer: robots as obstacles to one another (fleet_layer_kernel.hip, fleet_spans.hpp) ----
+// What the collision kernels read of a layer.  count [h][w] over the centres [-R, xsize + R) x [-R, ysize + R) (the geometry
+// of the inflated map with the layer's reach R = r_col + body): the number of stamped robots whose body a pose centred there
+// collides with.  cell [B][2]: every robot's cell (x, y) at the last update, x = kFleetNotStamped for a robot that is no
+// obstacle (masked, or outside the grid).  row_start [2R + 2] / spans: the offset set F as row spans (FleetSpan).
+constexpr int kFleetNotStamped = -2147483647 - 1;
+struct FleetSpan;
+struct FleetView
+{
+  const int* count = nullptr;
+  const int* cell = nullptr;
+  const int* row_start = nullptr;
+  const FleetSpan* spans = nullptr;
+  int R = 0, w = 0, h = 0;
+  unsigned B = 0;
+};
+// The span table of (radii, body) in the memory of `device`, built once and shared by the layers that use it.
+// release_fleet_spans: a layer gives its table back; release_fleet_span_cache frees the tables no layer holds.
+hipError_t acquire_fleet_spans(int device, const CollisionParams& c, int body, const int** d_row_start, const FleetSpan** d_spans,
+                               int* n_spans);
+void release_fleet_spans(int device, const FleetSpan* d_spans);
+void release_fleet_span_cache();
+// One update, three stream operations and no host wait: clear the difference map, one wavefront per robot stamps +1 / -1 at
+// the ends of its spans (and records its cell), a prefix sum along every row.  d_mask may be null (every robot is active)
+hipError_t launch_fleet_layer_update(const CollisionParams& c, const FleetView& v, int n_spans, int* d_count, int* d_cell,
+                                     const double* d_pose, const int* d_mask, hipStream_t s);
+// collisionCheck of P poses with the layer: d_grid may be null (robots only), d_self may be null (no pose is a robot's own)
+hipError_t launch_fleet_collision_check(const CollisionParams& c, const FleetView& v, const int8_t* d_grid, const double* d_pose,
+                                        const int* d_self, unsigned P, int* d_hit, hipStream_t s);
+// launch_validate_and_dwa_fleet with the layer in every collision test; robot r of the tick is robot r of the layer
+hipError_t launch_validate_and_dwa_fleet_layer(const CollisionParams& c, const DwaParams& d, const FleetView& v, const int8_t* d_grid,
+                                               unsigned long long grid_epoch, const double* d_x0, const double* d_vb,
+                                               const double* d_traj, unsigned n_ref, double dt_ref, double val_dt,
+                                               unsigned val_steps, int* d_valid, int* d_follow, unsigned* d_count, double* d_u,
+                                               int* d_source, unsigned P, hipStream_t s);
+
 // ---- range sensing of a simulated fleet (sense_kernel.hip) -------------------------------
 // every robot's 8 * range_cells rays through d_truth: the cells they cross are copied into d_known, d_ranges [P][8R]
 // (optional) = the step at which a ray met a blocking cell or -1; c: the geometry and occupied_threshold (radii unused)

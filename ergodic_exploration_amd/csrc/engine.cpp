@@ -12,6 +12,7 @@
 #include <cstring>
 #include <memory>
 #include <mutex>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -1895,7 +1896,11 @@ eea_status eea_integrate_twist_batch(int device, const double* d_x0, const doubl
   return EEA_OK;
 }
 
-void eea_release_collision_caches(void) { eea::release_collision_caches(); }
+void eea_release_collision_caches(void)
+{
+  eea::release_collision_caches();
+  eea::release_fleet_span_cache();  // (the span tables no fleet layer holds)
+}
 
 // ---- range sensing of a simulated fleet ------------------------------------------------------
 // the geometry of an eea_collision_cfg without Collision::Collision's checks of the radii, which the sensor does not read
@@ -2017,26 +2022,55 @@ eea_status eea_set_target_gain(eea_engine* e, const eea_collision_cfg* cfg, unsi
   return EEA_OK;
 }
 
-// One tick of Exploration<ModelT>::control's loop body for B robots (exploration.hpp:220-279): see ergodic_amd.h
-eea_status eea_tick_batch(eea_engine* e, unsigned B, const eea_batch_io* io, const eea_tick_io* tick,
-                          const eea_collision_cfg* ccfg, const eea_dwa_cfg* dcfg, void* stream)
+}  // extern "C"
+
+// ---- fleet layer: robots as obstacles to one another --------------------------------------------
+struct eea_fleet_layer
+{
+  int device = 0, body = 0, n_spans = 0;
+  eea::CollisionParams c{};
+  eea::FleetView v{};  // (count / cell point at d_count / d_cell)
+  int* d_count = nullptr;
+  int* d_cell = nullptr;
+};
+
+static bool same_collision_params(const eea::CollisionParams& a, const eea::CollisionParams& b)
+{
+  return a.xmin == b.xmin && a.ymin == b.ymin && a.resolution == b.resolution && a.xsize == b.xsize && a.ysize == b.ysize &&
+         a.r_bnd == b.r_bnd && a.r_col == b.r_col && a.r_max == b.r_max && a.occupied_threshold == b.occupied_threshold;
+}
+
+// One tick of Exploration<ModelT>::control's loop body for B robots (exploration.hpp:220-279): see ergodic_amd.h.  with_layer: the
+// call is eea_tick_batch_fleet -- `layer` must not be null and is used in steps 3 and 4, and the messages name that entry
+static eea_status tick_batch_impl(eea_engine* e, unsigned B, const eea_batch_io* io, const eea_tick_io* tick,
+                                  const eea_collision_cfg* ccfg, const eea_dwa_cfg* dcfg, const eea_fleet_layer* layer,
+                                  bool with_layer, void* stream)
 {
   // (refusals of several kinds, B == 0 and the parameter blocks come before the device is touched: no shared prologue)
+  const char* const entry = with_layer ? "eea_tick_batch_fleet" : "eea_tick_batch";  // (for the refusal messages)
   if (e == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null engine");
   if (io == nullptr || tick == nullptr || dcfg == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
-  if (e->f32) return fail(EEA_ERR_UNSUPPORTED, "eea_tick_batch takes fp64 engines (poses and twists are doubles)");
+  if (e->f32) return fail(EEA_ERR_UNSUPPORTED, std::string(entry) + " takes fp64 engines (poses and twists are doubles)");
   if (io->d_pose == nullptr || io->d_ut == nullptr || tick->d_follow_dwa == nullptr || tick->d_dwa_count == nullptr ||
       tick->d_u == nullptr || tick->d_vb == nullptr || tick->d_grid == nullptr || tick->d_traj == nullptr ||
       tick->d_valid == nullptr || tick->d_skip == nullptr) {
     return fail(EEA_ERR_INVALID_ARGUMENT, "null tick buffer");
   }
   if (io->d_rec_ready != nullptr || io->d_ck_flag != nullptr) {
-    return fail(EEA_ERR_UNSUPPORTED, "eea_tick_batch does not take the device-bound exchange buffers");
+    return fail(EEA_ERR_UNSUPPORTED, std::string(entry) + " does not take the device-bound exchange buffers");
   }
-  if (B == 0) return EEA_OK;
+  if (with_layer && layer == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null fleet layer");
+  if (B == 0 && !with_layer) return EEA_OK;
   eea::CollisionParams c;
   eea_status st = make_collision_params(ccfg, c);
   if (st != EEA_OK) return st;
+  if (with_layer) {
+    if (B != layer->v.B) return fail(EEA_ERR_INVALID_ARGUMENT, "the tick's B is not the fleet layer's");
+    if (!same_collision_params(c, layer->c)) {
+      return fail(EEA_ERR_INVALID_ARGUMENT, "the tick's collision configuration is not the fleet layer's");
+    }
+    if (layer->device != e->cfg.device) return fail(EEA_ERR_INVALID_ARGUMENT, "the fleet layer lives on another device than the engine");
+  }
   eea::DwaParams d;
   st = make_dwa_params(dcfg, d);
   if (st != EEA_OK) return st;
@@ -2066,10 +2100,121 @@ eea_status eea_tick_batch(eea_engine* e, unsigned B, const eea_batch_io* io, con
   // 3. validate_control (:238, numerics.hpp:312-330); 4. the dynamic window where the twist was rejected (:240-277), u /
   // follow_dwa / i updated in place.  One inflated map for both
   const unsigned val_steps = static_cast<unsigned>(std::abs(tick->val_horizon / tick->val_dt));
+  if (with_layer) {
+    EEA_HIP(eea::launch_validate_and_dwa_fleet_layer(c, d, layer->v, tick->d_grid, tick->grid_epoch,
+                                                     static_cast<const double*>(io->d_pose), tick->d_vb, tick->d_traj,
+                                                     static_cast<unsigned>(e->T), e->cfg.dt, tick->val_dt, val_steps, tick->d_valid,
+                                                     tick->d_follow_dwa, tick->d_dwa_count, tick->d_u, tick->d_source, B, s));
+    return EEA_OK;
+  }
   EEA_HIP(eea::launch_validate_and_dwa_fleet(c, d, tick->d_grid, tick->grid_epoch, static_cast<const double*>(io->d_pose),
                                              tick->d_vb, tick->d_traj, static_cast<unsigned>(e->T), e->cfg.dt, tick->val_dt,
                                              val_steps, tick->d_valid, tick->d_follow_dwa, tick->d_dwa_count, tick->d_u,
                                              tick->d_source, B, s));
+  return EEA_OK;
+}
+
+extern "C" {
+
+eea_status eea_tick_batch(eea_engine* e, unsigned B, const eea_batch_io* io, const eea_tick_io* tick,
+                          const eea_collision_cfg* ccfg, const eea_dwa_cfg* dcfg, void* stream)
+{
+  return tick_batch_impl(e, B, io, tick, ccfg, dcfg, nullptr, false, stream);
+}
+
+eea_status eea_tick_batch_fleet(eea_engine* e, unsigned B, const eea_batch_io* io, const eea_tick_io* tick,
+                                const eea_collision_cfg* ccfg, const eea_dwa_cfg* dcfg, const eea_fleet_layer* l, void* stream)
+{
+  return tick_batch_impl(e, B, io, tick, ccfg, dcfg, l, true, stream);
+}
+
+eea_status eea_fleet_layer_create(int device, const eea_collision_cfg* cfg, int body_cells, unsigned B, eea_fleet_layer** out)
+{
+  if (out == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  *out = nullptr;
+  eea::CollisionParams c;
+  const eea_status st = make_collision_params(cfg, c);
+  if (st != EEA_OK) return st;
+  if (B == 0) return fail(EEA_ERR_INVALID_ARGUMENT, "a fleet layer needs at least one robot");
+  if (body_cells < 0) return fail(EEA_ERR_INVALID_ARGUMENT, "the body radius of a fleet layer must be >= 0 cells");
+  if (cfg->xsize == 0 || cfg->ysize == 0) return fail(EEA_ERR_INVALID_ARGUMENT, "the grid's xsize and ysize must be positive");
+  if (!(cfg->resolution > 0.0)) return fail(EEA_ERR_INVALID_ARGUMENT, "the grid's resolution must be positive");
+  if (c.r_bnd < 0 || c.r_col < 0) return fail(EEA_ERR_INVALID_ARGUMENT, "the collision radii must not be negative");
+  // the reach R' = r_col + body (the span table holds shorts; the padded map grows by R' on every side)
+  if (c.r_col > 127 || body_cells > 127 || c.r_col + body_cells > 127) {
+    return fail(EEA_ERR_UNSUPPORTED, "a fleet layer's reach r_col + body above 127 cells");
+  }
+  const int R = c.r_col + body_cells;
+  const unsigned long long w = static_cast<unsigned long long>(c.xsize) + 2u * R, h = static_cast<unsigned long long>(c.ysize) + 2u * R;
+  if (w > 0x7fffffffull || h > 0x7fffffffull || w * h > (1ull << 31) || B > 0x7fffffffu) {
+    return fail(EEA_ERR_UNSUPPORTED, "a fleet layer of more than 2^31 centres or robots");
+  }
+  eea_fleet_layer* l = new (std::nothrow) eea_fleet_layer();
+  if (l == nullptr) return fail(EEA_ERR_HIP, "fleet layer: out of host memory");
+  l->device = device;
+  l->body = body_cells;
+  l->c = c;
+  l->v.R = R;
+  l->v.w = static_cast<int>(w);
+  l->v.h = static_cast<int>(h);
+  l->v.B = B;
+  hipError_t err = hipSetDevice(device);
+  if (err == hipSuccess) err = eea::acquire_fleet_spans(device, c, body_cells, &l->v.row_start, &l->v.spans, &l->n_spans);
+  if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&l->d_count), sizeof(int) * static_cast<size_t>(w * h));
+  if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&l->d_cell), sizeof(int) * 2 * static_cast<size_t>(B));
+  // before the first update: no robot is an obstacle
+  if (err == hipSuccess) err = hipMemset(l->d_count, 0, sizeof(int) * static_cast<size_t>(w * h));
+  if (err == hipSuccess) err = hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(l->d_cell), eea::kFleetNotStamped, 2 * static_cast<size_t>(B));
+  if (err == hipSuccess) err = hipDeviceSynchronize();  // (the fills are done when the layer is handed out, whatever stream reads it)
+  if (err != hipSuccess) {
+    (void)hipGetLastError();
+    const std::string msg = std::string("fleet layer of ") + std::to_string(w) + " x " + std::to_string(h) + " centres: " + hipGetErrorString(err);
+    eea_fleet_layer_destroy(l);
+    return fail(EEA_ERR_HIP, msg);
+  }
+  l->v.count = l->d_count;
+  l->v.cell = l->d_cell;
+  *out = l;
+  return EEA_OK;
+}
+
+void eea_fleet_layer_destroy(eea_fleet_layer* l)
+{
+  if (l == nullptr) return;
+  if (l->v.spans != nullptr) eea::release_fleet_spans(l->device, l->v.spans);
+  if ((l->d_count != nullptr || l->d_cell != nullptr) && hipSetDevice(l->device) == hipSuccess) {
+    if (l->d_count != nullptr) (void)hipFree(l->d_count);  // waits for its users
+    if (l->d_cell != nullptr) (void)hipFree(l->d_cell);
+  }
+  delete l;
+}
+
+int eea_fleet_layer_reach(const eea_fleet_layer* l) { return l != nullptr ? l->v.R : -1; }
+
+eea_status eea_fleet_layer_update(eea_fleet_layer* l, const double* d_pose, const int* d_mask, void* stream)
+{
+  if (l == nullptr || d_pose == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  EEA_HIP(hipSetDevice(l->device));
+  EEA_HIP(eea::launch_fleet_layer_update(l->c, l->v, l->n_spans, l->d_count, l->d_cell, d_pose, d_mask, static_cast<hipStream_t>(stream)));
+  return EEA_OK;
+}
+
+eea_status eea_fleet_layer_read(const eea_fleet_layer* l, int* h_count, int* h_cell)
+{
+  if (l == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  EEA_HIP(hipSetDevice(l->device));
+  EEA_HIP(hipDeviceSynchronize());
+  if (h_count != nullptr) EEA_HIP(hipMemcpy(h_count, l->d_count, sizeof(int) * static_cast<size_t>(l->v.w) * l->v.h, hipMemcpyDeviceToHost));
+  if (h_cell != nullptr) EEA_HIP(hipMemcpy(h_cell, l->d_cell, sizeof(int) * 2 * static_cast<size_t>(l->v.B), hipMemcpyDeviceToHost));
+  return EEA_OK;
+}
+
+eea_status eea_fleet_collision_check_batch(const eea_fleet_layer* l, const int8_t* d_grid, const double* d_pose, const int* d_self,
+                                           unsigned P, int* d_hit, void* stream)
+{
+  if (l == nullptr || d_pose == nullptr || d_hit == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  EEA_HIP(hipSetDevice(l->device));
+  EEA_HIP(eea::launch_fleet_collision_check(l->c, l->v, d_grid, d_pose, d_self, P, d_hit, static_cast<hipStream_t>(stream)));
   return EEA_OK;
 }
 

@@ -789,9 +789,69 @@ eea_status eea_sense_gain_field(int device, const eea_collision_cfg* cfg, unsign
 eea_status eea_set_target_gain(eea_engine* e, const eea_collision_cfg* cfg, unsigned range_cells, unsigned stride,
                                const int8_t* d_known, double floor, double lx, double ly, unsigned* d_gain, void* stream);
 
+/* ---- fleet layer: the robots of a fleet as obstacles to one another (additive to ABI 6: detect these entries by symbol) --------
+ * eea_tick_batch validates every twist against the occupancy grid only: the robots of a tick drive through one another.  A
+ * fleet layer is built from the fleet's poses, every tick, on the device, and eea_tick_batch_fleet adds it to every collision
+ * test of steps 3 and 4.  "Avoid" is the reference's own: Collision::collisionCheck (collision.cpp:126-243) on a grid in which
+ * the other robots' bodies are occupied cells.  Integer arithmetic throughout.  With r_bnd, r_col, r_max the cell radii of cfg
+ * (floor(boundary_radius / resolution), floor((boundary_radius + obstacle_threshold) / resolution), floor(search_radius /
+ * resolution)) and S the offsets (cell - centre) at which collisionCheck's ring search r_bnd .. r_max can report a collision
+ * (those within r_col):
+ *   body radius    body_cells >= 0, in cells, given at creation; the natural value is r_bnd; 0 makes a robot a single cell;
+ *   offset set     F = { o + d : o in S, d integer, d.d <= body_cells^2 }; S is closed under 90-degree rotations, so F = -F;
+ *                  the reach is R' = r_col + body_cells;
+ *   obstacles      at an update, every robot j that is active (d_mask[j] != 0, or d_mask == NULL) and whose cell lies inside
+ *                  the grid bounds; its cell is GridMap::world2Grid of its pose (grid.cpp:143-159) with the x86-64 wrap, as
+ *                  everywhere else; a robot's cell is an obstacle whatever occupied_threshold is;
+ *   collision      a pose with centre cell c collides with robot j iff c - cell_j in F; robot b never collides with itself;
+ *   verdict        (the static verdict as without a layer) OR (the pose collides with any other robot);
+ *   staleness      the other robots stand still at their cells of the last update for a whole rollout: a snapshot, as the grid
+ *                  itself is.
+ * This equals the reference run on a grid of its own per robot -- copy the grid, set every cell within d.d <= body_cells^2 of
+ * each other obstacle robot's cell to 100, then collisionCheck / validate_control / DynamicWindow::control on that grid --
+ * whenever every disc lies inside the grid and occupied_threshold <= 1.0.  Near the edge the rule keeps the WHOLE body: it does
+ * not clip the disc to the grid (a pose outside the grid still collides with the part of a body that the grid would cut off).
+ * What follows from the reference's ring search: with body_cells < r_bnd a robot nearer than the hollow of the ring is not seen
+ * (as a small obstacle under the robot's centre is not); and robots that start inside each other's F stand still -- every
+ * rollout of both that has not left F by its first step, the zero twist's included, predicts a collision, so validate_control
+ * fails and the dynamic window finds nothing (u = 0).
+ *
+ * The layer holds an int32 count per centre cell over [-R', xsize + R') x [-R', ysize + R') (row-major, row pitch xsize + 2 R':
+ * count[(cy + R') * (xsize + 2 R') + cx + R'] = the obstacle robots j with (cx, cy) - cell_j in F) and a [B][2] table of the
+ * robots' cells (x, y), both entries EEA_FLEET_NOT_STAMPED for a robot that is no obstacle.  Before the first update no robot
+ * is one.
+ * eea_fleet_layer_create: EEA_ERR_INVALID_ARGUMENT before any HIP call -- cfg or out null, B == 0, body_cells < 0, xsize or
+ *   ysize 0, resolution <= 0, the configuration errors of the collision calls; EEA_ERR_UNSUPPORTED -- R' > 127, more than 2^31
+ *   centres.  The row spans of F are cached per (device, radii, body_cells) and shared between layers.
+ * eea_fleet_layer_update: d_pose [B][3] doubles, d_mask [B] ints or NULL.  Three stream operations -- clear, one wavefront per
+ *   robot adds +1 / -1 at the ends of its spans of F (2 x spans atomic adds per robot, not |F|), a prefix sum along every row --
+ *   asynchronous on `stream`: reads nothing on the host, allocates nothing, makes no synchronising call.  The calls that read
+ *   the layer are issued on the same stream or ordered behind it by the caller.
+ * eea_fleet_layer_reach: R' (-1 for a null layer).
+ * eea_fleet_layer_read: for tests and tools; h_count [(ysize + 2 R')][(xsize + 2 R')] ints, h_cell [B][2] ints, either may be
+ *   NULL.  Synchronises the device.
+ * eea_fleet_collision_check_batch: eea_collision_check_batch of P poses on d_grid (the layer's geometry and radii) with the
+ *   layer; d_self [P] ints or NULL: the robot a pose belongs to, -1 (or NULL) for none; d_grid == NULL: robots only.
+ * eea_tick_batch_fleet: eea_tick_batch with the layer in steps 3 and 4 -- validate_control and the dynamic window see the other
+ *   robots; robot r of the tick is robot r of the layer.  ccfg must give the layer's geometry, radii and threshold and B the
+ *   layer's B (and the layer live on the engine's device), else EEA_ERR_INVALID_ARGUMENT: nothing is launched and the state is
+ *   untouched.  Everything else as eea_tick_batch.  A closed loop: eea_fleet_layer_update, eea_tick_batch_fleet,
+ *   eea_integrate_twist_batch on one stream, no host wait. */
+#define EEA_FLEET_NOT_STAMPED (-2147483647 - 1)
+typedef struct eea_fleet_layer eea_fleet_layer;
+eea_status eea_fleet_layer_create(int device, const eea_collision_cfg* cfg, int body_cells, unsigned B, eea_fleet_layer** out);
+void eea_fleet_layer_destroy(eea_fleet_layer* l);
+eea_status eea_fleet_layer_update(eea_fleet_layer* l, const double* d_pose, const int* d_mask, void* stream);
+int eea_fleet_layer_reach(const eea_fleet_layer* l);
+eea_status eea_fleet_layer_read(const eea_fleet_layer* l, int* h_count, int* h_cell);
+eea_status eea_fleet_collision_check_batch(const eea_fleet_layer* l, const int8_t* d_grid, const double* d_pose, const int* d_self,
+                                           unsigned P, int* d_hit, void* stream);
+eea_status eea_tick_batch_fleet(eea_engine* e, unsigned B, const eea_batch_io* io, const eea_tick_io* tick,
+                                const eea_collision_cfg* ccfg, const eea_dwa_cfg* dcfg, const eea_fleet_layer* l, void* stream);
+
 /* The collision / DWA / tick calls keep small device caches between calls (the ring offsets per radii, one
- * inflated-map buffer per (device, stream)).  A long-running process that changes streams or map sizes
- * can drop them; synchronises the devices involved.  No reference counterpart. */
+ * inflated-map buffer per (device, stream), the span tables of fleet layers that no layer holds any more).  A long-running
+ * process that changes streams or map sizes can drop them; synchronises the devices involved.  No reference counterpart. */
 void eea_release_collision_caches(void);
 
 #ifdef __cplusplus
