@@ -23,7 +23,9 @@
 //   * the gradient makes ONE pass over D per step (rows from LDS, wavefront-uniform broadcast reads: the LDS
 //     return path, 4 cycles per 16-byte row read and wavefront, is what bounded a two-pass form) with the
 //     cosine array and the G accumulators of ONE step in registers at a time: <= 128 registers, 4 wavefronts
-//     per SIMD, 9.2 KB of LDS per agent -- the 4096-agent batch is resident on the 1024 SIMDs in one round.
+//     per SIMD, 9.2 KB of LDS per agent -- the 4096-agent batch is resident on the 1024 SIMDs in one round.  fp64, K = 5 /
+//     10: D is held in registers instead and reaches the multiply-adds by DPP row broadcast (control_wave_regd.inc);
+//     the results are the LDS form's bits.
 //
 // What bounds it (profiles/r02_ubench_coissue.txt): fp64 matrix instructions run on the
 // vector pipe's own multipliers and hold it for their 64 cycles, so the pipe time of an agent is the SUM of its
@@ -46,6 +48,10 @@
 #define EEA_WSTAMP(n) ((void)0)
 #define EEA_WSTAMP_RT(n) ((void)0)
 #define EEA_WSTAMP_HWID(n) ((void)0)
+#endif
+// 1: the gradient of the fp64 K = 5 / 10 instances takes D from registers (control_wave_regd.inc); 0: from LDS, like the rest
+#ifndef EEA_WAVE_REGD
+#define EEA_WAVE_REGD 1
 #endif
 
 namespace eea
@@ -225,6 +231,26 @@ __device__ __forceinline__ double add_row_ror(double v)
   return v + dpp_or_zero<0x120 + N, 0xf>(v);  // row_ror:N, every lane has a source (bound_ctrl: no "old" operand to set up)
 }
 
+// a b - c d and a b + c d in fp64 as ONE v_mul_f64 (c d, rounded) and ONE v_fma_f64 (a b fused), said here.  Left to
+// contract `a * b + c * d` itself the compiler may fuse either product, and it picks by the use counts of the two
+// multiplies -- which code far behind the site can change: with the gradient's LDS reads of D replaced by registers the
+// K = 5 instances fused the other product in the sine of the basis rotations, the rollout's basis angles moved by one unit in
+// the last place, c_k with them, and 50 receding-horizon steps of clamped controls turn that into sign flips
+// (profiles/wave_regd.txt).  Every two-product site of the phases up to c_k is written with these, each in the form the
+// compiler had chosen when they were pinned, so that no instance's bits moved.  (fp32: the compiler's choice, as before.)
+template <typename R>
+__device__ __forceinline__ R mul_sub(R a, R b, R c, R d)
+{
+  if constexpr (sizeof(R) == 8) return __builtin_fma(a, b, -(c * d));
+  else return a * b - c * d;
+}
+template <typename R>
+__device__ __forceinline__ R mul_add(R a, R b, R c, R d)
+{
+  if constexpr (sizeof(R) == 8) return __builtin_fma(a, b, c * d);
+  else return a * b + c * d;
+}
+
 template <typename R, int MODEL>
 __device__ __forceinline__ void model_xy(R vx, R vy, R c, R s, R& fx, R& fy)
 {
@@ -234,6 +260,31 @@ __device__ __forceinline__ void model_xy(R vx, R vy, R c, R s, R& fx, R& fy)
   } else {  // cart.hpp:172
     fx = vx * c;
     fy = vx * s;
+  }
+}
+// the fp64 wavefront-per-agent kernel's, with the fused products pinned (mul_sub / mul_add above): f(x, u), and f(x, u) +
+// (ax, ay) for the Simpson sums k1 + 2 k2, where SimpleCart's single product takes 2 k2 as its addend
+template <int MODEL>
+__device__ __forceinline__ void model_xy_pinned(double vx, double vy, double c, double s, double& fx, double& fy)
+{
+  if (MODEL == kModelOmni) {
+    fx = mul_sub(vx, c, vy, s);
+    fy = mul_add(vx, s, vy, c);
+  } else {
+    fx = vx * c;
+    fy = vx * s;
+  }
+}
+template <int MODEL>
+__device__ __forceinline__ void model_xy_plus(double vx, double vy, double c, double s, double ax, double ay, double& fx,
+                                              double& fy)
+{
+  if (MODEL == kModelOmni) {
+    fx = mul_sub(vx, c, vy, s) + ax;
+    fy = mul_add(vx, s, vy, c) + ay;
+  } else {
+    fx = __builtin_fma(vx, c, ax);
+    fy = __builtin_fma(vx, s, ay);
   }
 }
 
@@ -264,6 +315,9 @@ constexpr int waves_per_simd(int KC, int real_size)
 // (the K <= 16 instance likewise: all 16 modes at once, 150-157 registers in fp64 = 3 wavefronts per SIMD, still 7-9 % faster
 // than two blocks of 8 at 4 wavefronts per SIMD: K = 16 69.5 -> 64.1 us, K = 12 54.0 -> 50.0, fp32 K = 16 39.3 -> 35.8)
 constexpr int grad_block(int KC) { return KC; }
+
+// RegDGrad<K>: the gradient's pass over D with D in registers (fp64, K = 5 / 10; the kernel's kRegD)
+#include "control_wave_regd.inc"
 
 }  // namespace wave
 }  // namespace eea
@@ -567,25 +621,34 @@ __global__ __launch_bounds__(WPB* kWave, waves_per_simd(KC, sizeof(R))) void con
         if (fast_h) {  // wavefront-uniform
           R sd, cd;
           sincospi_small(dt * (R(0.5) * w[j]) * inv_pi, &sd, &cd);
-          cm = c * cd - s * sd;
-          sm_ = s * cd + c * sd;
-          cpost = cm * cd - sm_ * sd;
-          spost = sm_ * cd + cm * sd;
+          cm = mul_sub(c, cd, s, sd);
+          sm_ = mul_add(c, sd, s, cd);
+          cpost = mul_sub(cm, cd, sm_, sd);
+          spost = mul_add(sm_, cd, cm, sd);
         } else {
           const R th_pre = (j == 0) ? thp[0] - dt6 * (((w[0] + R(2) * w[0]) + R(2) * w[0]) + w[0]) : thp[j - 1];
           sincospi_r((th_pre + dt * (R(0.5) * w[j])) * inv_pi, &sm_, &cm);
           const R c2m = R(1) - R(2) * sm_ * sm_, s2m = R(2) * sm_ * cm;
-          cpost = c2m * c + s2m * s;
-          spost = s2m * c - c2m * s;
+          cpost = mul_add(s2m, s, c2m, c);
+          spost = mul_sub(s2m, c, c2m, s);
         }
-        R k1x, k1y, k2x, k2y, k4x, k4y;
-        model_xy<R, MODEL>(vx[j], vy[j], c, s, k1x, k1y);
-        model_xy<R, MODEL>(vx[j], vy[j], cm, sm_, k2x, k2y);
-        model_xy<R, MODEL>(vx[j], vy[j], cpost, spost, k4x, k4y);
         // steps beyond the horizon carry zero controls (the loads are guarded), so their increments are exact
         // zeros: no select
-        incx[j] = dt6 * (((k1x + R(2) * k2x) + R(2) * k2x) + k4x);
-        incy[j] = dt6 * (((k1y + R(2) * k2y) + R(2) * k2y) + k4y);
+        if constexpr (sizeof(R) == 8) {
+          double k2x, k2y, k4x, k4y, k12x, k12y;  // k12 = k1 + 2 k2
+          model_xy_pinned<MODEL>(vx[j], vy[j], cm, sm_, k2x, k2y);
+          model_xy_pinned<MODEL>(vx[j], vy[j], cpost, spost, k4x, k4y);
+          model_xy_plus<MODEL>(vx[j], vy[j], c, s, k2x + k2x, k2y + k2y, k12x, k12y);
+          incx[j] = dt6 * ((k12x + R(2) * k2x) + k4x);
+          incy[j] = dt6 * ((k12y + R(2) * k2y) + k4y);
+        } else {
+          R k1x, k1y, k2x, k2y, k4x, k4y;
+          model_xy<R, MODEL>(vx[j], vy[j], c, s, k1x, k1y);
+          model_xy<R, MODEL>(vx[j], vy[j], cm, sm_, k2x, k2y);
+          model_xy<R, MODEL>(vx[j], vy[j], cpost, spost, k4x, k4y);
+          incx[j] = dt6 * (((k1x + R(2) * k2x) + R(2) * k2x) + k4x);
+          incy[j] = dt6 * (((k1y + R(2) * k2y) + R(2) * k2y) + k4y);
+        }
         rx += incx[j];
         ry += incy[j];
         // parked for the backward half: heading after step j (A = fdx(x_j, u_j), B = fdu(x_j))
@@ -640,11 +703,14 @@ __global__ __launch_bounds__(WPB* kWave, waves_per_simd(KC, sizeof(R))) void con
       if (j > 0 && fast_b) {  // wavefront-uniform
         R sd, cd;
         sincospi_small(incx[j] * p.inv_lx, &sd, &cd);
-        c1x[j] = c1x[j - 1] * cd - s1x[j - 1] * sd;
-        s1x[j] = s1x[j - 1] * cd + c1x[j - 1] * sd;
+        // (which product of the sine the compiler fused differed from instance to instance when the sites were pinned:
+        // s cd in the x angle at K = 20 and in the y angle at K = 5 and 20, c sd everywhere else -- kept, with their bits)
+        constexpr bool kFuseSCdX = (KC == 20), kFuseSCdY = (KC == 20 || KC == 5);
+        c1x[j] = mul_sub(c1x[j - 1], cd, s1x[j - 1], sd);
+        s1x[j] = kFuseSCdX ? mul_add(s1x[j - 1], cd, c1x[j - 1], sd) : mul_add(c1x[j - 1], sd, s1x[j - 1], cd);
         sincospi_small(incy[j] * p.inv_ly, &sd, &cd);
-        c1y[j] = c1y[j - 1] * cd - s1y[j - 1] * sd;
-        s1y[j] = s1y[j - 1] * cd + c1y[j - 1] * sd;
+        c1y[j] = mul_sub(c1y[j - 1], cd, s1y[j - 1], sd);
+        s1y[j] = kFuseSCdY ? mul_add(s1y[j - 1], cd, c1y[j - 1], sd) : mul_add(c1y[j - 1], sd, s1y[j - 1], cd);
       } else {
         sincospi_r(x * p.inv_lx, &s1x[j], &c1x[j]);
         sincospi_r(y * p.inv_ly, &s1y[j], &c1y[j]);
@@ -1275,6 +1341,19 @@ __global__ __launch_bounds__(WPB* kWave, waves_per_simd(KC, sizeof(R))) void con
     lds_fence();
   }
 
+  // fp64, K = 5 / 10: D goes into registers for the gradient of the slots a lane owns by itself -- element e = k2 K + k1 in
+  // lane e % 16 of EVERY row of 16 lanes, register e / 16 (7 at K = 10, 2 at K = 5) -- and enters the multiply-adds by DPP
+  // row broadcast (control_wave_regd.inc): the ~200 wavefront-uniform LDS reads per step of a lane, each with its wait,
+  // on an LDS that 16 wavefronts share, are gone.  The cooperative last slot keeps reading s_D: its lanes take different rows.
+  // (make WAVE_EXTRA=-DEEA_WAVE_REGD=0 VARIANT=_ldsd builds the LDS form of the same text for an A/B)
+  constexpr bool kRegD = EEA_WAVE_REGD && sizeof(R) == 8 && (KC == 10 || KC == 5);
+  constexpr int kDRegs = kRegD ? (KC * KC + 15) / 16 : 1;
+  double Dv[kDRegs];
+  if constexpr (kRegD) {
+#pragma unroll
+    for (int q = 0; q < kDRegs; ++q) Dv[q] = s_D[min(16 * q + (lane & 15), KC * KC - 1)];
+  }
+
   EEA_WSTAMP(6);
   // ================= backward half =======================================================================
   // per step: ergodic-metric gradient (:418-436, basis.cpp:91-107)
@@ -1282,8 +1361,27 @@ __global__ __launch_bounds__(WPB* kWave, waves_per_simd(KC, sizeof(R))) void con
   //   edx_y = -pi/ly sin(b y) sum_k2 k2 U_{k2-1}(cos b y) H(k2),  H(k2) = sum_k1 D(k1,k2) cos(a_k1 x)
   // (sin(k a) = sin(a) U_{k-1}(cos a)); rows of D^T / D are wavefront-uniform LDS reads
   constexpr int KA = (KC == 16) ? 16 : KC;
-  // the barrier gradient waits in LDS while the gradient needs the registers (the tiles are dead)
-  if (!STAGES) {
+  // the barrier gradient waits in LDS while the gradient needs the registers (the tiles are dead), and g = edx + bdx is
+  // formed at the end of every slot.  With D in registers the instances with stage outputs do the same and store edx / bdx
+  // from the slot (K = 10: 122 registers otherwise)
+  constexpr bool kSumInSlot = !STAGES || kRegD;
+  auto store_edx_bdx = [&](int j, R exj, R eyj, R bx, R by) {
+    if (j < cnt) {
+      if (p.edx != nullptr) {
+        R* const o = p.edx + 3 * (static_cast<size_t>(T) * b + i0 + j);
+        o[0] = exj;
+        o[1] = eyj;
+        o[2] = R(0);
+      }
+      if (p.bdx != nullptr) {
+        R* const o = p.bdx + 3 * (static_cast<size_t>(T) * b + i0 + j);
+        o[0] = bx;
+        o[1] = by;
+        o[2] = R(0);
+      }
+    }
+  };
+  if (kSumInSlot) {
 #pragma unroll
     for (int j = 0; j < kMaxS; ++j) {
       if (j < S) {
@@ -1292,7 +1390,7 @@ __global__ __launch_bounds__(WPB* kWave, waves_per_simd(KC, sizeof(R))) void con
       }
     }
   }
-  R ex[STAGES ? kMaxS : 1], ey[STAGES ? kMaxS : 1];  // kept apart from the barrier gradient only for the outputs
+  R ex[kSumInSlot ? 1 : kMaxS], ey[kSumInSlot ? 1 : kMaxS];  // kept apart from the barrier gradient only for the outputs
   // Top-heavy horizon with four slots (T = 193 .. 200): the last slot holds <= 8 steps in lanes 0 .. 7.  A regular pass
   // would spend a full slot's instructions on them (a vector instruction costs the same whatever the lane mask,
   // tools/ubench/exec_mask.hip); instead all 64 lanes take them together, 8 lanes per step (below the loop).
@@ -1405,7 +1503,7 @@ __global__ __launch_bounds__(WPB* kWave, waves_per_simd(KC, sizeof(R))) void con
 #pragma unroll
   for (int j = 0; j < kMaxS; ++j) {
     if (kPairGrad) break;
-    if (STAGES) ex[j] = ey[j] = R(0);
+    if (!kSumInSlot) ex[j] = ey[j] = R(0);
     // one step at a time: the rows of D are re-read per step; without the fence the compiler keeps them (and
     // the arrays of all four steps) in registers across the unrolled steps and spills
     asm volatile("" ::: "memory");
@@ -1432,7 +1530,9 @@ __global__ __launch_bounds__(WPB* kWave, waves_per_simd(KC, sizeof(R))) void con
           ta = tb;
           tb = tn;
         }
-        {
+        if constexpr (kRegD) {  // KB == KC: one block
+          RegDGrad<kRegD ? KC : 5>::run(Dv, cxa, G, c1y[j], twoy, accy);
+        } else {
         // row k2 = 0: cos(0 y) = 1 and k2 sin(0) = 0: only G takes part (G(0) is never used: k1 sin(0) = 0)
         {
           const R* const row = s_D + kb0;
@@ -1484,15 +1584,17 @@ __global__ __launch_bounds__(WPB* kWave, waves_per_simd(KC, sizeof(R))) void con
       const R sx = s1x[j], sy = s1y[j];
       const R exj = (-p.pi_lx * sx * accx) * p.expl_weight;
       const R eyj = (-p.pi_ly * sy * accy) * p.expl_weight;
-      if (STAGES) {
+      if (!kSumInSlot) {
         ex[j] = exj;
         ey[j] = eyj;
       } else {
         // g = edx + bdx (inactive steps contribute nothing to the suffix sums); the basis registers of this
         // step are dead from here on
         const bool act = j < cnt;
-        g0[j] = act ? exj + s_g[(2 * j + 0) * kWave + lane] : R(0);
-        g1[j] = act ? eyj + s_g[(2 * j + 1) * kWave + lane] : R(0);
+        const R bx = s_g[(2 * j + 0) * kWave + lane], by = s_g[(2 * j + 1) * kWave + lane];
+        if (STAGES) store_edx_bdx(j, exj, eyj, bx, by);
+        g0[j] = act ? exj + bx : R(0);
+        g1[j] = act ? eyj + by : R(0);
       }
     }
   }
@@ -1589,34 +1691,21 @@ __global__ __launch_bounds__(WPB* kWave, waves_per_simd(KC, sizeof(R))) void con
       const R sx = s1x[jt];
       const R exj = (-p.pi_lx * sx * accx) * p.expl_weight;
       const R eyj = (-p.pi_ly * accy) * p.expl_weight;  // (sin b is in the row factors)
-      if (STAGES) {
+      if (!kSumInSlot) {
         ex[jt] = exj;
         ey[jt] = eyj;
       } else {
         const bool act = jt < cnt;  // lanes 0 .. r-1
-        g0[jt] = act ? exj + s_g[(2 * jt + 0) * kWave + lane] : R(0);
-        g1[jt] = act ? eyj + s_g[(2 * jt + 1) * kWave + lane] : R(0);
+        const R bx = s_g[(2 * jt + 0) * kWave + lane], by = s_g[(2 * jt + 1) * kWave + lane];
+        if (STAGES) store_edx_bdx(jt, exj, eyj, bx, by);
+        g0[jt] = act ? exj + bx : R(0);
+        g1[jt] = act ? eyj + by : R(0);
       }
     }
   }
-  if (STAGES) {
+  if (STAGES && !kSumInSlot) {
 #pragma unroll
-    for (int j = 0; j < kMaxS; ++j) {
-      if (j < cnt) {
-        if (p.edx != nullptr) {
-          R* const o = p.edx + 3 * (static_cast<size_t>(T) * b + i0 + j);
-          o[0] = ex[j];
-          o[1] = ey[j];
-          o[2] = R(0);
-        }
-        if (p.bdx != nullptr) {
-          R* const o = p.bdx + 3 * (static_cast<size_t>(T) * b + i0 + j);
-          o[0] = g0[j];
-          o[1] = g1[j];
-          o[2] = R(0);
-        }
-      }
-    }
+    for (int j = 0; j < kMaxS; ++j) store_edx_bdx(j, ex[j], ey[j], g0[j], g1[j]);
   }
 
   EEA_WSTAMP(7);
@@ -1652,7 +1741,7 @@ __global__ __launch_bounds__(WPB* kWave, waves_per_simd(KC, sizeof(R))) void con
     R s0 = R(0), s1 = R(0);
 #pragma unroll
     for (int j = kMaxS - 1; j >= 0; --j) {
-      if (STAGES) {
+      if (!kSumInSlot) {
         const bool act = j < cnt;
         g0[j] = act ? ex[j] + g0[j] : R(0);  // g = edx + bdx
         g1[j] = act ? ey[j] + g1[j] : R(0);
