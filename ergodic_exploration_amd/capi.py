@@ -64,6 +64,14 @@ class CollisionCfg(C.Structure):
                 ("occupied_threshold", C.c_double)]
 
 
+class Clearance(C.Structure):
+    """eea_clearance: msg (COLLISION_*), sqrd_obs, dx, dy -- crash: 0, 0, 0; none: -1, 0, 0"""
+    _fields_ = [("msg", C.c_int), ("sqrd_obs", C.c_int), ("dx", C.c_int), ("dy", C.c_int)]
+
+
+COLLISION_CRASH, COLLISION_OBSTACLE, COLLISION_NONE = 0, 1, 2   # CollisionMsg (collision.hpp:55-60)
+
+
 class DwaCfg(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("dt", "horizon", "acc_dt", "acc_lim_x", "acc_lim_y", "acc_lim_th",
                                           "max_vel_x", "min_vel_x", "max_vel_y", "min_vel_y",
@@ -201,6 +209,10 @@ def lib():
         L.eea_validate_control_batch.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_double, C.c_double,
                                                  C.c_uint, C.c_void_p, C.c_void_p]
+        if hasattr(L, "eea_clearance_batch"):   # additive to ABI 6: found by symbol (an older library variant has neither)
+            L.eea_clearance_batch.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]
+            L.eea_clearance_field.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.eea_replay_create.argtypes = [C.c_int, C.c_uint, C.c_uint, C.c_uint, C.c_uint64, C.c_uint, C.c_size_t, C.POINTER(C.c_void_p)]
         L.eea_replay_destroy.argtypes = [C.c_void_p]
         L.eea_replay_destroy.restype = None
@@ -610,8 +622,22 @@ def dwa_control_batch(ccfg, dcfg, grid, x0, vb, u_opt, found, vref=None, xt_ref=
                                       _ptr(found), C.c_void_p(stream or 0)))
 
 
+def clearance_batch(cfg, grid, pose, out, dmin=None, disp=None, device=0, stream=None):
+    """eea_clearance_batch: Collision::minDistance + minDirection of the P poses pose [P][3] on the int8 device grid.  out: int32
+    [P][4] (one Clearance per pose: msg, sqrd_obs, dx, dy), dmin: float64 [P], disp: float64 [P][2]; each may be None, not all
+    three.  Device tensors; asynchronous"""
+    check(lib().eea_clearance_batch(device, C.byref(cfg), _ptr(grid), _ptr(pose), int(pose.shape[0]), _ptr(out), _ptr(dmin),
+                                    _ptr(disp), C.c_void_p(stream or 0)))
+
+
+def clearance_field(cfg, grid, field=None, dmin=None, device=0, stream=None):
+    """eea_clearance_field: the same for the centre of every cell; field: int32 [ysize][xsize][4], dmin: float64 [ysize][xsize];
+    either may be None, not both.  Device tensors; asynchronous"""
+    check(lib().eea_clearance_field(device, C.byref(cfg), _ptr(grid), _ptr(field), _ptr(dmin), C.c_void_p(stream or 0)))
+
+
 def release_collision_caches():
-    """drops the cached ring offsets / inflated-map buffers of the collision, validate and DWA calls"""
+    """drops the cached ring offsets / map buffers of the collision, validate, DWA and clearance calls"""
     L = lib()
     L.eea_release_collision_caches.restype = None
     L.eea_release_collision_caches()

@@ -314,6 +314,16 @@ hipError_t launch_validate_and_dwa_fleet(const CollisionParams& c, const DwaPara
 // frees the cached ring offsets and inflated-map buffers of every device
 void release_collision_caches();
 
+// ---- clearance queries: Collision::minDistance / minDirection (clearance_kernel.hip) ----------
+// false: the (|d|^2, k) key of the parameter set does not fit 32 bits (hit_map_table.hpp).  Host work only, no HIP call.
+bool clearance_supported(const CollisionParams& c);
+// d_pose != null: the n poses [n][3]; d_pose == null: the centres of the n = xsize * ysize cells, row-major.  d_out [n][4]
+// ints (msg, sqrd_obs, dx, dy), d_dmin [n], d_disp [n][2]: each may be null.  The caller has checked clearance_supported.
+hipError_t launch_clearance(const CollisionParams& c, double boundary_radius, const int8_t* d_grid, const double* d_pose,
+                            size_t n, int* d_out, double* d_dmin, double* d_disp, hipStream_t s);
+// frees the cached visit-ordered offsets and key-map buffers of every device
+void release_clearance_caches();
+
 // ---- fleet layer: robots as obstacles to one another (fleet_layer_kernel.hip, fleet_spans.hpp) ----
 // What the collision kernels read of a layer.  count [h][w] over the centres [-R, xsize + R) x [-R, ysize + R) (the geometry
 // of the inflated map with the layer's reach R = r_col + body): the number of stamped robots whose body a pose centred there

@@ -1896,9 +1896,60 @@ eea_status eea_integrate_twist_batch(int device, const double* d_x0, const doubl
   return EEA_OK;
 }
 
+// ---- clearance queries: Collision::minDistance / minDirection (collision.cpp:65-124) -----------
+static_assert(sizeof(eea_clearance) == 4 * sizeof(int), "the kernels write an eea_clearance as four ints");
+
+// the checks of the configuration both clearance calls share, before the device is selected: Collision::Collision's own
+// (collision.cpp:46-63), a grid the kernels can index, and the key bound
+static eea_status make_clearance_params(const eea_collision_cfg* cfg, eea::CollisionParams& c)
+{
+  if (cfg != nullptr && !(cfg->resolution > 0.0)) return fail(EEA_ERR_INVALID_ARGUMENT, "the grid's resolution must be positive");
+  const eea_status st = make_collision_params(cfg, c);
+  if (st != EEA_OK) return st;
+  // (with a size of 0 the reference's gridBounds, grid.cpp:96-100, lets every cell index through)
+  if (cfg->xsize == 0 || cfg->ysize == 0) return fail(EEA_ERR_INVALID_ARGUMENT, "the grid's xsize and ysize must be positive");
+  if (static_cast<unsigned long long>(cfg->xsize) * cfg->ysize > (1ull << 31)) {
+    return fail(EEA_ERR_UNSUPPORTED, "xsize * ysize above 2^31");
+  }
+  if (!eea::clearance_supported(c)) {
+    return fail(EEA_ERR_UNSUPPORTED, "the search radius is too large in cells: the clearance key (|d|^2, visit index) does not fit 32 bits");
+  }
+  return EEA_OK;
+}
+
+eea_status eea_clearance_batch(int device, const eea_collision_cfg* cfg, const int8_t* d_grid, const double* d_pose, unsigned P,
+                               eea_clearance* d_out, double* d_dmin, double* d_disp, void* stream)
+{
+  eea::CollisionParams c;
+  const eea_status st = make_clearance_params(cfg, c);
+  if (st != EEA_OK) return st;
+  if (d_grid == nullptr || d_pose == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  if (d_out == nullptr && d_dmin == nullptr && d_disp == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "no output");
+  if (P == 0) return EEA_OK;
+  EEA_HIP(hipSetDevice(device));
+  EEA_HIP(eea::launch_clearance(c, cfg->boundary_radius, d_grid, d_pose, P, reinterpret_cast<int*>(d_out), d_dmin, d_disp,
+                                static_cast<hipStream_t>(stream)));
+  return EEA_OK;
+}
+
+eea_status eea_clearance_field(int device, const eea_collision_cfg* cfg, const int8_t* d_grid, eea_clearance* d_field,
+                               double* d_dmin, void* stream)
+{
+  eea::CollisionParams c;
+  const eea_status st = make_clearance_params(cfg, c);
+  if (st != EEA_OK) return st;
+  if (d_grid == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  if (d_field == nullptr && d_dmin == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "no output");
+  EEA_HIP(hipSetDevice(device));
+  EEA_HIP(eea::launch_clearance(c, cfg->boundary_radius, d_grid, nullptr, static_cast<size_t>(c.xsize) * c.ysize,
+                                reinterpret_cast<int*>(d_field), d_dmin, nullptr, static_cast<hipStream_t>(stream)));
+  return EEA_OK;
+}
+
 void eea_release_collision_caches(void)
 {
   eea::release_collision_caches();
+  eea::release_clearance_caches();
   eea::release_fleet_span_cache();  // (the span tables no fleet layer holds)
 }
 

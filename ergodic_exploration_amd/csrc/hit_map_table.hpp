@@ -1,6 +1,7 @@
 // Host-side bookkeeping of the inflated collision map (collision_kernel.hip): the offset set of the dilation and the policy
 // of the map buffers kept between calls.  Plain C++: no HIP call, no global state, no lock -- collision_kernel.hip owns the
-// mutex and performs every effect; tests/hit_map_table_check.cpp drives this file alone, without a GPU.
+// mutex and performs every effect; tests/hit_map_table_check.cpp drives this file alone, without a GPU.  Also the visit-
+// ordered walk of the clearance queries (clearance_kernel.hip), which tests/clearance_walk_check.cpp drives the same way.
 #pragma once
 
 #include <set>
@@ -40,6 +41,57 @@ inline std::vector<short2> ring_offsets(int r_bnd, int r_col, int r_max)
     out.push_back(make_short2(static_cast<short>(p.first), static_cast<short>(p.second)));
   }
   return out;
+}
+
+// The same walk in VISIT order with duplicates kept (clearance_kernel.hip): offsets[k] is the k-th cell (cell - centre) the
+// search r_bnd..r_max tests, Q1 Q2 Q3 Q4 of every Bresenham step (collision.cpp:175-193).  Collision::minDistance /
+// minDirection keep the FIRST visited cell of the smallest squared distance, i.e. the smallest key (|d_k|^2, k); the device
+// holds that key in one 32-bit word, |d_k|^2 * n + k, with the all-ones word for "no cell".
+struct ClearanceWalk
+{
+  std::vector<short2> offsets;
+  int reach = 0;        // max |component| of an offset: the key map covers the centres [-reach, size + reach)
+  unsigned max_sq = 0;  // max |d_k|^2
+};
+constexpr unsigned kNoClearanceKey = 0xffffffffu;
+
+// every key of n offsets up to max_sq is below kNoClearanceKey
+inline bool clearance_key_fits(unsigned long long max_sq, unsigned long long n)
+{
+  return (max_sq + 1ull) * n <= 0xffffffffull;  // the largest key is max_sq * n + n - 1
+}
+
+// false: the parameter set is refused (its largest key does not fit), `w` is then unspecified
+inline bool clearance_walk(int r_bnd, int r_max, ClearanceWalk& w)
+{
+  w = ClearanceWalk{};
+  // The ring r_max alone has at least 4 r_max offsets (x goes from -r_max to 0 by at most 1 per step) of |d|^2 >= r_max^2:
+  // 4 r_max^3 >= 2^32 from r_max = 1024 on.  Refused here, before a walk of that size is enumerated.
+  if (r_max >= 1024 && r_bnd <= r_max) return false;
+  for (int r0 = r_bnd < 1 ? 1 : r_bnd; r0 <= r_max; ++r0) {  // (a ring of radius <= 0 visits nothing)
+    int r = r0, x = -r0, y = 0, err = 2 - 2 * r0;
+    while (x < 0) {
+      const int q[4][2] = { { -x, y }, { -y, -x }, { x, -y }, { y, x } };
+      for (const auto& d : q) {
+        w.offsets.push_back(make_short2(static_cast<short>(d[0]), static_cast<short>(d[1])));
+        const int ax = d[0] < 0 ? -d[0] : d[0], ay = d[1] < 0 ? -d[1] : d[1];
+        if (ax > w.reach) w.reach = ax;
+        if (ay > w.reach) w.reach = ay;
+        const unsigned sq = static_cast<unsigned>(d[0] * d[0] + d[1] * d[1]);
+        if (sq > w.max_sq) w.max_sq = sq;
+      }
+      r = err;
+      if (r <= y) {
+        y++;
+        err += 2 * y + 1;
+      }
+      if (r > x || err > y) {
+        x++;
+        err += 2 * x + 1;
+      }
+    }
+  }
+  return clearance_key_fits(w.max_sq, w.offsets.size());
 }
 
 // What one build of an inflated map has to do, in this order: reallocate, clear, launch the dilation with `stamp`.

@@ -849,8 +849,38 @@ eea_status eea_fleet_collision_check_batch(const eea_fleet_layer* l, const int8_
 eea_status eea_tick_batch_fleet(eea_engine* e, unsigned B, const eea_batch_io* io, const eea_tick_io* tick,
                                 const eea_collision_cfg* ccfg, const eea_dwa_cfg* dcfg, const eea_fleet_layer* l, void* stream);
 
-/* The collision / DWA / tick calls keep small device caches between calls (the ring offsets per radii, one
- * inflated-map buffer per (device, stream), the span tables of fleet layers that no layer holds any more).  A long-running
+/* ---- clearance queries: Collision::minDistance / minDirection (collision.cpp:65-124) -------------------------------
+ * How close a pose is to an occupied cell, and in which direction, by the reference's own search (collision.cpp:148-243):
+ * the Bresenham rings r_bnd .. r_max around the pose's cell (radii in cells as for eea_collision_check_batch), four cells
+ * per step; the occupied in-grid cell of the smallest squared cell distance is kept -- of equal distances the first one
+ * visited (a strict <) -- and the search stops with "crash" at the first cell within r_col.  The rings have gaps; a cell in
+ * a gap is not seen, as in the reference.  Per pose (eea_clearance, and the doubles the two reference functions return):
+ *   crash      msg 0, sqrd_obs = dx = dy = 0;          dmin = 0.0;                     disp = (0, 0)
+ *   obstacle   msg 1, sqrd_obs, (dx, dy) = cell - pose's cell;
+ *              dmin = sqrt((double)sqrd_obs) * resolution - boundary_radius;           disp = (resolution * dx, resolution * dy)
+ *   none       msg 2, sqrd_obs = -1, dx = dy = 0;      dmin = DBL_MAX;                 disp = (DBL_MAX, DBL_MAX)
+ * bit for bit the reference's x86-64 results.  A call runs one wavefront per pose (or cell) or goes through a key map built
+ * from the grid per call (EEA_OPT_COLLISION_IMPL: 0 = cost model, 1 / 2 force the one / the other).  Both calls are
+ * asynchronous on `stream`; the buffers are device memory.  P == 0 is EEA_OK.
+ * Before the device is selected -- EEA_ERR_INVALID_ARGUMENT: cfg, d_grid or d_pose null; every output null; xsize or ysize 0;
+ * resolution <= 0; the configuration errors of the collision calls.  EEA_ERR_UNSUPPORTED: xsize * ysize > 2^31; a search
+ * radius of so many cells that (largest squared distance + 1) * (cells the search visits) exceeds 2^32 - 1 (with r_bnd = 0:
+ * an r_max above 196 cells).  No output is touched then.  eea_abi_version() stays 6. */
+enum { EEA_COLLISION_CRASH = 0, EEA_COLLISION_OBSTACLE = 1, EEA_COLLISION_NONE = 2 }; /* CollisionMsg, collision.hpp:55-60 */
+typedef struct eea_clearance {
+  int msg, sqrd_obs, dx, dy;
+} eea_clearance;
+/* Collision::minDistance (collision.cpp:65-93) + minDirection (collision.cpp:95-124) of P poses d_pose [P][3]; d_out [P],
+ * d_dmin [P] and d_disp [P][2] may each be NULL, not all three. */
+eea_status eea_clearance_batch(int device, const eea_collision_cfg* cfg, const int8_t* d_grid, const double* d_pose, unsigned P,
+                               eea_clearance* d_out, double* d_dmin, double* d_disp, void* stream);
+/* the same for the centre of every grid cell, row-major [ysize][xsize] (collision.cpp:65-93 per cell; the displacement is
+ * resolution * (dx, dy) of d_field); either output may be NULL, not both */
+eea_status eea_clearance_field(int device, const eea_collision_cfg* cfg, const int8_t* d_grid, eea_clearance* d_field,
+                               double* d_dmin, void* stream);
+
+/* The collision / DWA / tick / clearance calls keep small device caches between calls (the ring offsets per radii, one
+ * inflated-map and one key-map buffer per (device, stream), the span tables of fleet layers that no layer holds any more).  A long-running
  * process that changes streams or map sizes can drop them; synchronises the devices involved.  No reference counterpart. */
 void eea_release_collision_caches(void);
 
