@@ -70,6 +70,8 @@ class Clearance(C.Structure):
 
 
 COLLISION_CRASH, COLLISION_OBSTACLE, COLLISION_NONE = 0, 1, 2   # CollisionMsg (collision.hpp:55-60)
+COLLISION_OFF_GRID = 3       # the distance queries only: the pose's cell is not on the grid
+DISTANCE_MAX_SIDE = 8192     # EEA_DISTANCE_MAX_SIDE
 
 
 class DwaCfg(C.Structure):
@@ -213,6 +215,12 @@ def lib():
             L.eea_clearance_batch.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p]
             L.eea_clearance_field.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "eea_distance_field"):    # additive to ABI 6 as well
+            L.eea_distance_field.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.eea_distance_query_batch.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.eea_distance_traj_min.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint,
+                                                C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.eea_replay_create.argtypes = [C.c_int, C.c_uint, C.c_uint, C.c_uint, C.c_uint64, C.c_uint, C.c_size_t, C.POINTER(C.c_void_p)]
         L.eea_replay_destroy.argtypes = [C.c_void_p]
         L.eea_replay_destroy.restype = None
@@ -634,6 +642,29 @@ def clearance_field(cfg, grid, field=None, dmin=None, device=0, stream=None):
     """eea_clearance_field: the same for the centre of every cell; field: int32 [ysize][xsize][4], dmin: float64 [ysize][xsize];
     either may be None, not both.  Device tensors; asynchronous"""
     check(lib().eea_clearance_field(device, C.byref(cfg), _ptr(grid), _ptr(field), _ptr(dmin), C.c_void_p(stream or 0)))
+
+
+def distance_field(cfg, grid, sq, nearest=None, device=0, stream=None):
+    """eea_distance_field: the exact Euclidean distance transform of the occupied cells of the int8 device grid.  sq: int32
+    [ysize][xsize] squared cell distances (-1 everywhere: no occupied cell), nearest: int32 [ysize][xsize] row-major index of
+    the nearest occupied cell (the smallest among equals) or None.  Device tensors; asynchronous"""
+    check(lib().eea_distance_field(device, C.byref(cfg), _ptr(grid), _ptr(sq), _ptr(nearest), C.c_void_p(stream or 0)))
+
+
+def distance_query_batch(cfg, sq, nearest, pose, out=None, dmin=None, disp=None, device=0, stream=None):
+    """eea_distance_query_batch: the P poses pose [P][3] through a built field.  out: int32 [P][4] (msg incl.
+    COLLISION_OFF_GRID, sqrd_obs, dx, dy), dmin: float64 [P], disp: float64 [P][2]; each may be None, not all three; nearest may
+    be None when out and disp are.  Device tensors; asynchronous"""
+    check(lib().eea_distance_query_batch(device, C.byref(cfg), _ptr(sq), _ptr(nearest), _ptr(pose), int(pose.shape[0]), _ptr(out),
+                                         _ptr(dmin), _ptr(disp), C.c_void_p(stream or 0)))
+
+
+def distance_traj_min(cfg, sq, nearest, traj, out=None, step=None, dmin=None, device=0, stream=None):
+    """eea_distance_traj_min: the worst step of each of the B trajectories traj [B][T][3] through a built field.  out: int32
+    [B][4], step: int32 [B], dmin: float64 [B]; each may be None, not all three; nearest may be None when out is.  Device
+    tensors; asynchronous"""
+    check(lib().eea_distance_traj_min(device, C.byref(cfg), _ptr(sq), _ptr(nearest), _ptr(traj), int(traj.shape[0]),
+                                      int(traj.shape[1]), _ptr(out), _ptr(step), _ptr(dmin), C.c_void_p(stream or 0)))
 
 
 def release_collision_caches():

@@ -324,6 +324,22 @@ hipError_t launch_clearance(const CollisionParams& c, double boundary_radius, co
 // frees the cached visit-ordered offsets and key-map buffers of every device
 void release_clearance_caches();
 
+// ---- distance field: the exact Euclidean distance transform of the occupied cells (distance_kernel.hip) ----
+// the largest xsize / ysize: a row of the plane fits a workgroup's LDS; squared distances and cell indices fit an int
+constexpr unsigned kDistanceMaxSide = 8192;
+// d_sq [ysize][xsize]: squared cell distance to the nearest occupied cell (-1: the grid has none); d_nearest (may be null):
+// that cell's row-major index, the smallest among equals
+hipError_t launch_distance_field(const CollisionParams& c, const int8_t* d_grid, int* d_sq, int* d_nearest, hipStream_t s);
+// P poses [P][3] through a built field: d_out [P][4] ints (msg, sqrd_obs, dx, dy), d_dmin [P], d_disp [P][2]: each may be
+// null; d_nearest may be null when d_out and d_disp are
+hipError_t launch_distance_query(const CollisionParams& c, double boundary_radius, const int* d_sq, const int* d_nearest,
+                                 const double* d_pose, unsigned P, int* d_out, double* d_dmin, double* d_disp, hipStream_t s);
+// the worst step of each of B trajectories [B][T][3] (T >= 1): d_out [B][4], d_step [B], d_dmin [B]: each may be null;
+// d_nearest may be null when d_out is
+hipError_t launch_distance_traj_min(const CollisionParams& c, double boundary_radius, const int* d_sq, const int* d_nearest,
+                                    const double* d_traj, unsigned B, unsigned T, int* d_out, int* d_step, double* d_dmin,
+                                    hipStream_t s);
+
 // ---- fleet layer: robots as obstacles to one another (fleet_layer_kernel.hip, fleet_spans.hpp) ----
 // What the collision kernels read of a layer.  count [h][w] over the centres [-R, xsize + R) x [-R, ysize + R) (the geometry
 // of the inflated map with the layer's reach R = r_col + body): the number of stamped robots whose body a pose centred there

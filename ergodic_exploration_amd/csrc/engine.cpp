@@ -1946,6 +1946,68 @@ eea_status eea_clearance_field(int device, const eea_collision_cfg* cfg, const i
   return EEA_OK;
 }
 
+// ---- distance field: the exact Euclidean distance transform of the occupied cells (distance_kernel.hip) ----
+// the checks of the configuration the three distance calls share, before the device is selected
+static eea_status make_distance_params(const eea_collision_cfg* cfg, eea::CollisionParams& c)
+{
+  if (cfg != nullptr && !(cfg->resolution > 0.0)) return fail(EEA_ERR_INVALID_ARGUMENT, "the grid's resolution must be positive");
+  const eea_status st = make_collision_params(cfg, c);
+  if (st != EEA_OK) return st;
+  if (cfg->xsize == 0 || cfg->ysize == 0) return fail(EEA_ERR_INVALID_ARGUMENT, "the grid's xsize and ysize must be positive");
+  if (cfg->xsize > eea::kDistanceMaxSide || cfg->ysize > eea::kDistanceMaxSide) {
+    return fail(EEA_ERR_UNSUPPORTED, "the distance field takes grids of up to EEA_DISTANCE_MAX_SIDE cells per side");
+  }
+  return EEA_OK;
+}
+
+eea_status eea_distance_field(int device, const eea_collision_cfg* cfg, const int8_t* d_grid, int* d_sq, int* d_nearest, void* stream)
+{
+  eea::CollisionParams c;
+  const eea_status st = make_distance_params(cfg, c);
+  if (st != EEA_OK) return st;
+  if (d_grid == nullptr || d_sq == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  EEA_HIP(hipSetDevice(device));
+  EEA_HIP(eea::launch_distance_field(c, d_grid, d_sq, d_nearest, static_cast<hipStream_t>(stream)));
+  return EEA_OK;
+}
+
+eea_status eea_distance_query_batch(int device, const eea_collision_cfg* cfg, const int* d_sq, const int* d_nearest,
+                                    const double* d_pose, unsigned P, eea_clearance* d_out, double* d_dmin, double* d_disp,
+                                    void* stream)
+{
+  eea::CollisionParams c;
+  const eea_status st = make_distance_params(cfg, c);
+  if (st != EEA_OK) return st;
+  if (d_sq == nullptr || d_pose == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  if (d_out == nullptr && d_dmin == nullptr && d_disp == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "no output");
+  if (d_nearest == nullptr && (d_out != nullptr || d_disp != nullptr)) {
+    return fail(EEA_ERR_INVALID_ARGUMENT, "d_out and d_disp need the field's d_nearest");
+  }
+  if (P == 0) return EEA_OK;
+  EEA_HIP(hipSetDevice(device));
+  EEA_HIP(eea::launch_distance_query(c, cfg->boundary_radius, d_sq, d_nearest, d_pose, P, reinterpret_cast<int*>(d_out), d_dmin,
+                                     d_disp, static_cast<hipStream_t>(stream)));
+  return EEA_OK;
+}
+
+eea_status eea_distance_traj_min(int device, const eea_collision_cfg* cfg, const int* d_sq, const int* d_nearest,
+                                 const double* d_traj, unsigned B, unsigned T, eea_clearance* d_out, int* d_step, double* d_dmin,
+                                 void* stream)
+{
+  eea::CollisionParams c;
+  const eea_status st = make_distance_params(cfg, c);
+  if (st != EEA_OK) return st;
+  if (d_sq == nullptr || d_traj == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  if (d_out == nullptr && d_step == nullptr && d_dmin == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "no output");
+  if (d_nearest == nullptr && d_out != nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "d_out needs the field's d_nearest");
+  if (T == 0 || T > 0x7fffffffu) return fail(EEA_ERR_INVALID_ARGUMENT, "T must be between 1 and 2^31 - 1");
+  if (B == 0) return EEA_OK;
+  EEA_HIP(hipSetDevice(device));
+  EEA_HIP(eea::launch_distance_traj_min(c, cfg->boundary_radius, d_sq, d_nearest, d_traj, B, T, reinterpret_cast<int*>(d_out),
+                                        d_step, d_dmin, static_cast<hipStream_t>(stream)));
+  return EEA_OK;
+}
+
 void eea_release_collision_caches(void)
 {
   eea::release_collision_caches();

@@ -879,6 +879,47 @@ eea_status eea_clearance_batch(int device, const eea_collision_cfg* cfg, const i
 eea_status eea_clearance_field(int device, const eea_collision_cfg* cfg, const int8_t* d_grid, eea_clearance* d_field,
                                double* d_dmin, void* stream);
 
+/* ---- distance field: the exact Euclidean distance transform of the occupied cells ------------------------------------
+ * No reference counterpart (the reference README lists a distance field under "Future Improvements").  The ring search above
+ * has gaps, sees nothing inside r_bnd and nothing beyond r_max; these calls give the exact distance, in cells, from every
+ * cell to the nearest occupied in-grid cell -- not an approximation, a chamfer or a bounded search.  A cell is occupied by
+ * checkCell's test, !(int8 / 100.0 < occupied_threshold); cells come from world2Grid as everywhere else (x86 wrap included).
+ * They stand beside the reference-exact calls and change none of them.  All three are asynchronous on `stream`; the buffers
+ * are device memory; no cache is kept between calls.  eea_abi_version() stays 6.
+ * Before the device is selected, with no output touched -- EEA_ERR_INVALID_ARGUMENT: cfg or a required buffer null (each
+ * call lists its own); xsize or ysize 0; resolution <= 0; the configuration errors of the collision calls.
+ * EEA_ERR_UNSUPPORTED: xsize or ysize above EEA_DISTANCE_MAX_SIDE (a row of the field is held in a workgroup's LDS; squared
+ * distances (xsize-1)^2 + (ysize-1)^2 and cell indices xsize * ysize stay far inside int). */
+#define EEA_DISTANCE_MAX_SIDE 8192
+enum { EEA_COLLISION_OFF_GRID = 3 }; /* eea_clearance.msg of the distance queries: the pose's cell fails gridBounds */
+/* Build.  d_sq [ysize][xsize]: the squared cell distance from cell (i, j) to the nearest occupied cell; 0 on an occupied
+ * cell; -1 everywhere when the grid has no occupied cell.  d_nearest [ysize][xsize] (may be NULL): the row-major index of
+ * that cell, -1 when there is none; among occupied cells at the same squared distance the smallest index.  Integer minima
+ * throughout: bit-reproducible.  Required: cfg, d_grid, d_sq. */
+eea_status eea_distance_field(int device, const eea_collision_cfg* cfg, const int8_t* d_grid, int* d_sq, int* d_nearest,
+                              void* stream);
+/* P poses d_pose [P][3] through a built field; d_out [P], d_dmin [P], d_disp [P][2] may each be NULL, not all three;
+ * d_nearest may be NULL when d_out and d_disp are.  P == 0 is EEA_OK.  Required: cfg, d_sq, d_pose.  Per pose:
+ *   off the grid  msg 3 (EEA_COLLISION_OFF_GRID), sqrd_obs = -1, dx = dy = 0;  dmin = 0.0;      disp = (0, 0)
+ *   empty field   msg 2 (none),                   sqrd_obs = -1, dx = dy = 0;  dmin = DBL_MAX;  disp = (DBL_MAX, DBL_MAX)
+ *   sq <= r_col^2 msg 0 (crash)   }  sqrd_obs = sq, (dx, dy) = nearest cell - pose's cell,
+ *   otherwise     msg 1 (obstacle)}  dmin = sqrt((double)sq) * resolution - boundary_radius (a correctly rounded root, one
+ *                                    product, one difference; negative inside the bounding radius), disp = resolution * (dx, dy)
+ * Unlike eea_clearance_batch a crash keeps its real values (the field knows them), and there is no r_bnd and no r_max: every
+ * occupied cell counts at any distance.  Off the map is not free space: hence the message of its own and the conservative
+ * constants. */
+eea_status eea_distance_query_batch(int device, const eea_collision_cfg* cfg, const int* d_sq, const int* d_nearest,
+                                    const double* d_pose, unsigned P, eea_clearance* d_out, double* d_dmin, double* d_disp,
+                                    void* stream);
+/* The worst step of each of B trajectories d_traj [B][T][3] (the layout of eea_rollout_batch's output, eea_control_batch's
+ * d_traj and eea_tick_io.d_traj): the query's answer at that step (d_out [B], d_dmin [B]) and the step's index (d_step [B]);
+ * each may be NULL, not all three; d_nearest may be NULL when d_out is.  An off-grid step is worse than any on-grid one,
+ * among on-grid steps the smallest sq is worst, among equals the earliest step; an empty field gives none at step 0.
+ * Required: cfg, d_sq, d_traj.  T == 0 (or above 2^31 - 1) is EEA_ERR_INVALID_ARGUMENT, B == 0 is EEA_OK. */
+eea_status eea_distance_traj_min(int device, const eea_collision_cfg* cfg, const int* d_sq, const int* d_nearest,
+                                 const double* d_traj, unsigned B, unsigned T, eea_clearance* d_out, int* d_step, double* d_dmin,
+                                 void* stream);
+
 /* The collision / DWA / tick / clearance calls keep small device caches between calls (the ring offsets per radii, one
  * inflated-map and one key-map buffer per (device, stream), the span tables of fleet layers that no layer holds any more).  A long-running
  * process that changes streams or map sizes can drop them; synchronises the devices involved.  No reference counterpart. */
