@@ -16,6 +16,7 @@
 //               built by scatter (the occupied cells atomicMin their key into every centre that reaches them); a query is
 //               one load.  The buffers are kept per (device, stream) like the inflated map's.
 // Which form a call takes: use_key_map below (measured: profiles/clearance.txt).
+#include <array>
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
@@ -24,14 +25,17 @@
 
 #include "../../include/ergodic_amd.h"
 #include "common.hpp"
-#include "grid_cell.hpp"      // world_to_grid (grid.cpp:143-159)
+#include "grid_cell.hpp"      // world_to_grid (grid.cpp:143-159), occupied, write_answer
 #include "hit_map_table.hpp"  // clearance_walk, kNoClearanceKey, HitMapTable
+#include "device_tables.hpp"  // DeviceTables: the walk kept per device
+#include "grid_buffers.hpp"   // upload_block, acquire_map_buffer, launch_then_free
 
 namespace eea
 {
 namespace
 {
-// the walk on the device: off [n] in visit order, root [n] = sqrt((double)|d_k|^2) as the host's IEEE sqrt gives it
+// the walk on the device: off [n] in visit order, root [n] = sqrt((double)|d_k|^2) as the host's IEEE sqrt gives it (one
+// allocation: the doubles first)
 struct ClearTable
 {
   const short2* off = nullptr;
@@ -68,40 +72,29 @@ __device__ __forceinline__ void clearance_centre(const CollisionParams& c, const
   }
 }
 
-// collision.cpp:79-92 and :107-123 from the smallest key of centre q
-__device__ __forceinline__ void store_clearance(const CollisionParams& c, const ClearTable& t, double boundary_radius,
-                                                unsigned key, size_t q, const ClearOut& o)
+// collision.cpp:79-92 and :107-123 from the smallest key of a centre
+__device__ __forceinline__ ClearanceAnswer clearance_answer(const CollisionParams& c, const ClearTable& t, double boundary_radius,
+                                                            unsigned key)
 {
-  int msg = EEA_COLLISION_NONE, sq = -1, dx = 0, dy = 0;
-  double dmin = DBL_MAX, d0 = DBL_MAX, d1 = DBL_MAX;
+  ClearanceAnswer a{ EEA_COLLISION_NONE, -1, 0, 0, DBL_MAX, DBL_MAX, DBL_MAX };
   if (key != kNoClearanceKey) {
     const unsigned ksq = key / static_cast<unsigned>(t.n), k = key - ksq * static_cast<unsigned>(t.n);
     if (static_cast<int>(ksq) <= c.r_col * c.r_col) {  // collision.cpp:239
-      msg = EEA_COLLISION_CRASH;
-      sq = 0;
-      dmin = d0 = d1 = 0.0;
+      a.msg = EEA_COLLISION_CRASH;
+      a.sq = 0;
+      a.dmin = a.d0 = a.d1 = 0.0;
     } else {
       const short2 d = t.off[k];
-      msg = EEA_COLLISION_OBSTACLE;
-      sq = static_cast<int>(ksq);
-      dx = d.x;
-      dy = d.y;
-      dmin = t.root[k] * c.resolution - boundary_radius;  // collision.cpp:86-87
-      d0 = c.resolution * static_cast<double>(dx);         // collision.cpp:116-117
-      d1 = c.resolution * static_cast<double>(dy);
+      a.msg = EEA_COLLISION_OBSTACLE;
+      a.sq = static_cast<int>(ksq);
+      a.dx = d.x;
+      a.dy = d.y;
+      a.dmin = t.root[k] * c.resolution - boundary_radius;  // collision.cpp:86-87
+      a.d0 = c.resolution * static_cast<double>(a.dx);       // collision.cpp:116-117
+      a.d1 = c.resolution * static_cast<double>(a.dy);
     }
   }
-  if (o.out != nullptr) {
-    o.out[4 * q] = msg;
-    o.out[4 * q + 1] = sq;
-    o.out[4 * q + 2] = dx;
-    o.out[4 * q + 3] = dy;
-  }
-  if (o.dmin != nullptr) o.dmin[q] = dmin;
-  if (o.disp != nullptr) {
-    o.disp[2 * q] = d0;
-    o.disp[2 * q + 1] = d1;
-  }
+  return a;
 }
 
 // ring form: wavefront q / 64 of the launch answers centre q / 64
@@ -122,8 +115,7 @@ __global__ __launch_bounds__(kBlock) void clearance_ring_kernel(const CollisionP
     const unsigned cj = static_cast<unsigned>(cx) + static_cast<unsigned>(static_cast<int>(d.x));
     const unsigned ci = static_cast<unsigned>(cy) + static_cast<unsigned>(static_cast<int>(d.y));
     if ((ci <= c.ysize - 1u) && (cj <= c.xsize - 1u)) {
-      const double cell = static_cast<double>(grid[ci * c.xsize + cj]) / 100.0;  // grid.cpp:177-184
-      if (!(cell < c.occupied_threshold)) {
+      if (occupied(c, grid[ci * c.xsize + cj])) {
         const unsigned key = static_cast<unsigned>(d.x * d.x + d.y * d.y) * static_cast<unsigned>(t.n) + static_cast<unsigned>(k);
         best = key < best ? key : best;  // (k ascends within a lane)
       }
@@ -134,11 +126,10 @@ __global__ __launch_bounds__(kBlock) void clearance_ring_kernel(const CollisionP
     const unsigned other = __shfl_xor(best, m, kWave);
     best = other < best ? other : best;
   }
-  if (lane == 0) store_clearance(c, t, boundary_radius, best, q, o);
+  if (lane == 0) write_answer(o.out, o.dmin, o.disp, q, clearance_answer(c, t, boundary_radius, best));
 }
 
-// map form, build: occupied cells put their key into every centre that reaches them (the block lists its occupied cells,
-// then all its threads walk the offsets of each listed cell together, as inflate_kernel does)
+// map form, build: occupied cells put their key into every centre that reaches them (listed and walked as in inflate_kernel)
 __global__ __launch_bounds__(kBlock) void clearance_scatter_kernel(const CollisionParams c, const int8_t* __restrict__ grid,
                                                                    const ClearTable t, unsigned* __restrict__ keys, int R,
                                                                    long long w)
@@ -149,10 +140,7 @@ __global__ __launch_bounds__(kBlock) void clearance_scatter_kernel(const Collisi
   __syncthreads();
   const size_t q = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
   const size_t n = static_cast<size_t>(c.xsize) * c.ysize;
-  if (q < n) {
-    const double cell = static_cast<double>(grid[q]) / 100.0;
-    if (!(cell < c.occupied_threshold)) s_list[atomicAdd(&s_n, 1u)] = threadIdx.x;
-  }
+  if (q < n && occupied(c, grid[q])) s_list[atomicAdd(&s_n, 1u)] = threadIdx.x;
   __syncthreads();
   const unsigned cnt = s_n;
   for (unsigned l = 0; l < cnt; ++l) {
@@ -183,32 +171,35 @@ __global__ __launch_bounds__(kBlock) void clearance_map_kernel(const CollisionPa
   const long long hx = static_cast<long long>(cx) + m.R, hy = static_cast<long long>(cy) + m.R;
   unsigned key = kNoClearanceKey;
   if (hx >= 0 && hy >= 0 && hx < m.w && hy < m.h) key = m.keys[static_cast<size_t>(hy * m.w + hx)];
-  store_clearance(c, t, boundary_radius, key, q, o);
+  write_answer(o.out, o.dmin, o.disp, q, clearance_answer(c, t, boundary_radius, key));
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------
-// The walk depends on two small integers: enumerated once per (r_bnd, r_max) and kept, with the verdict on its key.
+// The walk depends on two small integers: enumerated once per (r_bnd, r_max) and kept, with the verdict on its key; its copy
+// in a device's memory once per (device, r_bnd, r_max).
+using WalkKey = std::array<int, 2>;  // r_bnd, r_max
 struct WalkEntry
 {
-  int r_bnd, r_max;
+  WalkKey key;
   bool fits;
   ClearanceWalk walk;
 };
-struct TableEntry
+struct DeviceWalk
 {
-  int device, r_bnd, r_max, reach;
   ClearTable t;
+  int reach;
 };
 std::mutex g_walk_mutex;  // guards both lists
 std::vector<WalkEntry> g_walks;
-std::vector<TableEntry> g_tables;
+DeviceTables<WalkKey, DeviceWalk> g_tables;
 
 const WalkEntry& host_walk(const CollisionParams& c)  // (g_walk_mutex held; the reference stays valid until the next call)
 {
+  const WalkKey key{ c.r_bnd, c.r_max };
   for (const WalkEntry& e : g_walks) {
-    if (e.r_bnd == c.r_bnd && e.r_max == c.r_max) return e;
+    if (e.key == key) return e;
   }
-  WalkEntry e{ c.r_bnd, c.r_max, false, {} };
+  WalkEntry e{ key, false, {} };
   e.fits = clearance_walk(c.r_bnd, c.r_max, e.walk);
   if (!e.fits) e.walk = ClearanceWalk{};
   g_walks.push_back(std::move(e));
@@ -218,41 +209,25 @@ const WalkEntry& host_walk(const CollisionParams& c)  // (g_walk_mutex held; the
 hipError_t device_table(int device, const CollisionParams& c, ClearTable& t, int& reach)
 {
   std::lock_guard<std::mutex> lock(g_walk_mutex);
-  for (const TableEntry& e : g_tables) {
-    if (e.device == device && e.r_bnd == c.r_bnd && e.r_max == c.r_max) {
-      t = e.t;
-      reach = e.reach;
-      return hipSuccess;
-    }
-  }
-  const WalkEntry& we = host_walk(c);
-  if (!we.fits) return hipErrorInvalidValue;
-  const size_t n = we.walk.offsets.size();
-  TableEntry ent{ device, c.r_bnd, c.r_max, we.walk.reach, ClearTable{} };
-  ent.t.n = static_cast<int>(n);
-  if (n > 0) {
+  const DeviceTables<WalkKey, DeviceWalk>::Entry* ent = g_tables.find(device, WalkKey{ c.r_bnd, c.r_max });
+  if (ent == nullptr) {
+    const WalkEntry& we = host_walk(c);
+    if (!we.fits) return hipErrorInvalidValue;
+    const size_t n = we.walk.offsets.size();
     std::vector<double> root(n);
     for (size_t k = 0; k < n; ++k) {
       const short2 d = we.walk.offsets[k];
       root[k] = std::sqrt(static_cast<double>(d.x * d.x + d.y * d.y));
     }
-    short2* d_off = nullptr;
-    double* d_root = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_off), n * sizeof(short2));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_root), n * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(d_off, we.walk.offsets.data(), n * sizeof(short2), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_root, root.data(), n * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-      if (d_off) (void)hipFree(d_off);
-      if (d_root) (void)hipFree(d_root);
-      return e;
-    }
-    ent.t.off = d_off;
-    ent.t.root = d_root;
+    void* block = nullptr;  // (one allocation: the doubles first)
+    const hipError_t e = upload_block(root.data(), n * sizeof(double), we.walk.offsets.data(), n * sizeof(short2), &block);
+    if (e != hipSuccess) return e;
+    const double* const d_root = static_cast<const double*>(block);
+    const ClearTable table{ reinterpret_cast<const short2*>(d_root + n), d_root, static_cast<int>(n) };
+    ent = &g_tables.insert(device, we.key, block, DeviceWalk{ n > 0 ? table : ClearTable{}, we.walk.reach });
   }
-  g_tables.push_back(ent);
-  t = ent.t;
-  reach = ent.reach;
+  t = ent->view.t;
+  reach = ent->view.reach;
   return hipSuccess;
 }
 
@@ -266,32 +241,24 @@ hipError_t build_key_map(const CollisionParams& c, const ClearTable& t, int reac
 {
   const long long w = static_cast<long long>(c.xsize) + 2 * reach, h = static_cast<long long>(c.ysize) + 2 * reach;
   const size_t bytes = static_cast<size_t>(w) * static_cast<size_t>(h) * sizeof(unsigned);
-  void* cells = nullptr;
+  MapBuffer b;
+  hipError_t e;
   {
-    std::lock_guard<std::mutex> lock(g_key_maps_mutex);
-    const HitMapPlan p = g_key_maps.plan(device, s, bytes, nullptr, 0, c);
-    cells = p.cells;
-    if (p.slot < 0) {
-      const hipError_t e = hipMallocAsync(&async_cells, bytes, s);
-      if (e != hipSuccess) return e;
-      cells = async_cells;
-    } else if (p.reallocate) {
-      if (p.cells) (void)hipFree(p.cells);  // waits for the kernels that still use it (the slot has forgotten it already)
-      const hipError_t e = hipMalloc(&cells, bytes);
-      if (e != hipSuccess) return e;
-      g_key_maps.allocated(p.slot, cells, bytes);
-    }
+    std::lock_guard<std::mutex> lock(g_key_maps_mutex);  // (for the plan and the allocation only)
+    e = acquire_map_buffer(g_key_maps, device, s, bytes, nullptr, 0, c, b);
   }
-  hipError_t e = hipMemsetAsync(cells, 0xff, bytes, s);  // kNoClearanceKey in every word
+  async_cells = b.async_cells;
+  if (e != hipSuccess) return e;
+  e = hipMemsetAsync(b.cells, 0xff, bytes, s);  // kNoClearanceKey in every word
   if (e != hipSuccess) return e;
   if (t.n > 0) {
     const size_t n = static_cast<size_t>(c.xsize) * c.ysize;
     hipLaunchKernelGGL(clearance_scatter_kernel, dim3(static_cast<unsigned>((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, c,
-                       d_grid, t, static_cast<unsigned*>(cells), reach, w);
+                       d_grid, t, static_cast<unsigned*>(b.cells), reach, w);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
-  map = KeyMap{ static_cast<const unsigned*>(cells), reach, w, h };
+  map = KeyMap{ static_cast<const unsigned*>(b.cells), reach, w, h };
   return hipSuccess;
 }
 
@@ -341,43 +308,29 @@ hipError_t launch_clearance(const CollisionParams& c, double boundary_radius, co
   const ClearOut o{ d_out, d_dmin, d_disp };
   if (!use_key_map(n, c, t, reach)) {
     const dim3 blocks(static_cast<unsigned>((n + kBlock / kWave - 1) / (kBlock / kWave)));
-    if (field) hipLaunchKernelGGL(clearance_ring_kernel<true>, blocks, dim3(kBlock), 0, s, c, t, boundary_radius, d_grid, d_pose, n, o);
-    else hipLaunchKernelGGL(clearance_ring_kernel<false>, blocks, dim3(kBlock), 0, s, c, t, boundary_radius, d_grid, d_pose, n, o);
+    const auto ring = field ? clearance_ring_kernel<true> : clearance_ring_kernel<false>;
+    hipLaunchKernelGGL(ring, blocks, dim3(kBlock), 0, s, c, t, boundary_radius, d_grid, d_pose, n, o);
     return hipGetLastError();
   }
   KeyMap map;
   void* async_cells = nullptr;
   e = build_key_map(c, t, reach, d_grid, device, s, map, async_cells);
-  if (e == hipSuccess) {
-    const dim3 blocks(static_cast<unsigned>((n + kBlock - 1) / kBlock));
-    if (field) hipLaunchKernelGGL(clearance_map_kernel<true>, blocks, dim3(kBlock), 0, s, c, t, boundary_radius, map, d_pose, n, o);
-    else hipLaunchKernelGGL(clearance_map_kernel<false>, blocks, dim3(kBlock), 0, s, c, t, boundary_radius, map, d_pose, n, o);
-    e = hipGetLastError();
-  }
-  if (async_cells) (void)hipFreeAsync(async_cells, s);
-  return e;
+  return launch_then_free(e, async_cells, s, [&] {
+    const auto query = field ? clearance_map_kernel<true> : clearance_map_kernel<false>;
+    hipLaunchKernelGGL(query, dim3(static_cast<unsigned>((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, c, t, boundary_radius, map,
+                       d_pose, n, o);
+  });
 }
 
 void release_clearance_caches()
 {
-  int current = 0;
-  const bool have_device = hipGetDevice(&current) == hipSuccess;
+  const CurrentDeviceGuard guard;
   {
     std::lock_guard<std::mutex> lock(g_key_maps_mutex);
-    g_key_maps.release([](int device, void* cells) {
-      if (hipSetDevice(device) == hipSuccess) (void)hipFree(cells);  // waits for its users
-    });
+    g_key_maps.release(free_on_device);
   }
-  {
-    std::lock_guard<std::mutex> lock(g_walk_mutex);
-    for (TableEntry& e : g_tables) {
-      if (hipSetDevice(e.device) != hipSuccess) continue;
-      if (e.t.off != nullptr) (void)hipFree(const_cast<short2*>(e.t.off));
-      if (e.t.root != nullptr) (void)hipFree(const_cast<double*>(e.t.root));
-    }
-    g_tables.clear();
-    g_walks.clear();
-  }
-  if (have_device) (void)hipSetDevice(current);
+  std::lock_guard<std::mutex> lock(g_walk_mutex);
+  g_tables.release(free_on_device);
+  g_walks.clear();
 }
 }  // namespace eea

@@ -10,6 +10,7 @@
 // the occupied cells scatter a 1 to every centre that would see them, and a collision check becomes
 // one byte lookup (a robot centred inside a small obstacle still reports no collision: cells closer
 // than r_bnd are not in the set, as in the reference).
+#include <array>
 #include <cstdint>
 #include <cstdlib>
 #include <mutex>
@@ -18,8 +19,10 @@
 
 #include "../../include/ergodic_amd.h"
 #include "common.hpp"
-#include "grid_cell.hpp"      // cast_u32_x86, world_to_grid (grid.cpp:143-159): shared with sense_kernel.hip
+#include "grid_cell.hpp"      // cast_u32_x86, world_to_grid (grid.cpp:143-159), occupied
 #include "hit_map_table.hpp"  // ring_offsets, HitMapTable: the host-side policy of the inflated map
+#include "device_tables.hpp"  // DeviceTables: ... and of the offset lists kept per device
+#include "grid_buffers.hpp"   // upload_block, acquire_map_buffer, launch_then_free: the effects of both
 #include "fleet_spans.hpp"    // FleetSpan: the row spans of the fleet layer's offset set
 
 namespace eea
@@ -36,8 +39,7 @@ __device__ __forceinline__ bool check_cell(const CollisionParams& c, const int8_
                                            RingState& st, unsigned cj, unsigned ci)
 {
   if ((ci <= c.ysize - 1u) && (cj <= c.xsize - 1u)) {
-    const double cell = static_cast<double>(grid[ci * c.xsize + cj]) / 100.0;
-    if (!(cell < c.occupied_threshold)) {
+    if (occupied(c, grid[ci * c.xsize + cj])) {
       const unsigned ddx = static_cast<unsigned>(st.cx) - cj, ddy = static_cast<unsigned>(st.cy) - ci;
       const int sq = static_cast<int>(ddx * ddx + ddy * ddy);
       if (sq < st.sqrd_obs || st.sqrd_obs == -1) st.sqrd_obs = sq;
@@ -170,10 +172,7 @@ __global__ __launch_bounds__(kBlock) void inflate_kernel(const CollisionParams c
   __syncthreads();
   const size_t q = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
   const size_t n = static_cast<size_t>(c.xsize) * c.ysize;
-  if (q < n) {
-    const double cell = static_cast<double>(grid[q]) / 100.0;  // GridMap::getCell, grid.cpp:177-184
-    if (!(cell < c.occupied_threshold)) s_list[atomicAdd(&s_n, 1u)] = threadIdx.x;  // checkCell tests !(cell < threshold)
-  }
+  if (q < n && occupied(c, grid[q])) s_list[atomicAdd(&s_n, 1u)] = threadIdx.x;
   __syncthreads();
   const unsigned cnt = s_n;
   for (unsigned k = 0; k < cnt; ++k) {
@@ -515,41 +514,34 @@ __global__ __launch_bounds__(256) void tick_begin_kernel(int* __restrict__ follo
 
 namespace
 {
-// The offset list depends on three small integers only: built once per (device, radii) and kept for
-// the life of the process (a few KB), so that building a map needs no host synchronisation.
-struct OffsetEntry
+// The offset list depends on three small integers only: built once per (device, radii) and kept until
+// release_collision_caches (a few KB), so that building a map needs no host synchronisation.
+using RingKey = std::array<int, 3>;  // r_bnd, r_col, r_max
+struct RingTable
 {
-  int device, r_bnd, r_col, r_max, n;
-  short2* d_offsets;
+  const short2* offsets = nullptr;
+  int n = 0;
 };
 std::mutex g_offsets_mutex;
-std::vector<OffsetEntry> g_offsets;
+DeviceTables<RingKey, RingTable> g_offsets;
 
-hipError_t device_offsets(int device, const CollisionParams& c, const short2** d_out, int* n_out)
+hipError_t device_offsets(int device, const CollisionParams& c, RingTable& t)
 {
   std::lock_guard<std::mutex> lock(g_offsets_mutex);
-  for (const OffsetEntry& o : g_offsets) {
-    if (o.device == device && o.r_bnd == c.r_bnd && o.r_col == c.r_col && o.r_max == c.r_max) {
-      *d_out = o.d_offsets;
-      *n_out = o.n;
-      return hipSuccess;
-    }
+  const RingKey key{ c.r_bnd, c.r_col, c.r_max };
+  if (const auto* hit = g_offsets.find(device, key)) {
+    t = hit->view;
+    return hipSuccess;
   }
   const std::vector<short2> off = ring_offsets(c.r_bnd, c.r_col, c.r_max);
-  OffsetEntry ent{ device, c.r_bnd, c.r_col, c.r_max, static_cast<int>(off.size()), nullptr };
-  if (!off.empty()) {
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&ent.d_offsets), off.size() * sizeof(short2));
-    if (e != hipSuccess) return e;
-    e = hipMemcpy(ent.d_offsets, off.data(), off.size() * sizeof(short2), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return e;
-  }
-  g_offsets.push_back(ent);
-  *d_out = ent.d_offsets;
-  *n_out = ent.n;
+  void* block = nullptr;
+  const hipError_t e = upload_block(off.data(), off.size() * sizeof(short2), nullptr, 0, &block);
+  if (e != hipSuccess) return e;
+  t = g_offsets.insert(device, key, block, RingTable{ static_cast<const short2*>(block), static_cast<int>(off.size()) }).view;
   return hipSuccess;
 }
 
-// the map buffers kept between calls: the policy is HitMapTable's (hit_map_table.hpp), the effects are build_hit_map's
+// the map buffers kept between calls: the policy is HitMapTable's (hit_map_table.hpp), the effects are acquire_map_buffer's
 std::mutex g_maps_mutex;
 HitMapTable g_maps;
 
@@ -560,43 +552,35 @@ hipError_t build_hit_map(const CollisionParams& c, const int8_t* d_grid, hipStre
                          void*& async_cells)
 {
   if (c.r_col < 0 || c.r_col > 8192 || c.r_max < c.r_bnd) return hipErrorInvalidValue;
-  int device = 0, n_off = 0;
-  const short2* d_off = nullptr;
+  int device = 0;
+  RingTable ring;
   hipError_t e = hipGetDevice(&device);
-  if (e == hipSuccess) e = device_offsets(device, c, &d_off, &n_off);
+  if (e == hipSuccess) e = device_offsets(device, c, ring);
   if (e != hipSuccess) return e;
   const int R = c.r_col;
   const int w = static_cast<int>(c.xsize) + 2 * R, h = static_cast<int>(c.ysize) + 2 * R;
-  const size_t bytes = static_cast<size_t>(w) * h;
 
-  std::lock_guard<std::mutex> lock(g_maps_mutex);
-  const HitMapPlan p = g_maps.plan(device, s, bytes, d_grid, epoch, c);
-  void* cells = p.cells;
-  if (p.slot < 0) {
-    e = hipMallocAsync(&async_cells, bytes, s);
-    if (e != hipSuccess) return e;
-    cells = async_cells;
-  } else if (p.reallocate) {
-    if (p.cells) (void)hipFree(p.cells);  // waits for the kernels that still use it
-    e = hipMalloc(&cells, bytes);
-    if (e != hipSuccess) return e;
-    g_maps.allocated(p.slot, cells, bytes);
-  }
+  std::lock_guard<std::mutex> lock(g_maps_mutex);  // (held through the launch and built())
+  MapBuffer b;
+  e = acquire_map_buffer(g_maps, device, s, static_cast<size_t>(w) * h, d_grid, epoch, c, b);
+  async_cells = b.async_cells;
+  if (e != hipSuccess) return e;
+  const HitMapPlan& p = b.plan;
   if (p.clear) {
-    e = hipMemsetAsync(cells, 0, p.cap, s);
+    e = hipMemsetAsync(b.cells, 0, p.cap, s);
     if (e != hipSuccess) return e;
   }
   if (!p.reuse) {
-    if (n_off > 0) {
+    if (ring.n > 0) {
       const size_t n = static_cast<size_t>(c.xsize) * c.ysize;
       hipLaunchKernelGGL(inflate_kernel, dim3(static_cast<unsigned>((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, c,
-                         d_grid, d_off, n_off, static_cast<uint8_t*>(cells), R, w, static_cast<uint8_t>(p.stamp));
+                         d_grid, ring.offsets, ring.n, static_cast<uint8_t*>(b.cells), R, w, static_cast<uint8_t>(p.stamp));
       e = hipGetLastError();
       if (e != hipSuccess) return e;
     }
     if (p.slot >= 0) g_maps.built(p, d_grid, epoch, c);
   }
-  map = HitMap{ static_cast<const uint8_t*>(cells), R, w, h, static_cast<uint8_t>(p.stamp) };
+  map = HitMap{ static_cast<const uint8_t*>(b.cells), R, w, h, static_cast<uint8_t>(p.stamp) };
   return hipSuccess;
 }
 
@@ -627,13 +611,8 @@ hipError_t with_map_or_ring(size_t poses, unsigned sequential_steps, const Colli
   }
   HitMap map;
   void* async_cells = nullptr;
-  hipError_t e = build_hit_map(c, d_grid, s, epoch, map, async_cells);
-  if (e == hipSuccess) {
-    launch(map, std::true_type{});
-    e = hipGetLastError();
-  }
-  if (async_cells) (void)hipFreeAsync(async_cells, s);
-  return e;
+  const hipError_t built = build_hit_map(c, d_grid, s, epoch, map, async_cells);
+  return launch_then_free(built, async_cells, s, [&] { launch(map, std::true_type{}); });
 }
 
 // launch geometry of dwa_control_kernel: one lane per velocity sample -- a single wavefront when the window has at most 64
@@ -652,22 +631,13 @@ struct DwaGeometry
 
 void release_collision_caches()
 {
-  int current = 0;
-  const bool have_device = hipGetDevice(&current) == hipSuccess;
+  const CurrentDeviceGuard guard;
   {
     std::lock_guard<std::mutex> lock(g_maps_mutex);
-    g_maps.release([](int device, void* cells) {
-      if (hipSetDevice(device) == hipSuccess) (void)hipFree(cells);  // waits for its users
-    });
+    g_maps.release(free_on_device);
   }
-  {
-    std::lock_guard<std::mutex> lock(g_offsets_mutex);
-    for (OffsetEntry& o : g_offsets) {
-      if (o.d_offsets != nullptr && hipSetDevice(o.device) == hipSuccess) (void)hipFree(o.d_offsets);
-    }
-    g_offsets.clear();
-  }
-  if (have_device) (void)hipSetDevice(current);
+  std::lock_guard<std::mutex> lock(g_offsets_mutex);
+  g_offsets.release(free_on_device);
 }
 
 hipError_t launch_dwa_control(const CollisionParams& c, const DwaParams& d, const int8_t* d_grid,

@@ -285,6 +285,22 @@ struct CollisionParams
   int r_bnd, r_col, r_max;
   double occupied_threshold;
 };
+// the same grid, radii and threshold, field by field
+inline bool same_params(const CollisionParams& a, const CollisionParams& b)
+{
+  return a.xmin == b.xmin && a.ymin == b.ymin && a.resolution == b.resolution && a.xsize == b.xsize && a.ysize == b.ysize &&
+         a.r_bnd == b.r_bnd && a.r_col == b.r_col && a.r_max == b.r_max && a.occupied_threshold == b.occupied_threshold;
+}
+// checkCell's test !(cell / 100.0 < occupied_threshold) on getCell (collision.cpp:216-243, grid.cpp:177-184) as an integer
+// cutoff, for the kernels that take it as one: the smallest int8 value v that passes it (the quotient does not fall as v
+// rises, so the occupied values are an upper range of int8); 128: none does
+inline int blocking_cutoff(double occupied_threshold)
+{
+  for (int v = -128; v <= 127; ++v) {
+    if (!(static_cast<double>(v) / 100.0 < occupied_threshold)) return v;
+  }
+  return 128;
+}
 hipError_t launch_collision_check(const CollisionParams& c, const int8_t* d_grid,
                                   const double* d_pose, unsigned P, int* d_hit, hipStream_t s);
 // integrate_twist (numerics.hpp:273-297) per pose; wrap: the heading normalised to [-pi, pi) afterwards
@@ -357,10 +373,11 @@ struct FleetView
   unsigned B = 0;
 };
 // The span table of (radii, body) in the memory of `device`, built once and shared by the layers that use it.
-// release_fleet_spans: a layer gives its table back; release_fleet_span_cache frees the tables no layer holds.
+// release_fleet_spans: a layer gives its table (named by d_row_start, the start of its allocation) back;
+// release_fleet_span_cache frees the tables no layer holds.
 hipError_t acquire_fleet_spans(int device, const CollisionParams& c, int body, const int** d_row_start, const FleetSpan** d_spans,
                                int* n_spans);
-void release_fleet_spans(int device, const FleetSpan* d_spans);
+void release_fleet_spans(int device, const int* d_row_start);
 void release_fleet_span_cache();
 // One update, three stream operations and no host wait: clear the difference map, one wavefront per robot stamps +1 / -1 at
 // the ends of its spans (and records its cell), a prefix sum along every row.  d_mask may be null (every robot is active)
@@ -383,8 +400,7 @@ hipError_t launch_sense_reveal(const CollisionParams& c, unsigned range_cells, c
                                const double* d_pose, const int* d_mask, unsigned P, int* d_ranges, hipStream_t s);
 // d_counts[3] = cells < 0, cells >= 0 below the occupied threshold, blocking cells of d_grid [ysize][xsize]
 hipError_t launch_grid_census(const CollisionParams& c, const int8_t* d_grid, unsigned long long* d_counts, hipStream_t s);
-// the smallest int8 value v with !(v / 100.0 < occupied_threshold) (128: none): a cell blocks a ray iff cell >= that
-int blocking_cutoff(double occupied_threshold);
+// (a cell blocks a ray iff cell >= blocking_cutoff(occupied_threshold), above)
 
 // ---- information-gain field of a known grid (gain_kernel.hip) -----------------------------
 // d_gain [ysize][xsize] = per candidate cell (both indices multiples of stride, the cell not blocking) the unknown cells the

@@ -26,7 +26,7 @@
 
 #include "../../include/ergodic_amd.h"
 #include "common.hpp"
-#include "grid_cell.hpp"  // world_to_grid (grid.cpp:143-159)
+#include "grid_cell.hpp"  // world_to_grid (grid.cpp:143-159), ClearanceAnswer, write_answer
 
 namespace eea
 {
@@ -42,7 +42,7 @@ static_assert(2ll * (kDistanceMaxSide - 1) * (kDistanceMaxSide - 1) < INT32_MAX,
 static_assert(static_cast<long long>(kDistanceMaxSide) * kDistanceMaxSide < INT32_MAX, "a cell's index fits an int");
 static_assert(kDistanceMaxSide * sizeof(int) <= 64 * 1024, "a row of dy fits a workgroup's LDS");
 
-// column pass: plane [ysize][xsize] <- dy.  occupied: cell >= v_min (distance_v_min below: checkCell's test as an integer)
+// column pass: plane [ysize][xsize] <- dy.  occupied: cell >= v_min (blocking_cutoff, common.hpp: checkCell's test as an integer)
 __global__ __launch_bounds__(kColumns* kStrips) void distance_columns_kernel(const int8_t* __restrict__ grid, int xsize, int ysize,
                                                                             int v_min, int* __restrict__ plane)
 {
@@ -141,13 +141,6 @@ struct DistanceField
   const int* nearest;  // may be null when no output needs the cell
 };
 
-// the answer of one pose's cell: what eea_distance_query_batch documents
-struct DistanceAnswer
-{
-  int msg, sq, dx, dy;
-  double dmin, d0, d1;
-};
-
 // sqrt of a positive integer below 2^31, correctly rounded: the device's sqrt followed by one Markstein step (the residual
 // x - r * r is exact in an fma; r + residual / (2 r) then rounds to the correctly rounded root whenever r was within an
 // ulp of it, and leaves a correctly rounded r as it is)
@@ -157,10 +150,11 @@ __device__ __forceinline__ double sqrt_rn(double x)
   return fma(fma(-r, r, x), 0.5 / r, r);
 }
 
-__device__ __forceinline__ DistanceAnswer distance_answer(const CollisionParams& c, double boundary_radius, const DistanceField& f,
-                                                          unsigned j, unsigned i, bool want_cell)
+// the answer of one pose's cell: what eea_distance_query_batch documents
+__device__ __forceinline__ ClearanceAnswer distance_answer(const CollisionParams& c, double boundary_radius, const DistanceField& f,
+                                                           unsigned j, unsigned i, bool want_cell)
 {
-  DistanceAnswer a{ EEA_COLLISION_OFF_GRID, -1, 0, 0, 0.0, 0.0, 0.0 };
+  ClearanceAnswer a{ EEA_COLLISION_OFF_GRID, -1, 0, 0, 0.0, 0.0, 0.0 };
   if (!((i <= c.ysize - 1u) && (j <= c.xsize - 1u))) return a;  // gridBounds (grid.cpp:96-100)
   const size_t at = static_cast<size_t>(i) * c.xsize + j;
   const int sq = f.sq[at];
@@ -192,18 +186,7 @@ __global__ __launch_bounds__(kBlock) void distance_query_kernel(const CollisionP
   if (q >= P) return;
   unsigned j, i;
   world_to_grid(c, pose[3 * q], pose[3 * q + 1], j, i);
-  const DistanceAnswer a = distance_answer(c, boundary_radius, f, j, i, out != nullptr || disp != nullptr);
-  if (out != nullptr) {
-    out[4 * q] = a.msg;
-    out[4 * q + 1] = a.sq;
-    out[4 * q + 2] = a.dx;
-    out[4 * q + 3] = a.dy;
-  }
-  if (dmin != nullptr) dmin[q] = a.dmin;
-  if (disp != nullptr) {
-    disp[2 * q] = a.d0;
-    disp[2 * q + 1] = a.d1;
-  }
+  write_answer(out, dmin, disp, q, distance_answer(c, boundary_radius, f, j, i, out != nullptr || disp != nullptr));
 }
 
 // one wavefront per trajectory: lanes take the steps lane, lane + 64, ...; the worst step is the smallest key
@@ -238,25 +221,8 @@ __global__ __launch_bounds__(kBlock) void distance_traj_min_kernel(const Collisi
   const unsigned t = static_cast<unsigned>(best & 0xffffffffull);
   unsigned j, i;
   world_to_grid(c, x[3 * static_cast<size_t>(t)], x[3 * static_cast<size_t>(t) + 1], j, i);
-  const DistanceAnswer a = distance_answer(c, boundary_radius, f, j, i, out != nullptr);
-  if (out != nullptr) {
-    out[4 * b] = a.msg;
-    out[4 * b + 1] = a.sq;
-    out[4 * b + 2] = a.dx;
-    out[4 * b + 3] = a.dy;
-  }
+  write_answer(out, dmin, nullptr, b, distance_answer(c, boundary_radius, f, j, i, out != nullptr));
   if (step != nullptr) step[b] = static_cast<int>(t);
-  if (dmin != nullptr) dmin[b] = a.dmin;
-}
-
-// checkCell's test !(cell / 100.0 < occupied_threshold) (grid.cpp:177-184) as cell >= v_min: the quotient does not fall as
-// the cell rises, so the occupied values are an upper range of int8; 128: none is
-int distance_v_min(double occupied_threshold)
-{
-  for (int v = -128; v <= 127; ++v) {
-    if (!(static_cast<double>(v) / 100.0 < occupied_threshold)) return v;
-  }
-  return 128;
 }
 }  // namespace
 
@@ -264,7 +230,7 @@ hipError_t launch_distance_field(const CollisionParams& c, const int8_t* d_grid,
 {
   const int xsize = static_cast<int>(c.xsize), ysize = static_cast<int>(c.ysize);
   hipLaunchKernelGGL(distance_columns_kernel, dim3((c.xsize + kColumns - 1) / kColumns), dim3(kColumns * kStrips), 0, s, d_grid, xsize,
-                     ysize, distance_v_min(c.occupied_threshold), d_sq);
+                     ysize, blocking_cutoff(c.occupied_threshold), d_sq);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(distance_rows_kernel, dim3(c.ysize), dim3(kBlock), c.xsize * sizeof(int), s, xsize, d_sq, d_nearest);

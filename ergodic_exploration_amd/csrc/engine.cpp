@@ -1835,36 +1835,80 @@ eea_status eea_target_fill(int device, unsigned n_gauss, const double* mu, const
 }
 
 // ---- collision lookups ---------------------------------------------------------------------
-static eea_status make_collision_params(const eea_collision_cfg* cfg, eea::CollisionParams& c)
+// The checks of an eea_collision_cfg, one refusal each.  Every entry makes the ones it needs, in its own order, before it
+// selects a device, and then takes its parameters (collision_params / grid_params).
+static eea_status cfg_given(const eea_collision_cfg* cfg)
 {
-  if (cfg == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null collision config");
-  // Collision::Collision (collision.cpp:46-63)
-  if (cfg->search_radius < cfg->boundary_radius) {
-    return fail(EEA_ERR_INVALID_ARGUMENT, "Search radius must be at least the same size as the boundary radius");
-  }
-  if (cfg->occupied_threshold > 100.0 || cfg->occupied_threshold < 0.0) {
-    return fail(EEA_ERR_INVALID_ARGUMENT, "Occupied threshold must be between 0 and 100");
-  }
-  c.xmin = cfg->xmin;
-  c.ymin = cfg->ymin;
-  c.resolution = cfg->resolution;
-  c.xsize = cfg->xsize;
-  c.ysize = cfg->ysize;
-  // CollisionConfig radii in cells (collision.cpp:130-133)
+  return cfg != nullptr ? EEA_OK : fail(EEA_ERR_INVALID_ARGUMENT, "null collision config");
+}
+// Collision::Collision (collision.cpp:46-63)
+static eea_status cfg_radii_ordered(const eea_collision_cfg* cfg)
+{
+  if (!(cfg->search_radius < cfg->boundary_radius)) return EEA_OK;
+  return fail(EEA_ERR_INVALID_ARGUMENT, "Search radius must be at least the same size as the boundary radius");
+}
+static eea_status cfg_threshold_in_range(const eea_collision_cfg* cfg)
+{
+  if (!(cfg->occupied_threshold > 100.0 || cfg->occupied_threshold < 0.0)) return EEA_OK;
+  return fail(EEA_ERR_INVALID_ARGUMENT, "Occupied threshold must be between 0 and 100");
+}
+// (with a size of 0 the reference's gridBounds, grid.cpp:96-100, lets every cell index through)
+static eea_status cfg_has_cells(const eea_collision_cfg* cfg)
+{
+  if (cfg->xsize != 0 && cfg->ysize != 0) return EEA_OK;
+  return fail(EEA_ERR_INVALID_ARGUMENT, "the grid's xsize and ysize must be positive");
+}
+static eea_status cfg_has_resolution(const eea_collision_cfg* cfg)
+{
+  return cfg->resolution > 0.0 ? EEA_OK : fail(EEA_ERR_INVALID_ARGUMENT, "the grid's resolution must be positive");
+}
+// what collisionCheck, validate_control, the dynamic window and a fleet layer ask first: Collision::Collision's own checks
+static eea_status collision_cfg_refusal(const eea_collision_cfg* cfg)
+{
+  eea_status st = cfg_given(cfg);
+  if (st == EEA_OK) st = cfg_radii_ordered(cfg);
+  if (st == EEA_OK) st = cfg_threshold_in_range(cfg);
+  return st;
+}
+// what the clearance and the distance calls ask first: those around a grid the kernels can index
+static eea_status grid_query_cfg_refusal(const eea_collision_cfg* cfg)
+{
+  eea_status st = cfg_given(cfg);
+  if (st == EEA_OK) st = cfg_has_resolution(cfg);
+  if (st == EEA_OK) st = cfg_radii_ordered(cfg);
+  if (st == EEA_OK) st = cfg_threshold_in_range(cfg);
+  if (st == EEA_OK) st = cfg_has_cells(cfg);
+  return st;
+}
+// what the sensor, the gain field and (behind its own arguments) a fleet layer ask of the grid
+static eea_status grid_cfg_refusal(const eea_collision_cfg* cfg)
+{
+  const eea_status st = cfg_has_cells(cfg);
+  return st == EEA_OK ? cfg_has_resolution(cfg) : st;
+}
+
+// the geometry and the threshold of a configuration, the radii 0 (the sensor and the gain field do not read them)
+static eea::CollisionParams grid_params(const eea_collision_cfg* cfg)
+{
+  return eea::CollisionParams{ cfg->xmin, cfg->ymin, cfg->resolution, cfg->xsize, cfg->ysize, 0, 0, 0, cfg->occupied_threshold };
+}
+// ... with CollisionConfig's radii in cells (collision.cpp:130-133)
+static eea::CollisionParams collision_params(const eea_collision_cfg* cfg)
+{
+  eea::CollisionParams c = grid_params(cfg);
   c.r_bnd = static_cast<int>(std::floor(cfg->boundary_radius / cfg->resolution));
   c.r_col = static_cast<int>(std::floor((cfg->boundary_radius + cfg->obstacle_threshold) / cfg->resolution));
   c.r_max = static_cast<int>(std::floor(cfg->search_radius / cfg->resolution));
-  c.occupied_threshold = cfg->occupied_threshold;
-  return EEA_OK;
+  return c;
 }
 
 eea_status eea_collision_check_batch(int device, const eea_collision_cfg* cfg, const int8_t* d_grid,
                                      const double* d_pose, unsigned P, int* d_hit, void* stream)
 {
-  eea::CollisionParams c;
-  eea_status st = make_collision_params(cfg, c);
+  const eea_status st = collision_cfg_refusal(cfg);
   if (st != EEA_OK) return st;
   if (d_grid == nullptr || d_pose == nullptr || d_hit == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  const eea::CollisionParams c = collision_params(cfg);
   EEA_HIP(hipSetDevice(device));
   EEA_HIP(eea::launch_collision_check(c, d_grid, d_pose, P, d_hit, static_cast<hipStream_t>(stream)));
   return EEA_OK;
@@ -1874,12 +1918,12 @@ eea_status eea_validate_control_batch(int device, const eea_collision_cfg* cfg, 
                                       const double* d_x0, const double* d_u, double dt,
                                       double horizon, unsigned P, int* d_valid, void* stream)
 {
-  eea::CollisionParams c;
-  eea_status st = make_collision_params(cfg, c);
+  const eea_status st = collision_cfg_refusal(cfg);
   if (st != EEA_OK) return st;
   if (d_grid == nullptr || d_x0 == nullptr || d_u == nullptr || d_valid == nullptr) {
     return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
   }
+  const eea::CollisionParams c = collision_params(cfg);
   const unsigned steps = static_cast<unsigned>(std::abs(horizon / dt));  // numerics.hpp:317
   EEA_HIP(hipSetDevice(device));
   EEA_HIP(eea::launch_validate_control(c, d_grid, d_x0, d_u, dt, steps, P, d_valid,
@@ -1899,19 +1943,15 @@ eea_status eea_integrate_twist_batch(int device, const double* d_x0, const doubl
 // ---- clearance queries: Collision::minDistance / minDirection (collision.cpp:65-124) -----------
 static_assert(sizeof(eea_clearance) == 4 * sizeof(int), "the kernels write an eea_clearance as four ints");
 
-// the checks of the configuration both clearance calls share, before the device is selected: Collision::Collision's own
-// (collision.cpp:46-63), a grid the kernels can index, and the key bound
-static eea_status make_clearance_params(const eea_collision_cfg* cfg, eea::CollisionParams& c)
+// the checks of the configuration both clearance calls share, before the device is selected: ... and the key bound
+static eea_status clearance_cfg_refusal(const eea_collision_cfg* cfg)
 {
-  if (cfg != nullptr && !(cfg->resolution > 0.0)) return fail(EEA_ERR_INVALID_ARGUMENT, "the grid's resolution must be positive");
-  const eea_status st = make_collision_params(cfg, c);
+  const eea_status st = grid_query_cfg_refusal(cfg);
   if (st != EEA_OK) return st;
-  // (with a size of 0 the reference's gridBounds, grid.cpp:96-100, lets every cell index through)
-  if (cfg->xsize == 0 || cfg->ysize == 0) return fail(EEA_ERR_INVALID_ARGUMENT, "the grid's xsize and ysize must be positive");
   if (static_cast<unsigned long long>(cfg->xsize) * cfg->ysize > (1ull << 31)) {
     return fail(EEA_ERR_UNSUPPORTED, "xsize * ysize above 2^31");
   }
-  if (!eea::clearance_supported(c)) {
+  if (!eea::clearance_supported(collision_params(cfg))) {
     return fail(EEA_ERR_UNSUPPORTED, "the search radius is too large in cells: the clearance key (|d|^2, visit index) does not fit 32 bits");
   }
   return EEA_OK;
@@ -1920,12 +1960,12 @@ static eea_status make_clearance_params(const eea_collision_cfg* cfg, eea::Colli
 eea_status eea_clearance_batch(int device, const eea_collision_cfg* cfg, const int8_t* d_grid, const double* d_pose, unsigned P,
                                eea_clearance* d_out, double* d_dmin, double* d_disp, void* stream)
 {
-  eea::CollisionParams c;
-  const eea_status st = make_clearance_params(cfg, c);
+  const eea_status st = clearance_cfg_refusal(cfg);
   if (st != EEA_OK) return st;
   if (d_grid == nullptr || d_pose == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
   if (d_out == nullptr && d_dmin == nullptr && d_disp == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "no output");
   if (P == 0) return EEA_OK;
+  const eea::CollisionParams c = collision_params(cfg);
   EEA_HIP(hipSetDevice(device));
   EEA_HIP(eea::launch_clearance(c, cfg->boundary_radius, d_grid, d_pose, P, reinterpret_cast<int*>(d_out), d_dmin, d_disp,
                                 static_cast<hipStream_t>(stream)));
@@ -1935,11 +1975,11 @@ eea_status eea_clearance_batch(int device, const eea_collision_cfg* cfg, const i
 eea_status eea_clearance_field(int device, const eea_collision_cfg* cfg, const int8_t* d_grid, eea_clearance* d_field,
                                double* d_dmin, void* stream)
 {
-  eea::CollisionParams c;
-  const eea_status st = make_clearance_params(cfg, c);
+  const eea_status st = clearance_cfg_refusal(cfg);
   if (st != EEA_OK) return st;
   if (d_grid == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
   if (d_field == nullptr && d_dmin == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "no output");
+  const eea::CollisionParams c = collision_params(cfg);
   EEA_HIP(hipSetDevice(device));
   EEA_HIP(eea::launch_clearance(c, cfg->boundary_radius, d_grid, nullptr, static_cast<size_t>(c.xsize) * c.ysize,
                                 reinterpret_cast<int*>(d_field), d_dmin, nullptr, static_cast<hipStream_t>(stream)));
@@ -1948,12 +1988,10 @@ eea_status eea_clearance_field(int device, const eea_collision_cfg* cfg, const i
 
 // ---- distance field: the exact Euclidean distance transform of the occupied cells (distance_kernel.hip) ----
 // the checks of the configuration the three distance calls share, before the device is selected
-static eea_status make_distance_params(const eea_collision_cfg* cfg, eea::CollisionParams& c)
+static eea_status distance_cfg_refusal(const eea_collision_cfg* cfg)
 {
-  if (cfg != nullptr && !(cfg->resolution > 0.0)) return fail(EEA_ERR_INVALID_ARGUMENT, "the grid's resolution must be positive");
-  const eea_status st = make_collision_params(cfg, c);
+  const eea_status st = grid_query_cfg_refusal(cfg);
   if (st != EEA_OK) return st;
-  if (cfg->xsize == 0 || cfg->ysize == 0) return fail(EEA_ERR_INVALID_ARGUMENT, "the grid's xsize and ysize must be positive");
   if (cfg->xsize > eea::kDistanceMaxSide || cfg->ysize > eea::kDistanceMaxSide) {
     return fail(EEA_ERR_UNSUPPORTED, "the distance field takes grids of up to EEA_DISTANCE_MAX_SIDE cells per side");
   }
@@ -1962,9 +2000,9 @@ static eea_status make_distance_params(const eea_collision_cfg* cfg, eea::Collis
 
 eea_status eea_distance_field(int device, const eea_collision_cfg* cfg, const int8_t* d_grid, int* d_sq, int* d_nearest, void* stream)
 {
-  eea::CollisionParams c;
-  const eea_status st = make_distance_params(cfg, c);
+  const eea_status st = distance_cfg_refusal(cfg);
   if (st != EEA_OK) return st;
+  const eea::CollisionParams c = collision_params(cfg);
   if (d_grid == nullptr || d_sq == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
   EEA_HIP(hipSetDevice(device));
   EEA_HIP(eea::launch_distance_field(c, d_grid, d_sq, d_nearest, static_cast<hipStream_t>(stream)));
@@ -1975,9 +2013,9 @@ eea_status eea_distance_query_batch(int device, const eea_collision_cfg* cfg, co
                                     const double* d_pose, unsigned P, eea_clearance* d_out, double* d_dmin, double* d_disp,
                                     void* stream)
 {
-  eea::CollisionParams c;
-  const eea_status st = make_distance_params(cfg, c);
+  const eea_status st = distance_cfg_refusal(cfg);
   if (st != EEA_OK) return st;
+  const eea::CollisionParams c = collision_params(cfg);
   if (d_sq == nullptr || d_pose == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
   if (d_out == nullptr && d_dmin == nullptr && d_disp == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "no output");
   if (d_nearest == nullptr && (d_out != nullptr || d_disp != nullptr)) {
@@ -1994,9 +2032,9 @@ eea_status eea_distance_traj_min(int device, const eea_collision_cfg* cfg, const
                                  const double* d_traj, unsigned B, unsigned T, eea_clearance* d_out, int* d_step, double* d_dmin,
                                  void* stream)
 {
-  eea::CollisionParams c;
-  const eea_status st = make_distance_params(cfg, c);
+  const eea_status st = distance_cfg_refusal(cfg);
   if (st != EEA_OK) return st;
+  const eea::CollisionParams c = collision_params(cfg);
   if (d_sq == nullptr || d_traj == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
   if (d_out == nullptr && d_step == nullptr && d_dmin == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "no output");
   if (d_nearest == nullptr && d_out != nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "d_out needs the field's d_nearest");
@@ -2016,21 +2054,6 @@ void eea_release_collision_caches(void)
 }
 
 // ---- range sensing of a simulated fleet ------------------------------------------------------
-// the geometry of an eea_collision_cfg without Collision::Collision's checks of the radii, which the sensor does not read
-static eea_status make_sense_params(const eea_collision_cfg* cfg, eea::CollisionParams& c)
-{
-  if (cfg->xsize == 0 || cfg->ysize == 0) return fail(EEA_ERR_INVALID_ARGUMENT, "the grid's xsize and ysize must be positive");
-  if (!(cfg->resolution > 0.0)) return fail(EEA_ERR_INVALID_ARGUMENT, "the grid's resolution must be positive");
-  c.xmin = cfg->xmin;
-  c.ymin = cfg->ymin;
-  c.resolution = cfg->resolution;
-  c.xsize = cfg->xsize;
-  c.ysize = cfg->ysize;
-  c.r_bnd = c.r_col = c.r_max = 0;
-  c.occupied_threshold = cfg->occupied_threshold;
-  return EEA_OK;
-}
-
 unsigned eea_sense_ray_count(unsigned range_cells) { return 8u * range_cells; }
 
 eea_status eea_sense_reveal_batch(int device, const eea_collision_cfg* cfg, unsigned range_cells, const int8_t* d_truth,
@@ -2041,12 +2064,12 @@ eea_status eea_sense_reveal_batch(int device, const eea_collision_cfg* cfg, unsi
     return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
   }
   if (d_truth == d_known) return fail(EEA_ERR_INVALID_ARGUMENT, "d_truth and d_known must be different grids");
-  eea::CollisionParams c;
-  const eea_status st = make_sense_params(cfg, c);
+  const eea_status st = grid_cfg_refusal(cfg);
   if (st != EEA_OK) return st;
   if (range_cells == 0) return fail(EEA_ERR_INVALID_ARGUMENT, "range_cells must be positive");
   if (range_cells > 1024u) return fail(EEA_ERR_UNSUPPORTED, "range_cells above 1024");
   if (P == 0) return EEA_OK;
+  const eea::CollisionParams c = grid_params(cfg);
   EEA_HIP(hipSetDevice(device));
   EEA_HIP(eea::launch_sense_reveal(c, range_cells, d_truth, d_known, d_pose, d_mask, P, d_ranges,
                                    static_cast<hipStream_t>(stream)));
@@ -2057,9 +2080,9 @@ eea_status eea_grid_census(int device, const eea_collision_cfg* cfg, const int8_
                            void* stream)
 {
   if (cfg == nullptr || d_grid == nullptr || d_counts == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
-  eea::CollisionParams c;
-  const eea_status st = make_sense_params(cfg, c);
+  const eea_status st = grid_cfg_refusal(cfg);
   if (st != EEA_OK) return st;
+  const eea::CollisionParams c = grid_params(cfg);
   EEA_HIP(hipSetDevice(device));
   EEA_HIP(eea::launch_grid_census(c, d_grid, d_counts, static_cast<hipStream_t>(stream)));
   return EEA_OK;
@@ -2067,9 +2090,9 @@ eea_status eea_grid_census(int device, const eea_collision_cfg* cfg, const int8_
 
 // ---- information-gain target ------------------------------------------------------------------
 // the argument checks eea_sense_gain_field and eea_set_target_gain share (after their null checks), before any HIP call
-static eea_status make_gain_params(const eea_collision_cfg* cfg, unsigned range_cells, unsigned stride, eea::CollisionParams& c)
+static eea_status gain_refusal(const eea_collision_cfg* cfg, unsigned range_cells, unsigned stride)
 {
-  const eea_status st = make_sense_params(cfg, c);
+  const eea_status st = grid_cfg_refusal(cfg);
   if (st != EEA_OK) return st;
   if (range_cells == 0) return fail(EEA_ERR_INVALID_ARGUMENT, "range_cells must be positive");
   if (stride == 0) return fail(EEA_ERR_INVALID_ARGUMENT, "stride must be positive");
@@ -2081,9 +2104,9 @@ eea_status eea_sense_gain_field(int device, const eea_collision_cfg* cfg, unsign
                                 const int8_t* d_known, unsigned* d_gain, void* stream)
 {
   if (cfg == nullptr || d_known == nullptr || d_gain == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
-  eea::CollisionParams c;
-  const eea_status st = make_gain_params(cfg, range_cells, stride, c);
+  const eea_status st = gain_refusal(cfg, range_cells, stride);
   if (st != EEA_OK) return st;
+  const eea::CollisionParams c = grid_params(cfg);
   EEA_HIP(hipSetDevice(device));
   EEA_HIP(eea::launch_gain_field(c, range_cells, stride, d_known, d_gain, static_cast<hipStream_t>(stream)));
   return EEA_OK;
@@ -2094,9 +2117,9 @@ eea_status eea_set_target_gain(eea_engine* e, const eea_collision_cfg* cfg, unsi
 {
   if (e == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null engine");
   if (cfg == nullptr || d_known == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
-  eea::CollisionParams c;
-  eea_status st = make_gain_params(cfg, range_cells, stride, c);
+  eea_status st = gain_refusal(cfg, range_cells, stride);
   if (st != EEA_OK) return st;
+  const eea::CollisionParams c = grid_params(cfg);
   if (!(floor >= 0.0) || !std::isfinite(floor)) return fail(EEA_ERR_INVALID_ARGUMENT, "floor must be finite and >= 0");
   if (!(lx > 0.0 && ly > 0.0)) return fail(EEA_ERR_INVALID_ARGUMENT, "bad gain target domain");
   const size_t P = static_cast<size_t>(c.xsize) * c.ysize;
@@ -2147,12 +2170,6 @@ struct eea_fleet_layer
   int* d_cell = nullptr;
 };
 
-static bool same_collision_params(const eea::CollisionParams& a, const eea::CollisionParams& b)
-{
-  return a.xmin == b.xmin && a.ymin == b.ymin && a.resolution == b.resolution && a.xsize == b.xsize && a.ysize == b.ysize &&
-         a.r_bnd == b.r_bnd && a.r_col == b.r_col && a.r_max == b.r_max && a.occupied_threshold == b.occupied_threshold;
-}
-
 // One tick of Exploration<ModelT>::control's loop body for B robots (exploration.hpp:220-279): see ergodic_amd.h.  with_layer: the
 // call is eea_tick_batch_fleet -- `layer` must not be null and is used in steps 3 and 4, and the messages name that entry
 static eea_status tick_batch_impl(eea_engine* e, unsigned B, const eea_batch_io* io, const eea_tick_io* tick,
@@ -2174,12 +2191,12 @@ static eea_status tick_batch_impl(eea_engine* e, unsigned B, const eea_batch_io*
   }
   if (with_layer && layer == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null fleet layer");
   if (B == 0 && !with_layer) return EEA_OK;
-  eea::CollisionParams c;
-  eea_status st = make_collision_params(ccfg, c);
+  eea_status st = collision_cfg_refusal(ccfg);
   if (st != EEA_OK) return st;
+  const eea::CollisionParams c = collision_params(ccfg);
   if (with_layer) {
     if (B != layer->v.B) return fail(EEA_ERR_INVALID_ARGUMENT, "the tick's B is not the fleet layer's");
-    if (!same_collision_params(c, layer->c)) {
+    if (!eea::same_params(c, layer->c)) {
       return fail(EEA_ERR_INVALID_ARGUMENT, "the tick's collision configuration is not the fleet layer's");
     }
     if (layer->device != e->cfg.device) return fail(EEA_ERR_INVALID_ARGUMENT, "the fleet layer lives on another device than the engine");
@@ -2245,13 +2262,13 @@ eea_status eea_fleet_layer_create(int device, const eea_collision_cfg* cfg, int 
 {
   if (out == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
   *out = nullptr;
-  eea::CollisionParams c;
-  const eea_status st = make_collision_params(cfg, c);
+  eea_status st = collision_cfg_refusal(cfg);
   if (st != EEA_OK) return st;
   if (B == 0) return fail(EEA_ERR_INVALID_ARGUMENT, "a fleet layer needs at least one robot");
   if (body_cells < 0) return fail(EEA_ERR_INVALID_ARGUMENT, "the body radius of a fleet layer must be >= 0 cells");
-  if (cfg->xsize == 0 || cfg->ysize == 0) return fail(EEA_ERR_INVALID_ARGUMENT, "the grid's xsize and ysize must be positive");
-  if (!(cfg->resolution > 0.0)) return fail(EEA_ERR_INVALID_ARGUMENT, "the grid's resolution must be positive");
+  st = grid_cfg_refusal(cfg);
+  if (st != EEA_OK) return st;
+  const eea::CollisionParams c = collision_params(cfg);
   if (c.r_bnd < 0 || c.r_col < 0) return fail(EEA_ERR_INVALID_ARGUMENT, "the collision radii must not be negative");
   // the reach R' = r_col + body (the span table holds shorts; the padded map grows by R' on every side)
   if (c.r_col > 127 || body_cells > 127 || c.r_col + body_cells > 127) {
@@ -2294,7 +2311,7 @@ eea_status eea_fleet_layer_create(int device, const eea_collision_cfg* cfg, int 
 void eea_fleet_layer_destroy(eea_fleet_layer* l)
 {
   if (l == nullptr) return;
-  if (l->v.spans != nullptr) eea::release_fleet_spans(l->device, l->v.spans);
+  if (l->v.row_start != nullptr) eea::release_fleet_spans(l->device, l->v.row_start);
   if ((l->d_count != nullptr || l->d_cell != nullptr) && hipSetDevice(l->device) == hipSuccess) {
     if (l->d_count != nullptr) (void)hipFree(l->d_count);  // waits for its users
     if (l->d_cell != nullptr) (void)hipFree(l->d_cell);
@@ -2336,9 +2353,9 @@ eea_status eea_dwa_control_batch(int device, const eea_collision_cfg* ccfg, cons
                                  const double* d_vref, const double* d_xt_ref, unsigned n_ref,
                                  double dt_ref, unsigned P, double* d_u_opt, int* d_found, void* stream)
 {
-  eea::CollisionParams c;
-  eea_status st = make_collision_params(ccfg, c);
+  eea_status st = collision_cfg_refusal(ccfg);
   if (st != EEA_OK) return st;
+  const eea::CollisionParams c = collision_params(ccfg);
   if (dcfg == nullptr || d_grid == nullptr || d_x0 == nullptr || d_vb == nullptr || d_u_opt == nullptr ||
       d_found == nullptr) {
     return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");

@@ -18,12 +18,15 @@
 //   3. prefix sum along every row, in place.  Integer sums: the result is exact whatever the order of the atomics.
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <cstdint>
 #include <mutex>
 #include <vector>
 
 #include "common.hpp"
+#include "device_tables.hpp"  // DeviceTables: the span tables kept per device, counted by the layers that hold them
 #include "fleet_spans.hpp"
+#include "grid_buffers.hpp"  // upload_block, CurrentDeviceGuard
 #include "grid_cell.hpp"  // world_to_grid: the cell of a pose as the collision kernels and the range sensor derive it
 
 namespace eea
@@ -89,82 +92,52 @@ __global__ __launch_bounds__(kWave* kScanRows) void fleet_row_scan_kernel(int* _
 // ---- the span tables in device memory -----------------------------------------------------------
 namespace
 {
-struct SpanEntry
+using SpanKey = std::array<int, 4>;  // r_bnd, r_col, r_max, body
+struct SpanTable
 {
-  int device, r_bnd, r_col, r_max, body, n_spans, users;
-  int* d_row_start;
-  FleetSpan* d_spans;
+  const int* row_start;
+  const FleetSpan* spans;
+  int n_spans;
 };
 std::mutex g_spans_mutex;
-std::vector<SpanEntry> g_span_tables;
+DeviceTables<SpanKey, SpanTable> g_span_tables;  // (the layers hold their entry: a live layer reads it)
 }  // namespace
 
 hipError_t acquire_fleet_spans(int device, const CollisionParams& c, int body, const int** d_row_start, const FleetSpan** d_spans,
                                int* n_spans)
 {
   std::lock_guard<std::mutex> lock(g_spans_mutex);
-  for (SpanEntry& e : g_span_tables) {
-    if (e.device == device && e.r_bnd == c.r_bnd && e.r_col == c.r_col && e.r_max == c.r_max && e.body == body) {
-      e.users += 1;
-      *d_row_start = e.d_row_start;
-      *d_spans = e.d_spans;
-      *n_spans = e.n_spans;
-      return hipSuccess;
-    }
+  const SpanKey key{ c.r_bnd, c.r_col, c.r_max, body };
+  const DeviceTables<SpanKey, SpanTable>::Entry* ent = g_span_tables.find(device, key, true);
+  if (ent == nullptr) {
+    const FleetSpans t = fleet_spans(c.r_bnd, c.r_col, c.r_max, body);
+    // (one allocation: the row index, then the spans -- 8-byte elements at the next multiple of 8 bytes)
+    const size_t row_bytes = t.row_start.size() * sizeof(int);
+    void* block = nullptr;
+    const hipError_t e = upload_block(t.row_start.data(), row_bytes, t.spans.data(), t.spans.size() * sizeof(FleetSpan), &block);
+    if (e != hipSuccess) return e;
+    const SpanTable table{ static_cast<const int*>(block),
+                           reinterpret_cast<const FleetSpan*>(static_cast<const char*>(block) + block_offset(row_bytes)),
+                           static_cast<int>(t.spans.size()) };
+    ent = &g_span_tables.insert(device, key, block, table, true);
   }
-  const FleetSpans t = fleet_spans(c.r_bnd, c.r_col, c.r_max, body);
-  SpanEntry ent{ device, c.r_bnd, c.r_col, c.r_max, body, static_cast<int>(t.spans.size()), 1, nullptr, nullptr };
-  // (one allocation: the row index, then the spans -- 8-byte elements behind an even number of ints)
-  const size_t n_rows = t.row_start.size() + (t.row_start.size() & 1u);
-  const size_t bytes = n_rows * sizeof(int) + (t.spans.size() + 1) * sizeof(FleetSpan);
-  void* p = nullptr;
-  hipError_t e = hipMalloc(&p, bytes);
-  if (e != hipSuccess) return e;
-  ent.d_row_start = static_cast<int*>(p);
-  ent.d_spans = reinterpret_cast<FleetSpan*>(ent.d_row_start + n_rows);
-  e = hipMemcpy(ent.d_row_start, t.row_start.data(), t.row_start.size() * sizeof(int), hipMemcpyHostToDevice);
-  if (e == hipSuccess && !t.spans.empty()) {
-    e = hipMemcpy(ent.d_spans, t.spans.data(), t.spans.size() * sizeof(FleetSpan), hipMemcpyHostToDevice);
-  }
-  if (e != hipSuccess) {
-    (void)hipFree(p);
-    return e;
-  }
-  g_span_tables.push_back(ent);
-  *d_row_start = ent.d_row_start;
-  *d_spans = ent.d_spans;
-  *n_spans = ent.n_spans;
+  *d_row_start = ent->view.row_start;
+  *d_spans = ent->view.spans;
+  *n_spans = ent->view.n_spans;
   return hipSuccess;
 }
 
-void release_fleet_spans(int device, const FleetSpan* d_spans)
+void release_fleet_spans(int device, const int* d_row_start)
 {
   std::lock_guard<std::mutex> lock(g_spans_mutex);
-  for (SpanEntry& e : g_span_tables) {
-    if (e.device == device && e.d_spans == d_spans && e.users > 0) {
-      e.users -= 1;
-      return;
-    }
-  }
+  g_span_tables.give_back(device, d_row_start);
 }
 
 void release_fleet_span_cache()
 {
-  int current = 0;
-  const bool have_device = hipGetDevice(&current) == hipSuccess;
-  {
-    std::lock_guard<std::mutex> lock(g_spans_mutex);
-    std::vector<SpanEntry> kept;
-    for (SpanEntry& e : g_span_tables) {
-      if (e.users > 0) {
-        kept.push_back(e);  // a live layer reads it
-      } else if (hipSetDevice(e.device) == hipSuccess) {
-        (void)hipFree(e.d_row_start);  // waits for its users
-      }
-    }
-    g_span_tables.swap(kept);
-  }
-  if (have_device) (void)hipSetDevice(current);
+  const CurrentDeviceGuard guard;
+  std::lock_guard<std::mutex> lock(g_spans_mutex);
+  g_span_tables.release(free_on_device);
 }
 
 hipError_t launch_fleet_layer_update(const CollisionParams& c, const FleetView& v, int n_spans, int* d_count, int* d_cell,

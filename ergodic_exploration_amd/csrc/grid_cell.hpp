@@ -1,6 +1,7 @@
 // GridMap::world2Grid (reference grid.cpp:143-159) on the device, bit-exact with the reference's x86-64 build: the ONE
 // definition the collision kernels (collision_kernel.hip) and the range sensor (sense_kernel.hip) take a pose's cell from.
-// Both translation units are compiled with -ffp-contract=off.
+// With it the other device pieces the grid queries share: the literal occupancy test and the writer of a clearance answer
+// (clearance_kernel.hip, distance_kernel.hip).  Every translation unit that includes this is compiled with -ffp-contract=off.
 #pragma once
 
 #include "common.hpp"
@@ -23,5 +24,35 @@ __device__ __forceinline__ void world_to_grid(const CollisionParams& c, double p
   i = cast_u32_x86(floor((py - c.ymin) / c.resolution));
   if (j == c.xsize) j--;
   if (i == c.ysize) i--;
+}
+
+// checkCell's test on GridMap::getCell (collision.cpp:216-243, grid.cpp:177-184) in the reference's literal form: a cell of
+// value v is occupied iff !(v / 100.0 < threshold)
+__device__ __forceinline__ bool occupied(const CollisionParams& c, int8_t v)
+{
+  return !(static_cast<double>(v) / 100.0 < c.occupied_threshold);
+}
+
+// The answer of one centre (clearance_kernel.hip, distance_kernel.hip) and its one writer: out [.][4] ints (msg, sqrd_obs,
+// dx, dy), dmin [.], disp [.][2], each of which may be null
+struct ClearanceAnswer
+{
+  int msg, sq, dx, dy;
+  double dmin, d0, d1;
+};
+__device__ __forceinline__ void write_answer(int* __restrict__ out, double* __restrict__ dmin, double* __restrict__ disp, size_t q,
+                                             const ClearanceAnswer& a)
+{
+  if (out != nullptr) {
+    out[4 * q] = a.msg;
+    out[4 * q + 1] = a.sq;
+    out[4 * q + 2] = a.dx;
+    out[4 * q + 3] = a.dy;
+  }
+  if (dmin != nullptr) dmin[q] = a.dmin;
+  if (disp != nullptr) {
+    disp[2 * q] = a.d0;
+    disp[2 * q + 1] = a.d1;
+  }
 }
 }  // namespace eea

@@ -1,7 +1,8 @@
-// Host-side bookkeeping of the inflated collision map (collision_kernel.hip): the offset set of the dilation and the policy
-// of the map buffers kept between calls.  Plain C++: no HIP call, no global state, no lock -- collision_kernel.hip owns the
-// mutex and performs every effect; tests/hit_map_table_check.cpp drives this file alone, without a GPU.  Also the visit-
-// ordered walk of the clearance queries (clearance_kernel.hip), which tests/clearance_walk_check.cpp drives the same way.
+// Host-side bookkeeping of the grid queries: the ring walk of the reference's search with its two views -- the offset set of
+// the inflated collision map's dilation (collision_kernel.hip) and the visit-ordered list of the clearance queries
+// (clearance_kernel.hip) -- and the policy of the map buffers both keep between calls.  Plain C++: no HIP call, no global
+// state, no lock -- the callers own their mutex and grid_buffers.hpp performs the effects; tests/hit_map_table_check.cpp and
+// tests/clearance_walk_check.cpp drive this file alone, without a GPU.
 #pragma once
 
 #include <set>
@@ -12,18 +13,20 @@
 
 namespace eea
 {
-// offsets (cell - centre) the ring search r_bnd..r_max can report a collision at: the walk of
-// collision.cpp:166-214, keeping the cells within r_col (collision.cpp:239)
-inline std::vector<short2> ring_offsets(int r_bnd, int r_col, int r_max)
+// The reference's ring walk (collision.cpp:166-214), written ONCE on the host: the rings r_bnd..r_max one after the other,
+// within a ring the Bresenham steps in order, within a step Q1 Q2 Q3 Q4 (collision.cpp:175-193); visit(dx, dy) per visit,
+// (dx, dy) = cell - centre.  A ring of radius <= 0 visits nothing.  (The device's own bresenham_circle, collision_kernel.hip,
+// is the reference-literal search; this is its enumeration.)
+template <typename Visit>
+inline void walk_rings(int r_bnd, int r_max, Visit visit)
 {
-  std::set<std::pair<int, int>> pts;  // (sorted, each offset once)
-  for (int r0 = r_bnd; r0 <= r_max; ++r0) {
+  for (int r0 = r_bnd < 1 ? 1 : r_bnd; r0 <= r_max; ++r0) {
     int r = r0, x = -r0, y = 0, err = 2 - 2 * r0;
     while (x < 0) {
-      pts.emplace(-x, y);
-      pts.emplace(-y, -x);
-      pts.emplace(x, -y);
-      pts.emplace(y, x);
+      visit(-x, y);
+      visit(-y, -x);
+      visit(x, -y);
+      visit(y, x);
       r = err;
       if (r <= y) {
         y++;
@@ -35,18 +38,25 @@ inline std::vector<short2> ring_offsets(int r_bnd, int r_col, int r_max)
       }
     }
   }
+}
+
+// offsets (cell - centre) the ring search r_bnd..r_max can report a collision at: the set of the walk's visits within r_col
+// (collision.cpp:239), sorted, each offset once
+inline std::vector<short2> ring_offsets(int r_bnd, int r_col, int r_max)
+{
+  std::set<std::pair<int, int>> pts;
+  walk_rings(r_bnd, r_max, [&](int dx, int dy) {
+    if (dx * dx + dy * dy <= r_col * r_col) pts.emplace(dx, dy);
+  });
   std::vector<short2> out;
-  for (const auto& p : pts) {
-    if (p.first * p.first + p.second * p.second > r_col * r_col) continue;
-    out.push_back(make_short2(static_cast<short>(p.first), static_cast<short>(p.second)));
-  }
+  for (const auto& p : pts) out.push_back(make_short2(static_cast<short>(p.first), static_cast<short>(p.second)));
   return out;
 }
 
-// The same walk in VISIT order with duplicates kept (clearance_kernel.hip): offsets[k] is the k-th cell (cell - centre) the
-// search r_bnd..r_max tests, Q1 Q2 Q3 Q4 of every Bresenham step (collision.cpp:175-193).  Collision::minDistance /
-// minDirection keep the FIRST visited cell of the smallest squared distance, i.e. the smallest key (|d_k|^2, k); the device
-// holds that key in one 32-bit word, |d_k|^2 * n + k, with the all-ones word for "no cell".
+// The walk's visits as a list, in VISIT order with duplicates kept (clearance_kernel.hip): offsets[k] is the k-th cell the
+// search r_bnd..r_max tests.  Collision::minDistance / minDirection keep the FIRST visited cell of the smallest squared
+// distance, i.e. the smallest key (|d_k|^2, k); the device holds that key in one 32-bit word, |d_k|^2 * n + k, with the
+// all-ones word for "no cell".
 struct ClearanceWalk
 {
   std::vector<short2> offsets;
@@ -68,29 +78,14 @@ inline bool clearance_walk(int r_bnd, int r_max, ClearanceWalk& w)
   // The ring r_max alone has at least 4 r_max offsets (x goes from -r_max to 0 by at most 1 per step) of |d|^2 >= r_max^2:
   // 4 r_max^3 >= 2^32 from r_max = 1024 on.  Refused here, before a walk of that size is enumerated.
   if (r_max >= 1024 && r_bnd <= r_max) return false;
-  for (int r0 = r_bnd < 1 ? 1 : r_bnd; r0 <= r_max; ++r0) {  // (a ring of radius <= 0 visits nothing)
-    int r = r0, x = -r0, y = 0, err = 2 - 2 * r0;
-    while (x < 0) {
-      const int q[4][2] = { { -x, y }, { -y, -x }, { x, -y }, { y, x } };
-      for (const auto& d : q) {
-        w.offsets.push_back(make_short2(static_cast<short>(d[0]), static_cast<short>(d[1])));
-        const int ax = d[0] < 0 ? -d[0] : d[0], ay = d[1] < 0 ? -d[1] : d[1];
-        if (ax > w.reach) w.reach = ax;
-        if (ay > w.reach) w.reach = ay;
-        const unsigned sq = static_cast<unsigned>(d[0] * d[0] + d[1] * d[1]);
-        if (sq > w.max_sq) w.max_sq = sq;
-      }
-      r = err;
-      if (r <= y) {
-        y++;
-        err += 2 * y + 1;
-      }
-      if (r > x || err > y) {
-        x++;
-        err += 2 * x + 1;
-      }
-    }
-  }
+  walk_rings(r_bnd, r_max, [&](int dx, int dy) {
+    w.offsets.push_back(make_short2(static_cast<short>(dx), static_cast<short>(dy)));
+    const int ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy;
+    if (ax > w.reach) w.reach = ax;
+    if (ay > w.reach) w.reach = ay;
+    const unsigned sq = static_cast<unsigned>(dx * dx + dy * dy);
+    if (sq > w.max_sq) w.max_sq = sq;
+  });
   return clearance_key_fits(w.max_sq, w.offsets.size());
 }
 
@@ -131,7 +126,7 @@ public:
       s = Slot{ device, stream };
       p.cap = bytes;
     }
-    p.reuse = epoch != 0 && s.stamp != 0 && s.built_grid == grid && s.built_epoch == epoch && same(s.built_params, c);
+    p.reuse = epoch != 0 && s.stamp != 0 && s.built_grid == grid && s.built_epoch == epoch && same_params(s.built_params, c);
     if (p.reuse) return p;
     s.built_epoch = 0;  // (no call's epoch)
     p.clear = s.stamp == 0 || s.stamp >= 255u;  // a fresh buffer, or the stamps wrap
@@ -184,11 +179,6 @@ private:
     unsigned long long built_epoch = 0;
     CollisionParams built_params{};
   };
-  static bool same(const CollisionParams& a, const CollisionParams& b)
-  {
-    return a.xmin == b.xmin && a.ymin == b.ymin && a.resolution == b.resolution && a.xsize == b.xsize && a.ysize == b.ysize &&
-           a.r_bnd == b.r_bnd && a.r_col == b.r_col && a.r_max == b.r_max && a.occupied_threshold == b.occupied_threshold;
-  }
   std::vector<Slot> slots_;
 };
 }  // namespace eea

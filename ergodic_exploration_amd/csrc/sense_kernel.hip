@@ -7,7 +7,7 @@
 //  - integers only: the robot's cell is world2Grid of grid_cell.hpp (the collision kernels' definition), a ray's step s sits
 //    at sgn(m) ((2 s |m| + R) div 2R) per axis -- formed here by adding 2|m| per step to a remainder that starts at R and
 //    wraps at 2R, which is that quotient exactly (2|m| <= 2R: at most one wrap per step) --, and "blocks a ray" is
-//    cell >= cutoff, cutoff = the smallest int8 value v with !(v / 100.0 < occupied_threshold) found on the host (the
+//    cell >= cutoff, cutoff = the smallest int8 value v with !(v / 100.0 < occupied_threshold) found on the host (common.hpp; the
 //    quotient is monotone in v: checkCell's test, collision.cpp:216-243 with grid.cpp:177-184, is a threshold on the cell);
 //  - every write to a cell of `known` stores that cell of `truth`, whoever makes it: robots, rays and calls may overlap in
 //    any order, no atomics, byte (vector) stores only;
@@ -174,16 +174,6 @@ __global__ __launch_bounds__(kSenseBlock) void grid_census_kernel(const int8_t* 
   }
 }
 }  // namespace
-
-int blocking_cutoff(double occupied_threshold)
-{
-  // checkCell's test on getCell (collision.cpp:216-243, grid.cpp:177-184), cell by cell; v / 100.0 is monotone in v
-  for (int v = -128; v <= 127; ++v) {
-    const double cell = static_cast<double>(static_cast<int8_t>(v)) / 100.0;
-    if (!(cell < occupied_threshold)) return v;
-  }
-  return 128;
-}
 
 hipError_t launch_sense_reveal(const CollisionParams& c, unsigned range_cells, const int8_t* d_truth, int8_t* d_known,
                                const double* d_pose, const int* d_mask, unsigned P, int* d_ranges, hipStream_t s)

@@ -78,8 +78,34 @@ void one_set(int r_bnd, int r_col, int r_max, size_t n_off)
   for (size_t k = 0; k < joined.size(); ++k) CHECK(joined[k].x == w.offsets[k].x && joined[k].y == w.offsets[k].y);
 }
 
+// the two views of the one walk: the walk's offsets within r_col, as a set, are ring_offsets -- for every r_col up to r_max
+// (both are filters over walk_rings: this catches a wrong filter, not a wrong walk -- the walk itself is held to the oracle's
+// ring search by tests/test_hit_map_table.py and to the restatement's own enumeration by tests/test_clearance.py)
+void views_of_one_walk()
+{
+  for (int r_bnd = 0; r_bnd <= 6; ++r_bnd) {
+    for (int r_max = r_bnd; r_max <= 12; ++r_max) {
+      ClearanceWalk w;
+      CHECK(clearance_walk(r_bnd, r_max, w));
+      for (int r_col = 0; r_col <= r_max; ++r_col) {
+        std::set<std::pair<int, int>> near;
+        for (const short2& d : w.offsets) {
+          if (d.x * d.x + d.y * d.y <= r_col * r_col) near.emplace(d.x, d.y);
+        }
+        const std::vector<short2> ring = ring_offsets(r_bnd, r_col, r_max);
+        std::set<std::pair<int, int>> dilation;
+        for (const short2& d : ring) dilation.emplace(d.x, d.y);
+        CHECK(dilation.size() == ring.size());  // each offset once
+        CHECK(near == dilation);
+        CHECK(near.empty() == (r_col < (r_bnd < 1 ? 1 : r_bnd)));  // (ring 0 visits nothing; ring r > 0 starts at (r, 0))
+      }
+    }
+  }
+}
+
 void checks()
 {
+  views_of_one_walk();
   for (const Set& s : kSets) {
     // the radii in cells as csrc/engine.cpp derives them (collision.cpp:130-133)
     one_set(static_cast<int>(std::floor(s.boundary / s.resolution)), static_cast<int>(std::floor((s.boundary + s.obstacle) / s.resolution)),

@@ -13,7 +13,7 @@ COLL_S = (0.2, 0.4, 0.1, 0.8)     # small robots: boundary 0.2 m, search 0.4 m, 
 
 
 def radii(coll, res):
-    """(r_bnd, r_col, r_max) in cells, the library's formula (csrc/engine.cpp make_collision_params, collision.cpp:130-133)"""
+    """(r_bnd, r_col, r_max) in cells, the library's formula (csrc/engine.cpp collision_params, collision.cpp:130-133)"""
     return (int(math.floor(coll[0] / res)), int(math.floor((coll[0] + coll[2]) / res)), int(math.floor(coll[1] / res)))
 
 
@@ -63,6 +63,22 @@ def counts(g, F, reach, cells):
         if x == NOT_STAMPED:
             continue
         np.add.at(out, (y + off[:, 1] + reach, x + off[:, 0] + reach), 1)
+    return out
+
+
+def verdicts(g, data, S, F, cells, poses, owner):
+    """eea_fleet_collision_check_batch by the rule, pose by pose: with c the pose's cell (the wrapped indices of a pose outside
+    the grid taken as signed ints), 1 iff an occupied cell o of data [ysize][xsize] has o - c in S, or a stamped robot j other
+    than owner (-1: nobody) has c - cell_j in F"""
+    signed = lambda v: v - (1 << 32) if v >= (1 << 31) else v
+    occupied = [(x, y) for y, x in zip(*np.nonzero(np.vectorize(lambda v: sr.blocks(v, g.occupied_threshold))(data)))]
+    out = np.zeros(len(poses), dtype=np.int32)
+    for q, (p, b) in enumerate(zip(poses, owner)):
+        i, j = sr.world2grid(g, p[0], p[1])
+        cx, cy = signed(j), signed(i)
+        static = any((x - cx, y - cy) in S for (x, y) in occupied)
+        robots = any(r != b and x != NOT_STAMPED and (cx - x, cy - y) in F for r, (x, y) in enumerate(cells))
+        out[q] = 1 if static or robots else 0
     return out
 
 

@@ -357,3 +357,85 @@ def test_a_mismatched_configuration_or_fleet_size_is_refused_with_the_state_unto
     finally:
         layer.close()
         eng.close()
+
+
+COLL = (0.7, 1.0, 0.2, 0.8)      # the radii of tests/test_hit_map_table.py, at 0.1 m: 6, 8 and 10 cells
+
+
+@pytest.fixture(scope="module")
+def release_scene():
+    """24 x 16 cells at 0.1 m with four occupied cells, three robots of body 1 (the third masked), 64 poses: around the two
+    stamped robots the cells one short of the layer's reach, on its rim and one past it -- half of them outside the grid,
+    where the indices wrap --, the robots' own cells, and cells up to 11 outside the grid on every side.  The wanted verdicts
+    come from the rule (tests/fleet_layer_restatement.py), once."""
+    xmin, ymin, res, xs, ys, body = -0.4, -0.3, 0.1, 24, 16, 1
+    r_bnd, r_col, r_max = fr.radii(COLL, res)
+    reach = r_col + body
+    g = fr.sr.Geometry(xmin, ymin, res, xs, ys, COLL[3])
+    data = np.zeros((ys, xs), dtype=np.int8)
+    data[3, 3], data[12, 20], data[2, 12], data[15, 0] = 100, 100, 80, 90
+    data[8, 8] = 79                                                      # below the threshold: free
+    centre = lambda x, y: [xmin + (x + 0.5) * res, ymin + (y + 0.5) * res, 0.0]
+    robot_cells = [(6, 5), (17, 10), (12, 8)]
+    robots, mask = np.array([centre(x, y) for (x, y) in robot_cells]), np.array([1, 1, 0], dtype=np.int32)
+    cells = [(x + dx, y + dy) for (x, y) in robot_cells[:2] for d in (reach - 1, reach, reach + 1)
+             for (dx, dy) in ((d, 0), (-d, 0), (0, d), (0, -d))] + robot_cells
+    rng = np.random.default_rng(11)
+    while len(cells) < 64:
+        cells.append((int(rng.integers(-11, xs + 11)), int(rng.integers(-11, ys + 11))))
+    pose = np.array([centre(x, y) for (x, y) in cells])
+    owner = (np.arange(64, dtype=np.int32) % 4) - 1                      # nobody's, robot 0's, 1's, 2's
+    stamped = fr.cells_of(g, robots, mask)
+    assert np.array_equal(stamped[:2], robot_cells[:2]) and (stamped[2] == fr.NOT_STAMPED).all()
+    S, F = fr.ring_offsets(r_bnd, r_col, r_max), fr.offset_set(r_bnd, r_col, r_max, body)
+    want = fr.verdicts(g, data, S, F, stamped, pose, owner)
+    outside = np.array([not (j < xs and i < ys) for (i, j) in (fr.sr.world2grid(g, p[0], p[1]) for p in pose)])   # (unsigned)
+    assert 0 < want.sum() < 64 and want[outside].any() and not want[outside].all() and outside.sum() >= 16
+    # the layer bites, and so does a pose's own robot
+    nobody = np.full(64, -1, dtype=np.int32)
+    assert (want != fr.verdicts(g, data, S, F, np.full((3, 2), fr.NOT_STAMPED), pose, owner)).any()
+    assert (want != fr.verdicts(g, data, S, F, stamped, pose, nobody)).any()
+    return dict(cfg=capi.make_collision_cfg(xmin, ymin, res, xs, ys, *COLL), body=body, data=data, robots=robots, mask=mask,
+                pose=pose, owner=owner, want=want)
+
+
+@pytest.mark.parametrize("impl", [1, 2])
+def test_a_live_layer_survives_a_cache_release(release_scene, impl):
+    """release_collision_caches() with a layer alive frees the tables nobody holds and leaves the layer's span table where it
+    is: the layer, a second one made from the same parameters afterwards (a hit on the kept table), that one after the first
+    is gone, and a third one made after everything was released (a fresh table) all answer as the rule does.  The static part
+    goes through the ring search (impl 1) or the inflated map (2), whose offsets and buffers every release frees."""
+    s = release_scene
+    d_grid, d_pose, d_owner = dev(s["data"], torch.int8), dev(s["pose"]), dev(s["owner"], torch.int32)
+    d_robots, d_mask = dev(s["robots"]), dev(s["mask"], torch.int32)
+    layers = []
+
+    def create():
+        layers.append(capi.FleetLayer(s["cfg"], s["body"], len(s["robots"])))
+        layers[-1].update(d_robots, d_mask)
+        return layers[-1]
+
+    def answers(layer):
+        hit = torch.full((len(s["pose"]),), -7, dtype=torch.int32, device="cuda")
+        layer.collision_check(d_grid, d_pose, hit, self_index=d_owner)
+        return hit.cpu().numpy()
+
+    try:
+        capi.set_option(capi.OPT_COLLISION_IMPL, impl)
+        a = create()
+        assert np.array_equal(answers(a), s["want"])
+        capi.release_collision_caches()                   # a is alive
+        b = create()
+        assert np.array_equal(answers(a), s["want"]) and np.array_equal(answers(b), s["want"])
+        a.close()
+        capi.release_collision_caches()
+        assert np.array_equal(answers(b), s["want"])
+        b.close()
+        capi.release_collision_caches()
+        c = create()
+        assert np.array_equal(answers(c), s["want"])
+    finally:
+        capi.set_option(capi.OPT_COLLISION_IMPL, 0)
+        for layer in layers:
+            layer.close()
+        capi.release_collision_caches()
