@@ -72,6 +72,21 @@ class Clearance(C.Structure):
 COLLISION_CRASH, COLLISION_OBSTACLE, COLLISION_NONE = 0, 1, 2   # CollisionMsg (collision.hpp:55-60)
 COLLISION_OFF_GRID = 3       # the distance queries only: the pose's cell is not on the grid
 DISTANCE_MAX_SIDE = 8192     # EEA_DISTANCE_MAX_SIDE
+FOOTPRINT_MAX_VERTICES = 16  # EEA_FOOTPRINT_MAX_VERTICES
+
+
+class Footprint(C.Structure):
+    """eea_footprint: n vertices in the body frame, counter-clockwise and strictly convex, the body origin strictly inside.
+    Footprint.of(vertices) takes any number of (x, y) pairs up to the arrays' length (the library refuses n < 3)"""
+    _fields_ = [("n", C.c_uint), ("x", C.c_double * FOOTPRINT_MAX_VERTICES), ("y", C.c_double * FOOTPRINT_MAX_VERTICES)]
+
+    @classmethod
+    def of(cls, vertices):
+        fp = cls()
+        fp.n = len(vertices)
+        for k, (x, y) in enumerate(vertices[:FOOTPRINT_MAX_VERTICES]):
+            fp.x[k], fp.y[k] = float(x), float(y)
+        return fp
 
 
 class DwaCfg(C.Structure):
@@ -221,6 +236,12 @@ def lib():
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             L.eea_distance_traj_min.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint,
                                                 C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "eea_footprint_check_batch"):   # additive to ABI 6 as well
+            L.eea_footprint_radii.argtypes = [C.POINTER(Footprint), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+            L.eea_footprint_check_batch.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.POINTER(Footprint), C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p]
+            L.eea_footprint_traj_first.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.POINTER(Footprint), C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p]
         L.eea_replay_create.argtypes = [C.c_int, C.c_uint, C.c_uint, C.c_uint, C.c_uint64, C.c_uint, C.c_size_t, C.POINTER(C.c_void_p)]
         L.eea_replay_destroy.argtypes = [C.c_void_p]
         L.eea_replay_destroy.restype = None
@@ -665,6 +686,29 @@ def distance_traj_min(cfg, sq, nearest, traj, out=None, step=None, dmin=None, de
     tensors; asynchronous"""
     check(lib().eea_distance_traj_min(device, C.byref(cfg), _ptr(sq), _ptr(nearest), _ptr(traj), int(traj.shape[0]),
                                       int(traj.shape[1]), _ptr(out), _ptr(step), _ptr(dmin), C.c_void_p(stream or 0)))
+
+
+def footprint_radii(fp):
+    """eea_footprint_radii: (r_in, r_out) of the inscribed and the circumscribed circle about the body origin; validates the
+    footprint on the host, needs no device"""
+    r_in, r_out = C.c_double(), C.c_double()
+    check(lib().eea_footprint_radii(C.byref(fp), C.byref(r_in), C.byref(r_out)))
+    return r_in.value, r_out.value
+
+
+def footprint_check_batch(cfg, fp, grid, pose, hit, sq=None, device=0, stream=None):
+    """eea_footprint_check_batch: hit int32 [P] = 1 / 0 per pose of pose [P][3] for the polygon base fp on the int8 device grid;
+    sq: the int32 plane of distance_field for the same grid (the filter) or None (every pose takes the exact test).  Device
+    tensors; asynchronous"""
+    check(lib().eea_footprint_check_batch(device, C.byref(cfg), C.byref(fp), _ptr(grid), _ptr(sq), _ptr(pose), int(pose.shape[0]),
+                                          _ptr(hit), C.c_void_p(stream or 0)))
+
+
+def footprint_traj_first(cfg, fp, grid, traj, step, sq=None, device=0, stream=None):
+    """eea_footprint_traj_first: step int32 [B] = the first colliding step of each trajectory traj [B][T][3], -1: none; sq as in
+    footprint_check_batch.  Device tensors; asynchronous"""
+    check(lib().eea_footprint_traj_first(device, C.byref(cfg), C.byref(fp), _ptr(grid), _ptr(sq), _ptr(traj), int(traj.shape[0]),
+                                         int(traj.shape[1]), _ptr(step), C.c_void_p(stream or 0)))
 
 
 def release_collision_caches():

@@ -356,6 +356,24 @@ hipError_t launch_distance_traj_min(const CollisionParams& c, double boundary_ra
                                     const double* d_traj, unsigned B, unsigned T, int* d_out, int* d_step, double* d_dmin,
                                     hipStream_t s);
 
+// ---- footprint collision: a convex polygon base against the occupied cells (footprint_kernel.hip) ----
+// What the kernels read of a footprint, by value in the kernel arguments: the half-planes nx * bx + ny * by <= h of the body
+// frame and the filter's thresholds (footprint_planes.hpp derives both on the host)
+struct FootprintArgs
+{
+  unsigned n;
+  int sq_hit, sq_free, box;
+  int v_min;  // a cell is occupied iff its int8 >= v_min: blocking_cutoff(occupied_threshold)
+  double nx[16], ny[16], h[16];
+};
+// d_hit [P] = 1 / 0 per pose of d_pose [P][3]; d_sq: a built distance field of the same grid, or null (every pose takes the
+// exact test)
+hipError_t launch_footprint_check(const CollisionParams& c, const FootprintArgs& f, const int8_t* d_grid, const int* d_sq,
+                                  const double* d_pose, unsigned P, int* d_hit, hipStream_t s);
+// d_step [B] = the first colliding step of each trajectory d_traj [B][T][3] (T >= 1), -1: none
+hipError_t launch_footprint_traj_first(const CollisionParams& c, const FootprintArgs& f, const int8_t* d_grid, const int* d_sq,
+                                       const double* d_traj, unsigned B, unsigned T, int* d_step, hipStream_t s);
+
 // ---- fleet layer: robots as obstacles to one another (fleet_layer_kernel.hip, fleet_spans.hpp) ----
 // What the collision kernels read of a layer.  count [h][w] over the centres [-R, xsize + R) x [-R, ysize + R) (the geometry
 // of the inflated map with the layer's reach R = r_col + body): the number of stamped robots whose body a pose centred there

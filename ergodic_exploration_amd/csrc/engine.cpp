@@ -18,6 +18,7 @@
 
 #include "abi_util.hpp"
 #include "common.hpp"
+#include "footprint_planes.hpp"
 
 namespace
 {
@@ -2043,6 +2044,84 @@ eea_status eea_distance_traj_min(int device, const eea_collision_cfg* cfg, const
   EEA_HIP(hipSetDevice(device));
   EEA_HIP(eea::launch_distance_traj_min(c, cfg->boundary_radius, d_sq, d_nearest, d_traj, B, T, reinterpret_cast<int*>(d_out),
                                         d_step, d_dmin, static_cast<hipStream_t>(stream)));
+  return EEA_OK;
+}
+
+// ---- footprint collision: a convex polygon base through the distance field (footprint_kernel.hip) ----
+static_assert(sizeof(eea_footprint::x) == sizeof(double) * eea::kFootprintMaxVertices, "the header states the limit");
+
+// the footprint's own refusals (footprint_planes.hpp), before any device
+static eea_status footprint_refusal(const eea_footprint* fp, eea::FootprintPlanes& planes)
+{
+  if (fp == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null footprint");
+  // (n is checked before a vertex is read: the arrays hold EEA_FOOTPRINT_MAX_VERTICES)
+  const eea::FootprintFault fault = eea::footprint_planes(fp->n, fp->x, fp->y, planes);
+  return fault == eea::FootprintFault::none ? EEA_OK : fail(EEA_ERR_INVALID_ARGUMENT, eea::footprint_fault_text(fault));
+}
+
+eea_status eea_footprint_radii(const eea_footprint* fp, double* r_in, double* r_out)
+{
+  eea::FootprintPlanes planes;
+  const eea_status st = footprint_refusal(fp, planes);
+  if (st != EEA_OK) return st;
+  if (r_in != nullptr) *r_in = planes.r_in;
+  if (r_out != nullptr) *r_out = planes.r_out;
+  return EEA_OK;
+}
+
+// the checks both device calls share, in the header's order, and what the kernels read of the footprint
+static eea_status footprint_call_refusal(const eea_collision_cfg* cfg, const eea_footprint* fp, const void* d_grid, const void* d_in,
+                                         const void* d_out, eea::FootprintArgs& args)
+{
+  if (cfg == nullptr || fp == nullptr || d_grid == nullptr || d_in == nullptr || d_out == nullptr) {
+    return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  }
+  eea::FootprintPlanes planes;
+  eea_status st = footprint_refusal(fp, planes);
+  if (st == EEA_OK) st = grid_cfg_refusal(cfg);
+  if (st != EEA_OK) return st;
+  if (static_cast<unsigned long long>(cfg->xsize) * cfg->ysize > (1ull << 31)) {
+    return fail(EEA_ERR_UNSUPPORTED, "xsize * ysize above 2^31");
+  }
+  if (!eea::footprint_supported(planes, cfg->resolution)) {
+    return fail(EEA_ERR_UNSUPPORTED, "the footprint's circumscribed radius is above 1024 cells");
+  }
+  const eea::FootprintThresholds t = eea::footprint_thresholds(planes.r_in, planes.r_out, cfg->resolution);
+  args = eea::FootprintArgs{};
+  args.n = planes.n;
+  args.sq_hit = t.sq_hit;
+  args.sq_free = t.sq_free;
+  args.box = t.box;
+  args.v_min = eea::blocking_cutoff(cfg->occupied_threshold);
+  std::memcpy(args.nx, planes.nx, sizeof(args.nx));
+  std::memcpy(args.ny, planes.ny, sizeof(args.ny));
+  std::memcpy(args.h, planes.h, sizeof(args.h));
+  return EEA_OK;
+}
+
+eea_status eea_footprint_check_batch(int device, const eea_collision_cfg* cfg, const eea_footprint* fp, const int8_t* d_grid,
+                                     const int* d_sq, const double* d_pose, unsigned P, int* d_hit, void* stream)
+{
+  eea::FootprintArgs args;
+  const eea_status st = footprint_call_refusal(cfg, fp, d_grid, d_pose, d_hit, args);
+  if (st != EEA_OK) return st;
+  if (P == 0) return EEA_OK;
+  EEA_HIP(hipSetDevice(device));
+  EEA_HIP(eea::launch_footprint_check(grid_params(cfg), args, d_grid, d_sq, d_pose, P, d_hit, static_cast<hipStream_t>(stream)));
+  return EEA_OK;
+}
+
+eea_status eea_footprint_traj_first(int device, const eea_collision_cfg* cfg, const eea_footprint* fp, const int8_t* d_grid,
+                                    const int* d_sq, const double* d_traj, unsigned B, unsigned T, int* d_step, void* stream)
+{
+  eea::FootprintArgs args;
+  const eea_status st = footprint_call_refusal(cfg, fp, d_grid, d_traj, d_step, args);
+  if (st != EEA_OK) return st;
+  if (T == 0 || T > 0x7fffffffu) return fail(EEA_ERR_INVALID_ARGUMENT, "T must be between 1 and 2^31 - 1");
+  if (B == 0) return EEA_OK;
+  EEA_HIP(hipSetDevice(device));
+  EEA_HIP(eea::launch_footprint_traj_first(grid_params(cfg), args, d_grid, d_sq, d_traj, B, T, d_step,
+                                           static_cast<hipStream_t>(stream)));
   return EEA_OK;
 }
 

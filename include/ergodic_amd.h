@@ -920,6 +920,55 @@ eea_status eea_distance_traj_min(int device, const eea_collision_cfg* cfg, const
                                  const double* d_traj, unsigned B, unsigned T, eea_clearance* d_out, int* d_step, double* d_dmin,
                                  void* stream);
 
+/* ---- footprint collision: a convex polygon base, checked through the distance field ----------------------------------
+ * No reference counterpart (the reference README lists "model the robot's base as a polygon for collision detection" and "use
+ * a distance field for detecting obstacle cells" under "Future Improvements").  Every other collision call treats the robot
+ * as a disc and reads no heading; these read all three components of a pose.  They stand beside those calls and change none.
+ *
+ * The footprint: n vertices (x[k], y[k]) in the body frame, in metres, counter-clockwise and strictly convex, the body origin
+ * (the pose) strictly inside.  There is no padding: a caller who wants a margin passes a larger polygon.  Edge k runs from
+ * vertex k to vertex k + 1 (mod n); the host derives, each operation rounded on its own,
+ *   ex = x[k+1] - x[k], ey = y[k+1] - y[k], len = sqrt(ex * ex + ey * ey), (nx, ny) = (ey / len, -ex / len),
+ *   h = nx * x[k] + ny * y[k];   r_in = min h_k,   r_out = max sqrt(x[k] * x[k] + y[k] * y[k]).
+ *
+ * The verdict (the definition; the field is an optimisation of it): a pose (px, py, th) with all three components finite
+ * collides iff some in-grid cell (i, j) is occupied by checkCell's test, !(int8 / 100.0 < occupied_threshold), and its centre
+ * (GridMap::grid2World, grid.cpp:126-131) lies in the closed footprint placed at the pose:
+ *   cxw = j * res + res / 2.0 + xmin,  cyw = i * res + res / 2.0 + ymin,  dx = cxw - px,  dy = cyw - py,  (s, c) = sincos(th),
+ *   bx = c * dx + s * dy,  by = (-s) * dx + c * dy;   inside iff nx_k * bx + ny_k * by <= h_k for every k
+ * (no fused multiply-add).  A pose with a non-finite component collides with nothing.  The robot's own cell need not be on
+ * the grid: a base that hangs over the map's edge collides with the in-grid cells it covers, and nothing off the grid is an
+ * obstacle.  Sine and cosine are the device's, within a few ulp of libm: the verdict is pinned wherever no occupied centre
+ * lies within 1e-9 m of the footprint's boundary.  Of cfg only the geometry and occupied_threshold are read; the radii are
+ * neither read nor checked.
+ *
+ * d_sq (may be NULL): the plane eea_distance_field built for the same grid and threshold.  A pose whose own cell
+ * (floor((px - xmin) / res), floor((py - ymin) / res)) -- compared as doubles, no wrap, no upper-edge step -- is on the grid
+ * then reads one int: an occupied centre inside the inscribed circle is a hit, none inside the circumscribed circle is free,
+ * with 0.7072 + 1e-6 cells of margin for the pose's place in its cell; only the band in between takes the test above, over
+ * the cells within ceil(r_out / res) + 1 of the pose's.  The filter never contradicts the definition; without d_sq every
+ * pose takes the test.  Both device calls are asynchronous on `stream`, allocate nothing and keep nothing between calls;
+ * eea_abi_version() stays 6.
+ * Before the device is selected, with no output touched -- EEA_ERR_INVALID_ARGUMENT: a required pointer null (cfg, fp,
+ * d_grid, the poses, the output); n < 3 or n > EEA_FOOTPRINT_MAX_VERTICES; a vertex not finite; a turn not strictly left (the
+ * cross product of consecutive edges <= 0); some h_k <= 0; xsize or ysize 0; resolution <= 0; T == 0 or T > 2^31 - 1.
+ * EEA_ERR_UNSUPPORTED: xsize * ysize > 2^31; r_out / res > 1024. */
+#define EEA_FOOTPRINT_MAX_VERTICES 16
+typedef struct {
+  unsigned n;
+  double x[EEA_FOOTPRINT_MAX_VERTICES], y[EEA_FOOTPRINT_MAX_VERTICES];
+} eea_footprint;
+/* host only, needs no device: validates fp (the footprint's errors above) and returns the radii of the inscribed and the
+ * circumscribed circle about the body origin; r_in and r_out may each be NULL */
+eea_status eea_footprint_radii(const eea_footprint* fp, double* r_in, double* r_out);
+/* d_hit [P] = 1 (collides) or 0 per pose of d_pose [P][3].  P == 0 is EEA_OK with nothing launched. */
+eea_status eea_footprint_check_batch(int device, const eea_collision_cfg* cfg, const eea_footprint* fp, const int8_t* d_grid,
+                                     const int* d_sq, const double* d_pose, unsigned P, int* d_hit, void* stream);
+/* d_step [B] = the first colliding step of each trajectory d_traj [B][T][3] (the layout of eea_rollout_batch's output,
+ * eea_control_batch's d_traj and eea_tick_io.d_traj), -1 when none collides.  B == 0 is EEA_OK with nothing launched. */
+eea_status eea_footprint_traj_first(int device, const eea_collision_cfg* cfg, const eea_footprint* fp, const int8_t* d_grid,
+                                    const int* d_sq, const double* d_traj, unsigned B, unsigned T, int* d_step, void* stream);
+
 /* The collision / DWA / tick / clearance calls keep small device caches between calls (the ring offsets per radii, one
  * inflated-map and one key-map buffer per (device, stream), the span tables of fleet layers that no layer holds any more).  A long-running
  * process that changes streams or map sizes can drop them; synchronises the devices involved.  No reference counterpart. */
