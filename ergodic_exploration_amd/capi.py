@@ -242,6 +242,16 @@ def lib():
                                                     C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p]
             L.eea_footprint_traj_first.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.POINTER(Footprint), C.c_void_p, C.c_void_p,
                                                    C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p]
+        if hasattr(L, "eea_footprint_dwa_control_batch"):   # additive to ABI 6 as well
+            L.eea_footprint_validate_control_batch.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.POINTER(Footprint), C.c_void_p,
+                                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_uint,
+                                                               C.c_void_p, C.c_void_p]
+            L.eea_footprint_dwa_control_batch.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.POINTER(DwaCfg), C.POINTER(Footprint),
+                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                          C.c_uint, C.c_double, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.eea_tick_batch_footprint.argtypes = [C.c_void_p, C.c_uint, C.POINTER(BatchIO), C.POINTER(TickIO),
+                                                   C.POINTER(CollisionCfg), C.POINTER(DwaCfg), C.POINTER(Footprint), C.c_void_p,
+                                                   C.c_void_p]
         L.eea_replay_create.argtypes = [C.c_int, C.c_uint, C.c_uint, C.c_uint, C.c_uint64, C.c_uint, C.c_size_t, C.POINTER(C.c_void_p)]
         L.eea_replay_destroy.argtypes = [C.c_void_p]
         L.eea_replay_destroy.restype = None
@@ -543,6 +553,15 @@ class Engine:
         check(lib().eea_tick_batch_fleet(self.h, B, C.byref(io), C.byref(t), C.byref(coll), C.byref(dwa),
                                          layer.h if layer is not None else None, C.c_void_p(stream or 0)))
 
+    def tick_batch_footprint(self, fp, B, pose, ut, follow, count, u, vb, grid, traj, valid, skip, coll, dwa, val_dt, val_horizon,
+                             sq=None, source=None, mem_cols=None, n_mem=None, mem_stride=0, status=None, stream=None):
+        """eea_tick_batch_footprint: tick_batch with the polygon base fp (a Footprint) in validate_control and the dynamic
+        window; sq: the int32 plane of distance_field for the grid (rebuilt by the caller when the grid changes) or None"""
+        io, t = self._tick_io(pose, ut, follow, count, u, vb, grid, traj, valid, skip, val_dt, val_horizon, source, mem_cols,
+                              n_mem, mem_stride, status, 0)
+        check(lib().eea_tick_batch_footprint(self.h, B, C.byref(io), C.byref(t), C.byref(coll), C.byref(dwa),
+                                             C.byref(fp) if fp is not None else None, _ptr(sq), C.c_void_p(stream or 0)))
+
     def rollout_batch(self, B, pose, ut, traj, status=None, stream=None):
         check(lib().eea_rollout_batch(self.h, B, _ptr(pose), _ptr(ut), _ptr(traj), _ptr(status),
                                       C.c_void_p(stream or 0)))
@@ -709,6 +728,23 @@ def footprint_traj_first(cfg, fp, grid, traj, step, sq=None, device=0, stream=No
     footprint_check_batch.  Device tensors; asynchronous"""
     check(lib().eea_footprint_traj_first(device, C.byref(cfg), C.byref(fp), _ptr(grid), _ptr(sq), _ptr(traj), int(traj.shape[0]),
                                          int(traj.shape[1]), _ptr(step), C.c_void_p(stream or 0)))
+
+
+def footprint_validate_control_batch(cfg, fp, grid, x0, u, dt, horizon, valid, sq=None, device=0, stream=None):
+    """eea_footprint_validate_control_batch: validate_control_batch for the polygon base fp -- valid int32 [P] = 1 when no step
+    of the rollout of u [P][3] from x0 [P][3] collides; sq as in footprint_check_batch.  Device tensors; asynchronous"""
+    check(lib().eea_footprint_validate_control_batch(device, C.byref(cfg), C.byref(fp), _ptr(grid), _ptr(sq), _ptr(x0), _ptr(u),
+                                                     dt, horizon, int(x0.shape[0]), _ptr(valid), C.c_void_p(stream or 0)))
+
+
+def footprint_dwa_control_batch(ccfg, dcfg, fp, grid, x0, vb, u_opt, found, sq=None, vref=None, xt_ref=None, dt_ref=0.0, device=0,
+                                stream=None):
+    """eea_footprint_dwa_control_batch: dwa_control_batch for the polygon base fp; sq as in footprint_check_batch.  Device
+    tensors; asynchronous"""
+    n_ref = xt_ref.shape[1] if xt_ref is not None else 0
+    check(lib().eea_footprint_dwa_control_batch(device, C.byref(ccfg), C.byref(dcfg), C.byref(fp), _ptr(grid), _ptr(sq), _ptr(x0),
+                                                _ptr(vb), _ptr(vref), _ptr(xt_ref), n_ref, dt_ref, int(x0.shape[0]), _ptr(u_opt),
+                                                _ptr(found), C.c_void_p(stream or 0)))
 
 
 def release_collision_caches():

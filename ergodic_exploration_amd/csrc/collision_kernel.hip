@@ -24,6 +24,7 @@
 #include "device_tables.hpp"  // DeviceTables: ... and of the offset lists kept per device
 #include "grid_buffers.hpp"   // upload_block, acquire_map_buffer, launch_then_free: the effects of both
 #include "fleet_spans.hpp"    // FleetSpan: the row spans of the fleet layer's offset set
+#include "twist_step.hpp"     // wrap_pi_d, tick_sincos, body_displacement, advance_pose, sample_twist: the twist step
 
 namespace eea
 {
@@ -206,38 +207,6 @@ __global__ __launch_bounds__(kBlock) void collision_check_kernel(const Collision
   hit[q] = collision_check(c, grid, pose[3 * static_cast<size_t>(q)], pose[3 * static_cast<size_t>(q) + 1]) ? 1 : 0;
 }
 
-// Round 6: the constant-twist rollouts of validate_control / the dynamic window are instruction-issue bound (20 dependent steps
-// per lane of sincos + normalize_angle_PI + a byte lookup: ~245 instructions per step with the device library's sincos and the
-// literal wrap, whose quotient is an fp64 DIVISION).  EEA_TICK_FAST_TRIG (default): sin / cos by the engine's own sincospi_r
-// (exact reduction, max error 1.9e-16: common.hpp) of theta / pi, and the wrap's quotient by a multiplication with 1 / (2 pi) --
-// a quotient that lands on the other side of an integer is repaired by the wrap's own range fixes, everything else is bitwise
-// the literal form.  The outputs the reference pins are integer decisions (collision verdicts, the chosen sample), which
-// tests/test_gpu_collision_parity.py / test_gpu_dwa_parity.py / test_gpu_fleet_tick.py check bit for bit against the oracle.
-#ifndef EEA_TICK_FAST_TRIG
-#define EEA_TICK_FAST_TRIG 1
-#endif
-__device__ __forceinline__ double wrap_pi_d(double rad)
-{
-#if EEA_TICK_FAST_TRIG
-  const double pi = kPi, two_pi = 2.0 * kPi;
-  const double q = floor((rad + pi) * (1.0 / (2.0 * kPi)));
-  rad = (rad + pi) - q * two_pi;
-  if (rad < 0.0) rad += two_pi;
-  if (!(rad < two_pi)) rad -= two_pi;
-  return rad - pi;
-#else
-  return wrap_pi<double>(rad);
-#endif
-}
-__device__ __forceinline__ void tick_sincos(double th, double* s, double* c)
-{
-#if EEA_TICK_FAST_TRIG
-  sincospi_r<double>(th * (1.0 / kPi), s, c);
-#else
-  sincos(th, s, c);
-#endif
-}
-
 // one collision test through the inflated map (MAP) or by the ring search
 template <bool MAP>
 __device__ __forceinline__ bool pose_collides(const CollisionParams& c, const int8_t* __restrict__ grid,
@@ -269,41 +238,6 @@ __device__ __forceinline__ bool pose_collides(const CollisionParams& c, const in
   } else {
     return pose_collides<MAP>(c, grid, m, px, py);
   }
-}
-
-// The steps of a constant-twist rollout, written ONCE: this translation unit is compiled without FMA contraction and the sums
-// keep the reference's order and parentheses, so every caller gets the same bits.  FAST: sin / cos by tick_sincos (the
-// rollouts), otherwise by the device library (integrate_twist_kernel).
-
-// body-frame displacement of one step of the twist (u0, u1, u2) (numerics.hpp:273-297): the same every step
-template <bool FAST>
-__device__ __forceinline__ void body_displacement(double u0, double u1, double u2, double dt, double& d0, double& d1, double& d2)
-{
-  if (fabs(u2 - 0.0) < 1.0e-12) {
-    d0 = u0 * dt;
-    d1 = u1 * dt;
-    d2 = 0.0;
-  } else {
-    const double vb0 = u0 * dt, vb1 = u1 * dt, vb2 = u2 * dt;
-    double s, cc;
-    if constexpr (FAST) tick_sincos(vb2, &s, &cc);
-    else sincos(vb2, &s, &cc);
-    d0 = (vb0 * s + vb1 * (cc - 1.0)) / vb2;
-    d1 = (vb1 * s + vb0 * (1.0 - cc)) / vb2;
-    d2 = vb2;
-  }
-}
-
-// x + Rot(theta) d; the heading wrapped to [-pi, pi) (validate_control, numerics.hpp:325) or left as it is
-template <bool FAST>
-__device__ __forceinline__ void advance_pose(double& x, double& y, double& th, double d0, double d1, double d2, bool wrap)
-{
-  double s, cc;
-  if constexpr (FAST) tick_sincos(th, &s, &cc);
-  else sincos(th, &s, &cc);
-  x = x + (cc * d0 + (-s) * d1);
-  y = y + (s * d0 + cc * d1);
-  th = wrap ? wrap_pi_d(th + d2) : th + d2;
 }
 
 // numerics.hpp:273-330; LAYER: with a fleet layer, pose q is robot q's
@@ -358,19 +292,6 @@ __global__ __launch_bounds__(kBlock) void fleet_collision_check_kernel(const Col
   }
   hit[q] = h ? 1 : 0;
 }
-// velocity sample sidx = (i, j, k) in the reference's loop order; values by repeated += like the reference
-__device__ __forceinline__ void sample_twist(const DwaParams& d, const double (&lower)[3], const double (&delta)[3], unsigned sidx,
-                                             double& u0, double& u1, double& u2)
-{
-  const unsigned k = sidx % d.ns[2], j = (sidx / d.ns[2]) % d.ns[1], i = sidx / (d.ns[2] * d.ns[1]);
-  u0 = lower[0];
-  u1 = lower[1];
-  u2 = lower[2];
-  for (unsigned q = 0; q < i; ++q) u0 += delta[0];
-  for (unsigned q = 0; q < j; ++q) u1 += delta[1];
-  for (unsigned q = 0; q < k; ++q) u2 += delta[2];
-}
-
 // DynamicWindow::control (dynamic_window.cpp:92-286): one workgroup per robot, one lane per
 // velocity sample; lane 0 then takes the first strict minimum in the reference's loop order.
 constexpr int kDwaBlock = 128;

@@ -373,6 +373,20 @@ hipError_t launch_footprint_check(const CollisionParams& c, const FootprintArgs&
 // d_step [B] = the first colliding step of each trajectory d_traj [B][T][3] (T >= 1), -1: none
 hipError_t launch_footprint_traj_first(const CollisionParams& c, const FootprintArgs& f, const int8_t* d_grid, const int* d_sq,
                                        const double* d_traj, unsigned B, unsigned T, int* d_step, hipStream_t s);
+// ---- footprint planning (footprint_plan_kernel.hip): launch_validate_control / launch_dwa_control /
+// launch_validate_and_dwa_fleet with the footprint's verdict at every step; d_sq as above
+hipError_t launch_footprint_validate(const CollisionParams& c, const FootprintArgs& f, const int8_t* d_grid, const int* d_sq,
+                                     const double* d_x0, const double* d_u, double dt, unsigned steps, unsigned P, int* d_valid,
+                                     hipStream_t s);
+hipError_t launch_footprint_dwa(const CollisionParams& c, const DwaParams& d, const FootprintArgs& f, const int8_t* d_grid,
+                                const int* d_sq, const double* d_x0, const double* d_vb, const double* d_vref,
+                                const double* d_xt_ref, unsigned n_ref, double dt_ref, unsigned P, double* d_u_opt, int* d_found,
+                                hipStream_t s);
+hipError_t launch_footprint_validate_and_dwa_fleet(const CollisionParams& c, const DwaParams& d, const FootprintArgs& f,
+                                                   const int8_t* d_grid, const int* d_sq, const double* d_x0, const double* d_vb,
+                                                   const double* d_traj, unsigned n_ref, double dt_ref, double val_dt,
+                                                   unsigned val_steps, int* d_valid, int* d_follow, unsigned* d_count, double* d_u,
+                                                   int* d_source, unsigned P, hipStream_t s);
 
 // ---- fleet layer: robots as obstacles to one another (fleet_layer_kernel.hip, fleet_spans.hpp) ----
 // What the collision kernels read of a layer.  count [h][w] over the centres [-R, xsize + R) x [-R, ysize + R) (the geometry

@@ -2125,6 +2125,51 @@ eea_status eea_footprint_traj_first(int device, const eea_collision_cfg* cfg, co
   return EEA_OK;
 }
 
+// ---- footprint planning: the polygon base in validate_control and the dynamic window (footprint_plan_kernel.hip) ----
+eea_status eea_footprint_validate_control_batch(int device, const eea_collision_cfg* cfg, const eea_footprint* fp,
+                                                const int8_t* d_grid, const int* d_sq, const double* d_x0, const double* d_u,
+                                                double dt, double horizon, unsigned P, int* d_valid, void* stream)
+{
+  eea::FootprintArgs args;
+  const eea_status st = footprint_call_refusal(cfg, fp, d_grid, d_x0, d_valid, args);
+  if (st != EEA_OK) return st;
+  if (d_u == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  if (P == 0) return EEA_OK;
+  const unsigned steps = static_cast<unsigned>(std::abs(horizon / dt));  // numerics.hpp:317
+  EEA_HIP(hipSetDevice(device));
+  EEA_HIP(eea::launch_footprint_validate(grid_params(cfg), args, d_grid, d_sq, d_x0, d_u, dt, steps, P, d_valid,
+                                         static_cast<hipStream_t>(stream)));
+  return EEA_OK;
+}
+
+eea_status eea_footprint_dwa_control_batch(int device, const eea_collision_cfg* ccfg, const eea_dwa_cfg* dcfg,
+                                           const eea_footprint* fp, const int8_t* d_grid, const int* d_sq, const double* d_x0,
+                                           const double* d_vb, const double* d_vref, const double* d_xt_ref, unsigned n_ref,
+                                           double dt_ref, unsigned P, double* d_u_opt, int* d_found, void* stream)
+{
+  eea::FootprintArgs args;
+  eea_status st = footprint_call_refusal(ccfg, fp, d_grid, d_x0, d_u_opt, args);
+  if (st != EEA_OK) return st;
+  // eea_dwa_control_batch's, in its order
+  if (dcfg == nullptr || d_vb == nullptr || d_found == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  if ((d_vref == nullptr) == (d_xt_ref == nullptr)) {
+    return fail(EEA_ERR_INVALID_ARGUMENT, "give either d_vref or d_xt_ref");
+  }
+  if (d_xt_ref != nullptr && n_ref == 0) return fail(EEA_ERR_INVALID_ARGUMENT, "empty reference trajectory");
+  eea::DwaParams d;
+  st = make_dwa_params(dcfg, d);
+  if (st != EEA_OK) return st;
+  if (d_xt_ref != nullptr) {
+    st = check_reference_index(d, n_ref, dt_ref);
+    if (st != EEA_OK) return st;
+  }
+  if (P == 0) return EEA_OK;
+  EEA_HIP(hipSetDevice(device));
+  EEA_HIP(eea::launch_footprint_dwa(grid_params(ccfg), d, args, d_grid, d_sq, d_x0, d_vb, d_vref, d_xt_ref, n_ref, dt_ref, P,
+                                    d_u_opt, d_found, static_cast<hipStream_t>(stream)));
+  return EEA_OK;
+}
+
 void eea_release_collision_caches(void)
 {
   eea::release_collision_caches();
@@ -2250,13 +2295,19 @@ struct eea_fleet_layer
 };
 
 // One tick of Exploration<ModelT>::control's loop body for B robots (exploration.hpp:220-279): see ergodic_amd.h.  with_layer: the
-// call is eea_tick_batch_fleet -- `layer` must not be null and is used in steps 3 and 4, and the messages name that entry
+// call is eea_tick_batch_fleet -- `layer` must not be null and is used in steps 3 and 4, and the messages name that entry.
+// foot: the call is eea_tick_batch_footprint -- steps 3 and 4 judge every pose by the polygon base (no layer then)
+struct FootprintTick
+{
+  const eea_footprint* fp;
+  const int* d_sq;
+};
 static eea_status tick_batch_impl(eea_engine* e, unsigned B, const eea_batch_io* io, const eea_tick_io* tick,
                                   const eea_collision_cfg* ccfg, const eea_dwa_cfg* dcfg, const eea_fleet_layer* layer,
-                                  bool with_layer, void* stream)
+                                  bool with_layer, void* stream, const FootprintTick* foot = nullptr)
 {
   // (refusals of several kinds, B == 0 and the parameter blocks come before the device is touched: no shared prologue)
-  const char* const entry = with_layer ? "eea_tick_batch_fleet" : "eea_tick_batch";  // (for the refusal messages)
+  const char* const entry = foot != nullptr ? "eea_tick_batch_footprint" : with_layer ? "eea_tick_batch_fleet" : "eea_tick_batch";  // (for the refusal messages)
   if (e == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null engine");
   if (io == nullptr || tick == nullptr || dcfg == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
   if (e->f32) return fail(EEA_ERR_UNSUPPORTED, std::string(entry) + " takes fp64 engines (poses and twists are doubles)");
@@ -2269,10 +2320,16 @@ static eea_status tick_batch_impl(eea_engine* e, unsigned B, const eea_batch_io*
     return fail(EEA_ERR_UNSUPPORTED, std::string(entry) + " does not take the device-bound exchange buffers");
   }
   if (with_layer && layer == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null fleet layer");
+  eea::FootprintArgs fargs;
+  if (foot != nullptr) {  // the footprint, the grid's geometry and the cell limits, as eea_footprint_check_batch asks them
+    const eea_status fst = footprint_call_refusal(ccfg, foot->fp, tick->d_grid, io->d_pose, tick->d_valid, fargs);
+    if (fst != EEA_OK) return fst;
+  }
   if (B == 0 && !with_layer) return EEA_OK;
-  eea_status st = collision_cfg_refusal(ccfg);
+  // (the footprint reads the geometry and occupied_threshold only: the radii are neither read nor checked)
+  eea_status st = foot != nullptr ? EEA_OK : collision_cfg_refusal(ccfg);
   if (st != EEA_OK) return st;
-  const eea::CollisionParams c = collision_params(ccfg);
+  const eea::CollisionParams c = foot != nullptr ? grid_params(ccfg) : collision_params(ccfg);
   if (with_layer) {
     if (B != layer->v.B) return fail(EEA_ERR_INVALID_ARGUMENT, "the tick's B is not the fleet layer's");
     if (!eea::same_params(c, layer->c)) {
@@ -2309,6 +2366,13 @@ static eea_status tick_batch_impl(eea_engine* e, unsigned B, const eea_batch_io*
   // 3. validate_control (:238, numerics.hpp:312-330); 4. the dynamic window where the twist was rejected (:240-277), u /
   // follow_dwa / i updated in place.  One inflated map for both
   const unsigned val_steps = static_cast<unsigned>(std::abs(tick->val_horizon / tick->val_dt));
+  if (foot != nullptr) {  // (tick->grid_epoch is not read: no inflated map)
+    EEA_HIP(eea::launch_footprint_validate_and_dwa_fleet(c, d, fargs, tick->d_grid, foot->d_sq, static_cast<const double*>(io->d_pose),
+                                                         tick->d_vb, tick->d_traj, static_cast<unsigned>(e->T), e->cfg.dt,
+                                                         tick->val_dt, val_steps, tick->d_valid, tick->d_follow_dwa,
+                                                         tick->d_dwa_count, tick->d_u, tick->d_source, B, s));
+    return EEA_OK;
+  }
   if (with_layer) {
     EEA_HIP(eea::launch_validate_and_dwa_fleet_layer(c, d, layer->v, tick->d_grid, tick->grid_epoch,
                                                      static_cast<const double*>(io->d_pose), tick->d_vb, tick->d_traj,
@@ -2335,6 +2399,14 @@ eea_status eea_tick_batch_fleet(eea_engine* e, unsigned B, const eea_batch_io* i
                                 const eea_collision_cfg* ccfg, const eea_dwa_cfg* dcfg, const eea_fleet_layer* l, void* stream)
 {
   return tick_batch_impl(e, B, io, tick, ccfg, dcfg, l, true, stream);
+}
+
+eea_status eea_tick_batch_footprint(eea_engine* e, unsigned B, const eea_batch_io* io, const eea_tick_io* tick,
+                                    const eea_collision_cfg* ccfg, const eea_dwa_cfg* dcfg, const eea_footprint* fp,
+                                    const int* d_sq, void* stream)
+{
+  const FootprintTick foot{ fp, d_sq };
+  return tick_batch_impl(e, B, io, tick, ccfg, dcfg, nullptr, false, stream, &foot);
 }
 
 eea_status eea_fleet_layer_create(int device, const eea_collision_cfg* cfg, int body_cells, unsigned B, eea_fleet_layer** out)

@@ -2,7 +2,8 @@
 // velocity window from the current twist and the acceleration limits, a vx x vy x vth sample grid,
 // constant-twist rollouts with a collision check per step, and either the control-error cost or
 // the distance-to-reference-trajectory cost.  The search runs in the batched device kernel
-// (eea_dwa_control_batch), one lane per velocity sample.
+// (eea_dwa_control_batch), one lane per velocity sample.  The overloads that take a Footprint judge every step by that polygon
+// base instead of the Collision's disc (eea_footprint_dwa_control_batch; no reference counterpart).
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -14,6 +15,7 @@
 #include <tuple>
 
 #include <ergodic_exploration/collision.hpp>
+#include <ergodic_exploration/footprint.hpp>
 
 namespace ergodic_exploration
 {
@@ -58,6 +60,19 @@ public:
     return run(grid, x0, vb, nullptr, &xt_ref, dt_ref);
   }
 
+  // ... for a polygon base: every step of every sample judged by `base` (through `field`, a DistanceField of the same map and
+  // threshold, when given: the same answers) instead of the Collision's disc
+  std::tuple<bool, vec> control(const GridMap& grid, const vec& x0, const vec& vb, const vec& vref, const Footprint& base,
+                                const DistanceField* field = nullptr) const
+  {
+    return run(grid, x0, vb, &vref, nullptr, 0.0, &base, field);
+  }
+  std::tuple<bool, vec> control(const GridMap& grid, const vec& x0, const vec& vb, const mat& xt_ref, double dt_ref,
+                                const Footprint& base, const DistanceField* field = nullptr) const
+  {
+    return run(grid, x0, vb, nullptr, &xt_ref, dt_ref, &base, field);
+  }
+
   // rollout length of the planner (dynamic_window.hpp accessors used by Exploration)
   unsigned int steps() const { return static_cast<unsigned int>(std::abs(cfg_.horizon / cfg_.dt)); }
   double timeStep() const { return cfg_.dt; }
@@ -76,7 +91,7 @@ private:
     return n;
   }
   std::tuple<bool, vec> run(const GridMap& grid, const vec& x0, const vec& vb, const vec* vref, const mat* xt_ref,
-                            double dt_ref) const
+                            double dt_ref, const Footprint* base = nullptr, const DistanceField* field = nullptr) const
   {
     const size_t n_ref = xt_ref ? xt_ref->n_cols() : 0;
     const int8_t* const d_grid = device_cells(grid);
@@ -96,12 +111,18 @@ private:
       d_ref = static_cast<double*>(device_scratch(sizeof(double) * 3 * n_ref));
       hip_check(hipMemcpyAsync(d_ref, xt_ref->memptr(), sizeof(double) * 3 * n_ref, hipMemcpyHostToDevice, nullptr));
     }
-    const eea_collision_cfg ccfg = collision_.deviceConfig(grid);
-    const eea_status st =
-        eea_dwa_control_batch(device_ordinal(), &ccfg, &cfg_, d_grid, d_buf, d_buf + 3, vref ? d_buf + 6 : nullptr, d_ref,
-                              static_cast<unsigned>(n_ref), dt_ref, 1, d_buf + 9, reinterpret_cast<int*>(d_buf + 12),
-                              nullptr);
-    throw_on_error(st);
+    if (base != nullptr) {
+      const eea_collision_cfg ccfg = base->deviceConfig(grid);
+      throw_on_error(eea_footprint_dwa_control_batch(device_ordinal(), &ccfg, &cfg_, &base->deviceFootprint(), d_grid,
+                                                     field ? field->squaredDistances() : nullptr, d_buf, d_buf + 3,
+                                                     vref ? d_buf + 6 : nullptr, d_ref, static_cast<unsigned>(n_ref), dt_ref, 1,
+                                                     d_buf + 9, reinterpret_cast<int*>(d_buf + 12), nullptr));
+    } else {
+      const eea_collision_cfg ccfg = collision_.deviceConfig(grid);
+      throw_on_error(eea_dwa_control_batch(device_ordinal(), &ccfg, &cfg_, d_grid, d_buf, d_buf + 3, vref ? d_buf + 6 : nullptr,
+                                           d_ref, static_cast<unsigned>(n_ref), dt_ref, 1, d_buf + 9,
+                                           reinterpret_cast<int*>(d_buf + 12), nullptr));
+    }
     hip_check(hipStreamSynchronize(nullptr));  // also covers the pageable copy above
     vec u(3);
     for (int c = 0; c < 3; ++c) u(c) = h[9 + c];

@@ -1,5 +1,6 @@
 // Footprint: the robot's base as a convex polygon, checked against a GridMap's occupied cells on the device
-// (eea_footprint_radii / eea_footprint_check_batch / eea_footprint_traj_first).  No reference class: the reference README lists
+// (eea_footprint_radii / eea_footprint_check_batch / eea_footprint_traj_first / eea_footprint_validate_control_batch; the
+// dynamic window for such a base: DynamicWindow::control's overloads that take a Footprint).  No reference class: the reference README lists
 // a polygon base under "Future Improvements".  Beside Collision, which treats the robot as a disc and reads no heading.  A pose
 // collides iff an occupied in-grid cell has its centre in the closed polygon placed at the pose; a DistanceField of the same
 // map and the same occupied threshold, when given, decides most poses with one lookup and never changes an answer.
@@ -57,7 +58,7 @@ public:
     const size_t pose_bytes = sizeof(double) * 3 * P;
     const PinnedScratch sc = pinned_scratch(pose_bytes + sizeof(int) * P);
     std::memcpy(sc.host, poses.memptr(), pose_bytes);
-    const eea_collision_cfg cfg = config(grid);
+    const eea_collision_cfg cfg = deviceConfig(grid);
     throw_on_error(eea_footprint_check_batch(device_ordinal(), &cfg, &fp_, d_grid, field ? field->squaredDistances() : nullptr,
                                              static_cast<const double*>(sc.dev), P,
                                              reinterpret_cast<int*>(static_cast<char*>(sc.dev) + pose_bytes), nullptr));
@@ -74,7 +75,7 @@ public:
     const size_t traj_bytes = sizeof(double) * 3 * T;
     const PinnedScratch sc = pinned_scratch(traj_bytes + sizeof(int));
     std::memcpy(sc.host, traj.memptr(), traj_bytes);
-    const eea_collision_cfg cfg = config(grid);
+    const eea_collision_cfg cfg = deviceConfig(grid);
     throw_on_error(eea_footprint_traj_first(device_ordinal(), &cfg, &fp_, d_grid, field ? field->squaredDistances() : nullptr,
                                             static_cast<const double*>(sc.dev), 1, T,
                                             reinterpret_cast<int*>(static_cast<char*>(sc.dev) + traj_bytes), nullptr));
@@ -84,11 +85,31 @@ public:
     return step;
   }
 
+  // validate_control (numerics.hpp:312-330) for this base: true when no step of the rollout of the twist u from x0 collides
+  bool validateControl(const GridMap& grid, const vec& x0, const vec& u, double dt, double horizon,
+                       const DistanceField* field = nullptr) const
+  {
+    const int8_t* const d_grid = device_cells(grid);
+    const PinnedScratch sc = pinned_scratch(sizeof(double) * 7);  // x0 | u | valid
+    double* const h = static_cast<double*>(sc.host);
+    double* const d_buf = static_cast<double*>(sc.dev);
+    for (int c = 0; c < 3; ++c) {
+      h[c] = x0(c);
+      h[3 + c] = u(c);
+    }
+    const eea_collision_cfg cfg = deviceConfig(grid);
+    throw_on_error(eea_footprint_validate_control_batch(device_ordinal(), &cfg, &fp_, d_grid, field ? field->squaredDistances() : nullptr,
+                                                        d_buf, d_buf + 3, dt, horizon, 1, reinterpret_cast<int*>(d_buf + 6), nullptr));
+    hip_check(hipStreamSynchronize(nullptr));
+    int valid = 0;
+    std::memcpy(&valid, &h[6], sizeof(int));
+    return valid != 0;
+  }
+
   const eea_footprint& deviceFootprint() const { return fp_; }
 
-private:
   // the geometry and the occupied threshold; the calls read no radius
-  eea_collision_cfg config(const GridMap& grid) const
+  eea_collision_cfg deviceConfig(const GridMap& grid) const
   {
     eea_collision_cfg c{};
     c.xmin = grid.xmin();
@@ -99,6 +120,8 @@ private:
     c.occupied_threshold = occupied_threshold_;
     return c;
   }
+
+private:
   eea_footprint fp_;
   double occupied_threshold_;
   double r_in_ = 0.0, r_out_ = 0.0;

@@ -969,6 +969,36 @@ eea_status eea_footprint_check_batch(int device, const eea_collision_cfg* cfg, c
 eea_status eea_footprint_traj_first(int device, const eea_collision_cfg* cfg, const eea_footprint* fp, const int8_t* d_grid,
                                     const int* d_sq, const double* d_traj, unsigned B, unsigned T, int* d_step, void* stream);
 
+/* ---- footprint planning: the polygon base in validate_control, the dynamic window and the tick -------------------------
+ * The three calls that decide a robot's motion, with the verdict above in place of the disc's collisionCheck.  They are defined
+ * by composition and add no numerics: the poses of a rollout are those of eea_validate_control_batch / eea_dwa_control_batch
+ * bit for bit (the same twist step, the heading wrapped), every pose is judged as eea_footprint_check_batch judges a pose, and
+ * the window bounds, both objectives, the first strict minimum in loop order, found and u_opt = 0 are eea_dwa_control_batch's.
+ * Sine and cosine of a pose's heading are the rollout's own; the verdict is pinned under the rule above (no occupied centre
+ * within 1e-9 m of the polygon's boundary).  d_sq may be NULL; with it the outputs are the same bits.  Of the collision cfg only
+ * the geometry and occupied_threshold are read.  Additive to ABI 6 (eea_abi_version() stays 6); asynchronous on `stream`, nothing
+ * allocated, nothing kept between calls.  P == 0 / B == 0 is EEA_OK with nothing launched.
+ * Refusals, before the device is selected and with no output touched: eea_footprint_check_batch's for cfg / fp / d_grid
+ * (r_out / res > 1024 included), then eea_validate_control_batch's / eea_dwa_control_batch's for the rest (null pointers; both or
+ * neither of d_vref / d_xt_ref; n_ref == 0; more than 8192 samples; a rollout that would read past its reference). */
+/* validate_control (numerics.hpp:312-330): d_valid [P] = 1 when no step of the rollout of d_u [P][3] from d_x0 [P][3] collides */
+eea_status eea_footprint_validate_control_batch(int device, const eea_collision_cfg* cfg, const eea_footprint* fp,
+                                                const int8_t* d_grid, const int* d_sq, const double* d_x0, const double* d_u,
+                                                double dt, double horizon, unsigned P, int* d_valid, void* stream);
+/* DynamicWindow::control (dynamic_window.cpp:92-286), both modes as in eea_dwa_control_batch (d_vref, or d_xt_ref / n_ref /
+ * dt_ref) */
+eea_status eea_footprint_dwa_control_batch(int device, const eea_collision_cfg* ccfg, const eea_dwa_cfg* dcfg,
+                                           const eea_footprint* fp, const int8_t* d_grid, const int* d_sq, const double* d_x0,
+                                           const double* d_vb, const double* d_vref, const double* d_xt_ref, unsigned n_ref,
+                                           double dt_ref, unsigned P, double* d_u_opt, int* d_found, void* stream);
+/* eea_tick_batch with the footprint in steps 3 and 4; steps 1 and 2 are eea_tick_batch's, and d_valid, d_follow_dwa,
+ * d_dwa_count, d_u and d_source mean what they mean there.  tick->grid_epoch is ignored (there is no inflated map to cache):
+ * the caller rebuilds d_sq with eea_distance_field when the grid changes.  Refusals: eea_tick_batch's, in its order, with fp
+ * and the grid's geometry checked where eea_tick_batch_fleet checks its layer. */
+eea_status eea_tick_batch_footprint(eea_engine* e, unsigned B, const eea_batch_io* io, const eea_tick_io* tick,
+                                    const eea_collision_cfg* ccfg, const eea_dwa_cfg* dcfg, const eea_footprint* fp,
+                                    const int* d_sq, void* stream);
+
 /* The collision / DWA / tick / clearance calls keep small device caches between calls (the ring offsets per radii, one
  * inflated-map and one key-map buffer per (device, stream), the span tables of fleet layers that no layer holds any more).  A long-running
  * process that changes streams or map sizes can drop them; synchronises the devices involved.  No reference counterpart. */
