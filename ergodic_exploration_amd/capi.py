@@ -276,6 +276,23 @@ def lib():
         L.eea_sense_gain_field.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
         L.eea_set_target_gain.argtypes = [C.c_void_p, C.POINTER(CollisionCfg), C.c_uint, C.c_uint, C.c_void_p, C.c_double,
                                           C.c_double, C.c_double, C.c_void_p, C.c_void_p]
+        if hasattr(L, "eea_body_layer_create"):   # additive to ABI 6 as well
+            L.eea_body_layer_create.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.POINTER(Footprint), C.c_uint, C.c_uint,
+                                                C.POINTER(C.c_void_p)]
+            L.eea_body_layer_destroy.argtypes = [C.c_void_p]
+            L.eea_body_layer_destroy.restype = None
+            L.eea_body_layer_update.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.eea_body_layer_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.eea_body_layer_box.argtypes = [C.c_void_p]
+            L.eea_body_collision_check_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint,
+                                                         C.c_void_p, C.c_void_p]
+            L.eea_body_validate_control_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                          C.c_double, C.c_double, C.c_uint, C.c_void_p, C.c_void_p]
+            L.eea_body_dwa_control_batch.argtypes = [C.c_void_p, C.POINTER(DwaCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_uint, C.c_double, C.c_void_p, C.c_uint,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p]
+            L.eea_tick_batch_bodies.argtypes = [C.c_void_p, C.c_uint, C.POINTER(BatchIO), C.POINTER(TickIO),
+                                                C.POINTER(CollisionCfg), C.POINTER(DwaCfg), C.c_void_p, C.c_void_p, C.c_void_p]
         if hasattr(L, "eea_fleet_layer_create"):   # additive to ABI 6: found by symbol (an older library has none of them)
             L.eea_fleet_layer_create.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_int, C.c_uint, C.POINTER(C.c_void_p)]
             L.eea_fleet_layer_destroy.argtypes = [C.c_void_p]
@@ -562,6 +579,16 @@ class Engine:
         check(lib().eea_tick_batch_footprint(self.h, B, C.byref(io), C.byref(t), C.byref(coll), C.byref(dwa),
                                              C.byref(fp) if fp is not None else None, _ptr(sq), C.c_void_p(stream or 0)))
 
+    def tick_batch_bodies(self, layer, B, pose, ut, follow, count, u, vb, grid, traj, valid, skip, coll, dwa, val_dt, val_horizon,
+                          sq=None, source=None, mem_cols=None, n_mem=None, mem_stride=0, status=None, stream=None):
+        """eea_tick_batch_bodies: tick_batch_footprint with the BodyLayer `layer` in validate_control and the dynamic window --
+        the other robots' polygon bodies are obstacles; robot r of the tick is robot r of the layer (updated on the same
+        stream before).  The footprint is the layer's"""
+        io, t = self._tick_io(pose, ut, follow, count, u, vb, grid, traj, valid, skip, val_dt, val_horizon, source, mem_cols,
+                              n_mem, mem_stride, status, 0)
+        check(lib().eea_tick_batch_bodies(self.h, B, C.byref(io), C.byref(t), C.byref(coll) if coll is not None else None,
+                                          C.byref(dwa), layer.h if layer is not None else None, _ptr(sq), C.c_void_p(stream or 0)))
+
     def rollout_batch(self, B, pose, ut, traj, status=None, stream=None):
         check(lib().eea_rollout_batch(self.h, B, _ptr(pose), _ptr(ut), _ptr(traj), _ptr(status),
                                       C.c_void_p(stream or 0)))
@@ -846,6 +873,70 @@ class FleetLayer:
     def close(self):
         if self.h:
             lib().eea_fleet_layer_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+BODY_LAYER_NO_FILTER = 1   # EEA_BODY_LAYER_NO_FILTER
+
+
+class BodyLayer:
+    """eea_body_layer: the B robots of a fleet, each the convex polygon fp (a Footprint), as obstacles to one another
+    (include/ergodic_amd.h states the rule).  cfg: the make_collision_cfg(...) of the grid -- the geometry and
+    occupied_threshold are read.  update() builds the layer from the poses on the stream; check / validate / dwa and
+    Engine.tick_batch_bodies read it.  self_index [P] int32: the robot each pose belongs to (-1 / None: nobody)"""
+    SNAP = 5    # doubles per snapshot record: px, py, sine, cosine, stamped
+
+    def __init__(self, cfg, fp, B, flags=0, device=0):
+        self.h = C.c_void_p()
+        check(lib().eea_body_layer_create(device, C.byref(cfg) if cfg is not None else None, C.byref(fp) if fp is not None else None,
+                                          int(B), int(flags), C.byref(self.h)))
+        self.cfg, self.fp, self.B, self.flags = cfg, fp, int(B), int(flags)
+        self.box = int(lib().eea_body_layer_box(self.h))
+        self.cover_shape = (cfg.ysize, cfg.xsize)
+        self.near_shape = (cfg.ysize + 2 * self.box, cfg.xsize + 2 * self.box)   # the cells [-box, size + box)
+
+    def update(self, pose, mask=None, stream=None):
+        """pose [B][3] float64, mask [B] int32 or None: device tensors; asynchronous"""
+        check(lib().eea_body_layer_update(self.h, _ptr(pose), _ptr(mask), C.c_void_p(stream or 0)))
+
+    def read(self):
+        """(cover [ysize][xsize], near [ysize + 2 box][xsize + 2 box], snapshot [B][5]) as numpy arrays; synchronises"""
+        import numpy as np
+        cover, near = np.empty(self.cover_shape, dtype=np.int32), np.empty(self.near_shape, dtype=np.int32)
+        snap = np.empty((self.B, self.SNAP), dtype=np.float64)
+        check(lib().eea_body_layer_read(self.h, _ptr(cover), _ptr(near), _ptr(snap)))
+        return cover, near, snap
+
+    def check(self, grid, pose, hit, sq=None, self_index=None, stream=None):
+        """eea_body_collision_check_batch: hit [P] int32 = the footprint's verdict of pose [P][3] on grid (None: robots only)
+        OR a shared cell with the body of a robot other than self_index"""
+        check(lib().eea_body_collision_check_batch(self.h, _ptr(grid), _ptr(sq), _ptr(pose), _ptr(self_index),
+                                                   int(pose.shape[0]) if pose is not None else 0, _ptr(hit),
+                                                   C.c_void_p(stream or 0)))
+
+    def validate(self, grid, x0, u, dt, horizon, valid, sq=None, self_index=None, stream=None):
+        """eea_body_validate_control_batch: footprint_validate_control_batch with the layer"""
+        check(lib().eea_body_validate_control_batch(self.h, _ptr(grid), _ptr(sq), _ptr(x0), _ptr(u), _ptr(self_index), dt, horizon,
+                                                    int(x0.shape[0]) if x0 is not None else 0, _ptr(valid),
+                                                    C.c_void_p(stream or 0)))
+
+    def dwa(self, dcfg, grid, x0, vb, u_opt, found, sq=None, vref=None, xt_ref=None, dt_ref=0.0, self_index=None, stream=None):
+        """eea_body_dwa_control_batch: footprint_dwa_control_batch with the layer"""
+        n_ref = xt_ref.shape[1] if xt_ref is not None else 0
+        check(lib().eea_body_dwa_control_batch(self.h, C.byref(dcfg) if dcfg is not None else None, _ptr(grid), _ptr(sq), _ptr(x0),
+                                               _ptr(vb), _ptr(vref), _ptr(xt_ref), n_ref, dt_ref, _ptr(self_index),
+                                               int(x0.shape[0]) if x0 is not None else 0, _ptr(u_opt), _ptr(found),
+                                               C.c_void_p(stream or 0)))
+
+    def close(self):
+        if self.h:
+            lib().eea_body_layer_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):

@@ -425,6 +425,51 @@ hipError_t launch_validate_and_dwa_fleet_layer(const CollisionParams& c, const D
                                                unsigned val_steps, int* d_valid, int* d_follow, unsigned* d_count, double* d_u,
                                                int* d_source, unsigned P, hipStream_t s);
 
+// the layers' in-place inclusive prefix sum along every row of an int32 map [h][w] (fleet_layer_kernel.hip)
+hipError_t launch_fleet_row_scan(int* d_map, int w, int h, hipStream_t s);
+
+// ---- body layer: polygon robots as obstacles to one another (body_layer_kernel.hip) ----
+// What the footprint kernels read of a layer.  cover [ysize][xsize]: the number of stamped robots whose body holds the cell.
+// near [ysize + 2 box][xsize + 2 box] over the cells [-box, xsize + box) x [-box, ysize + box): the stamped robots whose cell
+// lies within Chebyshev distance Rn of this one (a filter: 0 proves that no body shares a cell with a polygon placed here).
+// snap [B][kBodySnap]: px, py, the sine and the cosine the stamp used, 1.0 / 0.0 = stamped or not.
+constexpr int kBodySnap = 5;
+constexpr unsigned kBodyLayerNoFilter = 1u;  // EEA_BODY_LAYER_NO_FILTER
+struct BodyView
+{
+  const int* cover = nullptr;
+  const int* near = nullptr;
+  const double* snap = nullptr;
+  int box = 0, Rn = 0, near_w = 0, near_h = 0;
+  unsigned B = 0, flags = 0;
+};
+// the view and whose pose a query is: self [P] (null: nobody's, or with self_is_index the query's own index)
+struct BodyArgs
+{
+  BodyView v;
+  const int* self = nullptr;
+  int self_is_index = 0;
+};
+// One update: a clear of both maps (one allocation, cover first), one stamp kernel, the row scans.  No host wait
+hipError_t launch_body_layer_update(const CollisionParams& c, const FootprintArgs& f, const BodyView& v, int* d_maps, double* d_snap,
+                                    const double* d_pose, const int* d_mask, hipStream_t s);
+// the footprint's verdict of P poses on the grid (may be null: robots only) with the bodies of the others
+hipError_t launch_body_check(const CollisionParams& c, const FootprintArgs& f, const BodyArgs& a, const int8_t* d_grid,
+                             const int* d_sq, const double* d_pose, unsigned P, int* d_hit, hipStream_t s);
+// launch_footprint_validate / _dwa / _validate_and_dwa_fleet with the layer in every verdict (footprint_plan_kernel.hip)
+hipError_t launch_body_validate(const CollisionParams& c, const FootprintArgs& f, const BodyArgs& a, const int8_t* d_grid,
+                                const int* d_sq, const double* d_x0, const double* d_u, double dt, unsigned steps, unsigned P,
+                                int* d_valid, hipStream_t s);
+hipError_t launch_body_dwa(const CollisionParams& c, const DwaParams& d, const FootprintArgs& f, const BodyArgs& a,
+                           const int8_t* d_grid, const int* d_sq, const double* d_x0, const double* d_vb, const double* d_vref,
+                           const double* d_xt_ref, unsigned n_ref, double dt_ref, unsigned P, double* d_u_opt, int* d_found,
+                           hipStream_t s);
+hipError_t launch_body_validate_and_dwa_fleet(const CollisionParams& c, const DwaParams& d, const FootprintArgs& f, const BodyView& v,
+                                              const int8_t* d_grid, const int* d_sq, const double* d_x0, const double* d_vb,
+                                              const double* d_traj, unsigned n_ref, double dt_ref, double val_dt,
+                                              unsigned val_steps, int* d_valid, int* d_follow, unsigned* d_count, double* d_u,
+                                              int* d_source, unsigned P, hipStream_t s);
+
 // ---- range sensing of a simulated fleet (sense_kernel.hip) -------------------------------
 // every robot's 8 * range_cells rays through d_truth: the cells they cross are copied into d_known, d_ranges [P][8R]
 // (optional) = the step at which a ray met a blocking cell or -1; c: the geometry and occupied_threshold (radii unused)

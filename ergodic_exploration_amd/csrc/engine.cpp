@@ -2069,13 +2069,11 @@ eea_status eea_footprint_radii(const eea_footprint* fp, double* r_in, double* r_
   return EEA_OK;
 }
 
-// the checks both device calls share, in the header's order, and what the kernels read of the footprint
-static eea_status footprint_call_refusal(const eea_collision_cfg* cfg, const eea_footprint* fp, const void* d_grid, const void* d_in,
-                                         const void* d_out, eea::FootprintArgs& args)
+// the footprint on the grid of cfg (both given), in the header's order, and what the kernels read of the footprint; r_out:
+// the circumscribed radius (may be null)
+static eea_status footprint_on_grid_refusal(const eea_collision_cfg* cfg, const eea_footprint* fp, eea::FootprintArgs& args,
+                                            double* r_out = nullptr)
 {
-  if (cfg == nullptr || fp == nullptr || d_grid == nullptr || d_in == nullptr || d_out == nullptr) {
-    return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
-  }
   eea::FootprintPlanes planes;
   eea_status st = footprint_refusal(fp, planes);
   if (st == EEA_OK) st = grid_cfg_refusal(cfg);
@@ -2096,7 +2094,18 @@ static eea_status footprint_call_refusal(const eea_collision_cfg* cfg, const eea
   std::memcpy(args.nx, planes.nx, sizeof(args.nx));
   std::memcpy(args.ny, planes.ny, sizeof(args.ny));
   std::memcpy(args.h, planes.h, sizeof(args.h));
+  if (r_out != nullptr) *r_out = planes.r_out;
   return EEA_OK;
+}
+
+// the checks the footprint's device calls share
+static eea_status footprint_call_refusal(const eea_collision_cfg* cfg, const eea_footprint* fp, const void* d_grid, const void* d_in,
+                                         const void* d_out, eea::FootprintArgs& args)
+{
+  if (cfg == nullptr || fp == nullptr || d_grid == nullptr || d_in == nullptr || d_out == nullptr) {
+    return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  }
+  return footprint_on_grid_refusal(cfg, fp, args);
 }
 
 eea_status eea_footprint_check_batch(int device, const eea_collision_cfg* cfg, const eea_footprint* fp, const int8_t* d_grid,
@@ -2294,20 +2303,47 @@ struct eea_fleet_layer
   int* d_cell = nullptr;
 };
 
+// ---- body layer: polygon robots as obstacles to one another (body_layer_kernel.hip) ----------------
+struct eea_body_layer
+{
+  int device = 0;
+  unsigned flags = 0;
+  eea_footprint fp{};
+  eea::CollisionParams c{};  // the grid's geometry and threshold (grid_params)
+  eea::FootprintArgs f{};
+  eea::BodyView v{};         // (cover / near / snap point into d_maps / d_snap)
+  int* d_block = nullptr;    // the allocation: kBodyGuard guard words, the maps, kBodyGuard guard words
+  int* d_maps = nullptr;     // cover [ysize][xsize], then near [near_h][near_w]: one clear
+  double* d_snap = nullptr;
+};
+
+// guard words on either side of the maps, written at creation and verified by eea_body_layer_read: a stamp outside the maps
+// is seen by the tests
+constexpr size_t kBodyGuard = 64;
+constexpr int kBodyGuardWord = 0x5a5a5a5a;
+
 // One tick of Exploration<ModelT>::control's loop body for B robots (exploration.hpp:220-279): see ergodic_amd.h.  with_layer: the
 // call is eea_tick_batch_fleet -- `layer` must not be null and is used in steps 3 and 4, and the messages name that entry.
 // foot: the call is eea_tick_batch_footprint -- steps 3 and 4 judge every pose by the polygon base (no layer then)
+// bodies: the call is eea_tick_batch_bodies -- the footprint is the body layer's, and steps 3 and 4 take the other robots'
+// bodies from it
 struct FootprintTick
 {
   const eea_footprint* fp;
   const int* d_sq;
+  bool with_bodies = false;
+  const eea_body_layer* bodies = nullptr;
 };
 static eea_status tick_batch_impl(eea_engine* e, unsigned B, const eea_batch_io* io, const eea_tick_io* tick,
                                   const eea_collision_cfg* ccfg, const eea_dwa_cfg* dcfg, const eea_fleet_layer* layer,
                                   bool with_layer, void* stream, const FootprintTick* foot = nullptr)
 {
   // (refusals of several kinds, B == 0 and the parameter blocks come before the device is touched: no shared prologue)
-  const char* const entry = foot != nullptr ? "eea_tick_batch_footprint" : with_layer ? "eea_tick_batch_fleet" : "eea_tick_batch";  // (for the refusal messages)
+  const bool with_bodies = foot != nullptr && foot->with_bodies;
+  const char* const entry = with_bodies     ? "eea_tick_batch_bodies"
+                            : foot != nullptr ? "eea_tick_batch_footprint"
+                            : with_layer      ? "eea_tick_batch_fleet"
+                                              : "eea_tick_batch";  // (for the refusal messages)
   if (e == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null engine");
   if (io == nullptr || tick == nullptr || dcfg == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
   if (e->f32) return fail(EEA_ERR_UNSUPPORTED, std::string(entry) + " takes fp64 engines (poses and twists are doubles)");
@@ -2320,12 +2356,14 @@ static eea_status tick_batch_impl(eea_engine* e, unsigned B, const eea_batch_io*
     return fail(EEA_ERR_UNSUPPORTED, std::string(entry) + " does not take the device-bound exchange buffers");
   }
   if (with_layer && layer == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null fleet layer");
+  if (with_bodies && foot->bodies == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, std::string(entry) + ": null body layer");
   eea::FootprintArgs fargs;
   if (foot != nullptr) {  // the footprint, the grid's geometry and the cell limits, as eea_footprint_check_batch asks them
-    const eea_status fst = footprint_call_refusal(ccfg, foot->fp, tick->d_grid, io->d_pose, tick->d_valid, fargs);
+    const eea_status fst = footprint_call_refusal(ccfg, with_bodies ? &foot->bodies->fp : foot->fp, tick->d_grid, io->d_pose,
+                                                  tick->d_valid, fargs);
     if (fst != EEA_OK) return fst;
   }
-  if (B == 0 && !with_layer) return EEA_OK;
+  if (B == 0 && !with_layer && !with_bodies) return EEA_OK;
   // (the footprint reads the geometry and occupied_threshold only: the radii are neither read nor checked)
   eea_status st = foot != nullptr ? EEA_OK : collision_cfg_refusal(ccfg);
   if (st != EEA_OK) return st;
@@ -2336,6 +2374,16 @@ static eea_status tick_batch_impl(eea_engine* e, unsigned B, const eea_batch_io*
       return fail(EEA_ERR_INVALID_ARGUMENT, "the tick's collision configuration is not the fleet layer's");
     }
     if (layer->device != e->cfg.device) return fail(EEA_ERR_INVALID_ARGUMENT, "the fleet layer lives on another device than the engine");
+  }
+  if (with_bodies) {
+    const eea_body_layer* const bl = foot->bodies;
+    if (B != bl->v.B) return fail(EEA_ERR_INVALID_ARGUMENT, std::string(entry) + ": the tick's B is not the body layer's");
+    if (!eea::same_params(c, bl->c)) {
+      return fail(EEA_ERR_INVALID_ARGUMENT, std::string(entry) + ": the tick's grid geometry or occupied_threshold is not the body layer's");
+    }
+    if (bl->device != e->cfg.device) {
+      return fail(EEA_ERR_INVALID_ARGUMENT, std::string(entry) + ": the body layer lives on another device than the engine");
+    }
   }
   eea::DwaParams d;
   st = make_dwa_params(dcfg, d);
@@ -2366,6 +2414,13 @@ static eea_status tick_batch_impl(eea_engine* e, unsigned B, const eea_batch_io*
   // 3. validate_control (:238, numerics.hpp:312-330); 4. the dynamic window where the twist was rejected (:240-277), u /
   // follow_dwa / i updated in place.  One inflated map for both
   const unsigned val_steps = static_cast<unsigned>(std::abs(tick->val_horizon / tick->val_dt));
+  if (with_bodies) {
+    EEA_HIP(eea::launch_body_validate_and_dwa_fleet(c, d, fargs, foot->bodies->v, tick->d_grid, foot->d_sq,
+                                                    static_cast<const double*>(io->d_pose), tick->d_vb, tick->d_traj,
+                                                    static_cast<unsigned>(e->T), e->cfg.dt, tick->val_dt, val_steps, tick->d_valid,
+                                                    tick->d_follow_dwa, tick->d_dwa_count, tick->d_u, tick->d_source, B, s));
+    return EEA_OK;
+  }
   if (foot != nullptr) {  // (tick->grid_epoch is not read: no inflated map)
     EEA_HIP(eea::launch_footprint_validate_and_dwa_fleet(c, d, fargs, tick->d_grid, foot->d_sq, static_cast<const double*>(io->d_pose),
                                                          tick->d_vb, tick->d_traj, static_cast<unsigned>(e->T), e->cfg.dt,
@@ -2407,6 +2462,171 @@ eea_status eea_tick_batch_footprint(eea_engine* e, unsigned B, const eea_batch_i
 {
   const FootprintTick foot{ fp, d_sq };
   return tick_batch_impl(e, B, io, tick, ccfg, dcfg, nullptr, false, stream, &foot);
+}
+
+eea_status eea_tick_batch_bodies(eea_engine* e, unsigned B, const eea_batch_io* io, const eea_tick_io* tick,
+                                 const eea_collision_cfg* ccfg, const eea_dwa_cfg* dcfg, const eea_body_layer* l, const int* d_sq,
+                                 void* stream)
+{
+  const FootprintTick foot{ nullptr, d_sq, true, l };
+  return tick_batch_impl(e, B, io, tick, ccfg, dcfg, nullptr, false, stream, &foot);
+}
+
+// the message of a refusal, with the entry's name in front
+static eea_status named(const char* entry, eea_status st)
+{
+  if (st != EEA_OK) eea::g_last_error = std::string(entry) + ": " + eea::g_last_error;
+  return st;
+}
+
+eea_status eea_body_layer_create(int device, const eea_collision_cfg* cfg, const eea_footprint* fp, unsigned B, unsigned flags,
+                                 eea_body_layer** out)
+{
+  static const char* const entry = "eea_body_layer_create";
+  if (out == nullptr) return named(entry, fail(EEA_ERR_INVALID_ARGUMENT, "null argument"));
+  *out = nullptr;
+  if (cfg == nullptr || fp == nullptr) return named(entry, fail(EEA_ERR_INVALID_ARGUMENT, "null argument"));
+  eea::FootprintArgs f;
+  eea_status st = named(entry, footprint_on_grid_refusal(cfg, fp, f));
+  if (st != EEA_OK) return st;
+  if (B == 0) return named(entry, fail(EEA_ERR_INVALID_ARGUMENT, "a body layer needs at least one robot"));
+  if ((flags & ~EEA_BODY_LAYER_NO_FILTER) != 0u) return named(entry, fail(EEA_ERR_INVALID_ARGUMENT, "unknown flag bits"));
+  // near covers the cells [-box, size + box): box <= 1025
+  const unsigned long long nw = static_cast<unsigned long long>(cfg->xsize) + 2ull * static_cast<unsigned>(f.box);
+  const unsigned long long nh = static_cast<unsigned long long>(cfg->ysize) + 2ull * static_cast<unsigned>(f.box);
+  if (nw > 0x7fffffffull || nh > 0x7fffffffull || nw * nh > (1ull << 31) || B > 0x7fffffffu) {
+    return named(entry, fail(EEA_ERR_UNSUPPORTED, "a body layer of more than 2^31 near cells or robots"));
+  }
+  eea_body_layer* l = new (std::nothrow) eea_body_layer();
+  if (l == nullptr) return named(entry, fail(EEA_ERR_HIP, "out of host memory"));
+  l->device = device;
+  l->flags = flags;
+  l->fp = *fp;
+  l->c = grid_params(cfg);
+  l->f = f;
+  l->v.box = f.box;
+  l->v.Rn = 2 * f.box;  // 2 ceil(r_out / res) + 2
+  l->v.near_w = static_cast<int>(nw);
+  l->v.near_h = static_cast<int>(nh);
+  l->v.B = B;
+  l->v.flags = flags;
+  const size_t n_cover = static_cast<size_t>(cfg->xsize) * cfg->ysize, n_maps = n_cover + static_cast<size_t>(nw * nh);
+  hipError_t err = hipSetDevice(device);
+  if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&l->d_block), sizeof(int) * (n_maps + 2 * kBodyGuard));
+  if (err == hipSuccess) l->d_maps = l->d_block + kBodyGuard;
+  if (err == hipSuccess) err = hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(l->d_block), kBodyGuardWord, n_maps + 2 * kBodyGuard);
+  if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&l->d_snap), sizeof(double) * eea::kBodySnap * static_cast<size_t>(B));
+  // before the first update: no robot is an obstacle
+  if (err == hipSuccess) err = hipMemset(l->d_maps, 0, sizeof(int) * n_maps);
+  if (err == hipSuccess) err = hipMemset(l->d_snap, 0, sizeof(double) * eea::kBodySnap * static_cast<size_t>(B));
+  if (err == hipSuccess) err = hipDeviceSynchronize();
+  if (err != hipSuccess) {
+    (void)hipGetLastError();
+    const std::string msg = std::string(entry) + ": " + std::to_string(n_maps) + " map cells: " + hipGetErrorString(err);
+    eea_body_layer_destroy(l);
+    return fail(EEA_ERR_HIP, msg);
+  }
+  l->v.cover = l->d_maps;
+  l->v.near = l->d_maps + n_cover;
+  l->v.snap = l->d_snap;
+  *out = l;
+  return EEA_OK;
+}
+
+void eea_body_layer_destroy(eea_body_layer* l)
+{
+  if (l == nullptr) return;
+  if ((l->d_block != nullptr || l->d_snap != nullptr) && hipSetDevice(l->device) == hipSuccess) {
+    if (l->d_block != nullptr) (void)hipFree(l->d_block);  // waits for its users
+    if (l->d_snap != nullptr) (void)hipFree(l->d_snap);
+  }
+  delete l;
+}
+
+eea_status eea_body_layer_update(eea_body_layer* l, const double* d_pose, const int* d_mask, void* stream)
+{
+  if (l == nullptr || d_pose == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "eea_body_layer_update: null argument");
+  EEA_HIP(hipSetDevice(l->device));
+  EEA_HIP(eea::launch_body_layer_update(l->c, l->f, l->v, l->d_maps, l->d_snap, d_pose, d_mask, static_cast<hipStream_t>(stream)));
+  return EEA_OK;
+}
+
+eea_status eea_body_layer_read(const eea_body_layer* l, int* h_cover, int* h_near, double* h_snapshot)
+{
+  if (l == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "eea_body_layer_read: null argument");
+  EEA_HIP(hipSetDevice(l->device));
+  EEA_HIP(hipDeviceSynchronize());
+  const size_t n_cover = static_cast<size_t>(l->c.xsize) * l->c.ysize, n_near = static_cast<size_t>(l->v.near_w) * l->v.near_h;
+  int guard[2 * kBodyGuard];
+  EEA_HIP(hipMemcpy(guard, l->d_block, sizeof(int) * kBodyGuard, hipMemcpyDeviceToHost));
+  EEA_HIP(hipMemcpy(guard + kBodyGuard, l->d_maps + n_cover + n_near, sizeof(int) * kBodyGuard, hipMemcpyDeviceToHost));
+  for (size_t k = 0; k < 2 * kBodyGuard; ++k) {
+    if (guard[k] != kBodyGuardWord) return fail(EEA_ERR_HIP, "eea_body_layer_read: a guard word beside the maps was overwritten");
+  }
+  if (h_cover != nullptr) EEA_HIP(hipMemcpy(h_cover, l->v.cover, sizeof(int) * n_cover, hipMemcpyDeviceToHost));
+  if (h_near != nullptr) EEA_HIP(hipMemcpy(h_near, l->v.near, sizeof(int) * n_near, hipMemcpyDeviceToHost));
+  if (h_snapshot != nullptr) {
+    EEA_HIP(hipMemcpy(h_snapshot, l->d_snap, sizeof(double) * eea::kBodySnap * static_cast<size_t>(l->v.B), hipMemcpyDeviceToHost));
+  }
+  return EEA_OK;
+}
+
+int eea_body_layer_box(const eea_body_layer* l) { return l != nullptr ? l->v.box : -1; }
+
+eea_status eea_body_collision_check_batch(const eea_body_layer* l, const int8_t* d_grid, const int* d_sq, const double* d_pose,
+                                          const int* d_self, unsigned P, int* d_hit, void* stream)
+{
+  // (the layer last: every other refusal can be reached without one)
+  if (d_pose == nullptr || d_hit == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "eea_body_collision_check_batch: null argument");
+  if (l == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "eea_body_collision_check_batch: null body layer");
+  if (P == 0) return EEA_OK;
+  EEA_HIP(hipSetDevice(l->device));
+  const eea::BodyArgs a{ l->v, d_self, 0 };
+  EEA_HIP(eea::launch_body_check(l->c, l->f, a, d_grid, d_sq, d_pose, P, d_hit, static_cast<hipStream_t>(stream)));
+  return EEA_OK;
+}
+
+eea_status eea_body_validate_control_batch(const eea_body_layer* l, const int8_t* d_grid, const int* d_sq, const double* d_x0,
+                                           const double* d_u, const int* d_self, double dt, double horizon, unsigned P,
+                                           int* d_valid, void* stream)
+{
+  if (d_grid == nullptr || d_x0 == nullptr || d_valid == nullptr || d_u == nullptr) {
+    return fail(EEA_ERR_INVALID_ARGUMENT, "eea_body_validate_control_batch: null argument");
+  }
+  if (l == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "eea_body_validate_control_batch: null body layer");
+  if (P == 0) return EEA_OK;
+  const unsigned steps = static_cast<unsigned>(std::abs(horizon / dt));  // numerics.hpp:317
+  EEA_HIP(hipSetDevice(l->device));
+  const eea::BodyArgs a{ l->v, d_self, 0 };
+  EEA_HIP(eea::launch_body_validate(l->c, l->f, a, d_grid, d_sq, d_x0, d_u, dt, steps, P, d_valid, static_cast<hipStream_t>(stream)));
+  return EEA_OK;
+}
+
+eea_status eea_body_dwa_control_batch(const eea_body_layer* l, const eea_dwa_cfg* dcfg, const int8_t* d_grid, const int* d_sq,
+                                      const double* d_x0, const double* d_vb, const double* d_vref, const double* d_xt_ref,
+                                      unsigned n_ref, double dt_ref, const int* d_self, unsigned P, double* d_u_opt, int* d_found,
+                                      void* stream)
+{
+  static const char* const entry = "eea_body_dwa_control_batch";
+  if (d_grid == nullptr || d_x0 == nullptr || d_u_opt == nullptr || dcfg == nullptr || d_vb == nullptr || d_found == nullptr) {
+    return named(entry, fail(EEA_ERR_INVALID_ARGUMENT, "null argument"));
+  }
+  if ((d_vref == nullptr) == (d_xt_ref == nullptr)) return named(entry, fail(EEA_ERR_INVALID_ARGUMENT, "give either d_vref or d_xt_ref"));
+  if (d_xt_ref != nullptr && n_ref == 0) return named(entry, fail(EEA_ERR_INVALID_ARGUMENT, "empty reference trajectory"));
+  eea::DwaParams d;
+  eea_status st = named(entry, make_dwa_params(dcfg, d));
+  if (st != EEA_OK) return st;
+  if (d_xt_ref != nullptr) {
+    st = named(entry, check_reference_index(d, n_ref, dt_ref));
+    if (st != EEA_OK) return st;
+  }
+  if (l == nullptr) return named(entry, fail(EEA_ERR_INVALID_ARGUMENT, "null body layer"));
+  if (P == 0) return EEA_OK;
+  EEA_HIP(hipSetDevice(l->device));
+  const eea::BodyArgs a{ l->v, d_self, 0 };
+  EEA_HIP(eea::launch_body_dwa(l->c, d, l->f, a, d_grid, d_sq, d_x0, d_vb, d_vref, d_xt_ref, n_ref, dt_ref, P, d_u_opt, d_found,
+                               static_cast<hipStream_t>(stream)));
+  return EEA_OK;
 }
 
 eea_status eea_fleet_layer_create(int device, const eea_collision_cfg* cfg, int body_cells, unsigned B, eea_fleet_layer** out)

@@ -149,8 +149,12 @@ hipError_t launch_fleet_layer_update(const CollisionParams& c, const FleetView& 
                      d_cell);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(fleet_row_scan_kernel, dim3((v.h + kScanRows - 1) / kScanRows), dim3(kWave * kScanRows), 0, s, d_count, v.w,
-                     v.h);
+  return launch_fleet_row_scan(d_count, v.w, v.h, s);
+}
+
+hipError_t launch_fleet_row_scan(int* d_map, int w, int h, hipStream_t s)
+{
+  hipLaunchKernelGGL(fleet_row_scan_kernel, dim3((h + kScanRows - 1) / kScanRows), dim3(kWave * kScanRows), 0, s, d_map, w, h);
   return hipGetLastError();
 }
 }  // namespace eea

@@ -22,6 +22,12 @@
 //            beside a solid obstacle a box holds hundreds of occupied cells, and a wavefront waits for its slowest lane.  The host sizes the window from vmin / vmax; a robot whose own reach is larger (vb outside the
 //            limits: lower above vmax), whose x0 is not finite, or a launch whose window does not fit the LDS takes its cells
 //            from memory through the cooperative resolve instead, with the same verdicts: a workgroup-uniform choice.
+//
+// Both kernels are templates over their last argument: NoBodies (the instances above, unchanged) or BodyArgs, the body layer
+// (body_layer_kernel.hip): a cell is then occupied when the grid says so or a stamped robot other than the pose's own covers
+// it.  The window's staging ORs those cells into the LDS bit rows (the robot's own body taken out where cover > 0) and leaves
+// one workgroup-uniform flag, "the window holds a body bit": without it a pose the field calls free is free; with it -- and on
+// the memory path wherever the layer's near map does not prove the opposite -- such a pose takes the exact test.
 #include <cmath>
 #include <cstdint>
 
@@ -38,12 +44,14 @@ namespace
 {
 constexpr int kPlanBlock = 128;  // dwa_control_kernel's block rule: 64 threads up to 64 samples, 128 beyond
 constexpr size_t kLdsLimit = 64 * 1024;
+constexpr size_t kBodyFlagBytes = sizeof(unsigned long long) * (kPlanBlock / kWave);
 
 // the ambiguous lanes of one step, resolved by the wavefront one after the other; true in the lanes whose pose collides.
 // Called by all lanes of a wavefront together
+template <class BV = NoBodies>
 __device__ __forceinline__ bool resolve_together(const CollisionParams& c, const FootprintArgs& f, const PlaneRegs& pl,
                                                  const int8_t* __restrict__ grid, bool ambiguous, double px, double py, double th,
-                                                 const Box& b, int lane)
+                                                 const Box& b, int lane, BV bv = BV{})
 {
   unsigned long long todo = __ballot(ambiguous);
   double sn = 0.0, cs = 0.0;
@@ -52,22 +60,41 @@ __device__ __forceinline__ bool resolve_together(const CollisionParams& c, const
   while (todo != 0ull) {
     const int src = __ffsll(static_cast<long long>(todo)) - 1;
     todo &= todo - 1ull;
-    const bool h = resolve(c, f, pl, grid, src, px, py, sn, cs, b, lane);
+    const bool h = resolve(c, f, pl, grid, src, px, py, sn, cs, b, lane, bv);
     if (lane == src) hit = h;
   }
   return hit;
 }
 
+// what a kernel instance judges poses with: nothing, or the layer as the lane sees it
+template <class VIEW>
+struct BodiesOf
+{
+  using type = NoBodies;
+};
+template <>
+struct BodiesOf<BodyArgs>
+{
+  using type = Bodies;
+};
+
+template <class VIEW>
 __global__ __launch_bounds__(kBlock) void footprint_validate_kernel(const CollisionParams c, const FootprintArgs f,
                                                                     const int8_t* __restrict__ grid, const int* __restrict__ d_sq,
                                                                     const double* __restrict__ x0, const double* __restrict__ u,
-                                                                    double dt, unsigned steps, unsigned P, int* __restrict__ valid)
+                                                                    double dt, unsigned steps, unsigned P, int* __restrict__ valid,
+                                                                    const VIEW view)
 {
   const int lane = threadIdx.x % kWave;
   const size_t q = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
   const PlaneRegs pl = load_planes(f, lane);
   const bool live = q < P;
   double x = 0.0, y = 0.0, th = 0.0, d0 = 0.0, d1 = 0.0, d2 = 0.0;
+  typename BodiesOf<VIEW>::type bv{};
+  if constexpr (std::is_same_v<VIEW, BodyArgs>) {
+    bv.v = view.v;
+    if (live) bv = load_bodies(view, q);
+  }
   if (live) {
     x = x0[3 * q];
     y = x0[3 * q + 1];
@@ -82,9 +109,9 @@ __global__ __launch_bounds__(kBlock) void footprint_validate_kernel(const Collis
     int cls = kFree;
     if (!done) {
       advance_pose<true>(x, y, th, d0, d1, d2, true);
-      cls = classify(c, f, d_sq, x, y, th, b);
+      cls = classify_with(c, f, d_sq, x, y, th, b, bv);
     }
-    const bool h = resolve_together(c, f, pl, grid, cls == kAmbiguous, x, y, th, b, lane);
+    const bool h = resolve_together(c, f, pl, grid, cls == kAmbiguous, x, y, th, b, lane, bv);
     if (cls == kHit || h) {
       ok = 0;
       done = true;
@@ -182,14 +209,21 @@ __device__ __forceinline__ bool resolve_window(const CollisionParams& c, const F
 
 // ... the same by one lane alone from the grid in memory: for a box that is not inside the window (the reach bound says there
 // is none; a wrong answer would be silent, this is only slow)
+template <class BV = NoBodies>
 __device__ __forceinline__ bool resolve_alone(const CollisionParams& c, const FootprintArgs& f, const PlaneRegs& pl,
-                                              const int8_t* __restrict__ grid, double px, double py, double sn, double cs, const Box& b)
+                                              const int8_t* __restrict__ grid, double px, double py, double sn, double cs, const Box& b,
+                                              BV bv = BV{})
 {
   for (int i = b.y0; i <= b.y1; ++i) {
     const double cyw = static_cast<double>(i) * c.resolution + c.resolution / 2.0 + c.ymin;
     const double dy = cyw - py;
     for (int j = b.x0; j <= b.x1; ++j) {
-      if (grid[static_cast<size_t>(i) * c.xsize + static_cast<size_t>(j)] < f.v_min) continue;
+      if constexpr (kWithBodies<BV>) {
+        const size_t at = static_cast<size_t>(i) * c.xsize + static_cast<size_t>(j);
+        if (grid[at] < f.v_min && !other_body(c, f, pl, bv.v.cover[at], i, j, bv.stamped, bv.px, bv.py, bv.sn, bv.cs)) continue;
+      } else {
+        if (grid[static_cast<size_t>(i) * c.xsize + static_cast<size_t>(j)] < f.v_min) continue;
+      }
       const double cxw = static_cast<double>(j) * c.resolution + c.resolution / 2.0 + c.xmin;
       const double dx = cxw - px;
       const double bx = cs * dx + sn * dy, by = (-sn) * dx + cs * dy;
@@ -215,14 +249,14 @@ struct PlanTick
 };
 
 // win_reach: the reach in cells the launch reserved a window for (after the costs in dynamic LDS), -1: none
-template <bool FLEET>
+template <bool FLEET, class VIEW>
 __global__ __launch_bounds__(kPlanBlock) void footprint_dwa_kernel(const CollisionParams c, const DwaParams d, const FootprintArgs f,
                                                                   const int8_t* __restrict__ grid, const int* __restrict__ d_sq,
                                                                   const double* __restrict__ x0s, const double* __restrict__ vbs,
                                                                   const double* __restrict__ vrefs,
                                                                   const double* __restrict__ xt_refs, unsigned n_ref, double dt_ref,
                                                                   double* __restrict__ u_opt, int* __restrict__ found,
-                                                                  const PlanTick ft, int win_reach)
+                                                                  const PlanTick ft, int win_reach, const VIEW view)
 {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   double* const s_cost = reinterpret_cast<double*>(smem_raw);
@@ -242,6 +276,10 @@ __global__ __launch_bounds__(kPlanBlock) void footprint_dwa_kernel(const Collisi
     u_opt = ft.u;
   }
   const PlaneRegs pl = load_planes(f, lane);
+  // (with the layer: the workgroup's robot, the same in every lane, and whether its window holds a body bit)
+  typename BodiesOf<VIEW>::type bv{};
+  [[maybe_unused]] bool body_in_window = false;  // (never read without the layer)
+  if constexpr (std::is_same_v<VIEW, BodyArgs>) bv = load_bodies(view, r);
   const double* const x0 = x0s + 3 * static_cast<size_t>(r);
   const double* const vb = vbs + 3 * static_cast<size_t>(r);
   const unsigned nsamp = d.ns[0] * d.ns[1] * d.ns[2];
@@ -290,11 +328,36 @@ __global__ __launch_bounds__(kPlanBlock) void footprint_dwa_kernel(const Collisi
       const int total = rows * w.nw;
       for (int first = wave * kStage; first < total; first += n_waves * kStage) {
         bool occ[kStage];
+        if constexpr (kWithBodies<decltype(bv)>) {
+          // (the layer: the cell's byte and its count, both loads of all kStage words first -- a lane past the window reads
+          // the window's first cell and drops it --, then the own-body test where a count is above 0)
+          int8_t gv[kStage];
+          int nb[kStage], ri[kStage], cj[kStage];
+          bool in[kStage];
+          const size_t first_at = static_cast<size_t>(w.wy0) * c.xsize + static_cast<size_t>(w.wx0);
 #pragma unroll
-        for (int u = 0; u < kStage; ++u) {
-          const int idx = first + u, row = idx / w.nw, col = 64 * (idx - row * w.nw) + lane;
-          occ[u] = idx < total && col < cols &&
-                   grid[static_cast<size_t>(w.wy0 + row) * c.xsize + static_cast<size_t>(w.wx0 + col)] >= f.v_min;
+          for (int u = 0; u < kStage; ++u) {
+            const int idx = first + u, row = idx / w.nw, col = 64 * (idx - row * w.nw) + lane;
+            in[u] = idx < total && col < cols;
+            ri[u] = w.wy0 + row;
+            cj[u] = w.wx0 + col;
+            const size_t at = in[u] ? static_cast<size_t>(ri[u]) * c.xsize + static_cast<size_t>(cj[u]) : first_at;
+            gv[u] = grid[at];
+            nb[u] = bv.v.cover[at];
+          }
+#pragma unroll
+          for (int u = 0; u < kStage; ++u) {
+            const bool body = in[u] && other_body(c, f, pl, nb[u], ri[u], cj[u], bv.stamped, bv.px, bv.py, bv.sn, bv.cs);
+            body_in_window = body_in_window || body;
+            occ[u] = in[u] && (gv[u] >= f.v_min || body);
+          }
+        } else {
+#pragma unroll
+          for (int u = 0; u < kStage; ++u) {
+            const int idx = first + u, row = idx / w.nw, col = 64 * (idx - row * w.nw) + lane;
+            occ[u] = idx < total && col < cols &&
+                     grid[static_cast<size_t>(w.wy0 + row) * c.xsize + static_cast<size_t>(w.wx0 + col)] >= f.v_min;
+          }
         }
 #pragma unroll
         for (int u = 0; u < kStage; ++u) {
@@ -303,7 +366,16 @@ __global__ __launch_bounds__(kPlanBlock) void footprint_dwa_kernel(const Collisi
         }
       }
     }
-    __syncthreads();
+    if constexpr (kWithBodies<decltype(bv)>) {  // one word per wavefront behind the bit rows (PlanGeometry reserves them)
+      unsigned long long* const s_flag = s_bits + static_cast<size_t>(side) * w.nw;
+      const bool mine = __any(body_in_window) != 0;
+      if (lane == 0) s_flag[wave] = mine ? 1ull : 0ull;
+      __syncthreads();
+      body_in_window = false;
+      for (int k = 0; k < n_waves; ++k) body_in_window = body_in_window || s_flag[k] != 0ull;
+    } else {
+      __syncthreads();
+    }
   }
 
   for (unsigned base = 0; base < nsamp; base += blockDim.x) {  // wavefront-uniform: resolve_together needs every lane
@@ -323,7 +395,20 @@ __global__ __launch_bounds__(kPlanBlock) void footprint_dwa_kernel(const Collisi
       int cls = kFree;
       if (!done) {
         advance_pose<true>(x, y, th, d0, d1, d2, true);
-        cls = classify(c, f, d_sq, x, y, th, b);
+        if constexpr (kWithBodies<decltype(bv)>) {
+          if (use_window) {  // the filter is the staging flag (a box outside the window -- there is none -- asks the near map)
+            cls = classify(c, f, d_sq, x, y, th, b);
+            if (cls == kFree && b.x1 >= b.x0) {
+              const bool inside = b.x0 >= w.wx0 && b.x1 <= w.wx1 && b.y0 >= w.wy0 && b.y1 <= w.wy1;
+              const bool clear = (bv.v.flags & kBodyLayerNoFilter) != 0u ? false : inside ? !body_in_window : nobody_near(c, bv, x, y);
+              if (!clear) cls = kAmbiguous;
+            }
+          } else {
+            cls = classify_with(c, f, d_sq, x, y, th, b, bv);
+          }
+        } else {
+          cls = classify(c, f, d_sq, x, y, th, b);
+        }
       }
       bool h = cls == kHit;
       if (use_window) {
@@ -331,10 +416,10 @@ __global__ __launch_bounds__(kPlanBlock) void footprint_dwa_kernel(const Collisi
           double sn, cs;
           tick_sincos(th, &sn, &cs);
           const bool inside = b.x0 >= w.wx0 && b.x1 <= w.wx1 && b.y0 >= w.wy0 && b.y1 <= w.wy1;
-          h = inside ? resolve_window(c, f, pl, w, x, y, sn, cs, b) : resolve_alone(c, f, pl, grid, x, y, sn, cs, b);
+          h = inside ? resolve_window(c, f, pl, w, x, y, sn, cs, b) : resolve_alone(c, f, pl, grid, x, y, sn, cs, b, bv);
         }
       } else {
-        h = resolve_together(c, f, pl, grid, cls == kAmbiguous, x, y, th, b, lane) || h;
+        h = resolve_together(c, f, pl, grid, cls == kAmbiguous, x, y, th, b, lane, bv) || h;
       }
       if (h) {
         hit = true;
@@ -396,14 +481,15 @@ struct PlanGeometry
   size_t nsamp, lds;
   unsigned block;
   int win_reach = -1;
-  PlanGeometry(const CollisionParams& c, const DwaParams& d, const FootprintArgs& f)
+  // flag_bytes: what the layer's instance keeps behind the window (a word per wavefront)
+  PlanGeometry(const CollisionParams& c, const DwaParams& d, const FootprintArgs& f, size_t flag_bytes = 0)
     : nsamp(static_cast<size_t>(d.ns[0]) * d.ns[1] * d.ns[2]), lds(sizeof(double) * nsamp), block(nsamp <= 64 ? 64 : kPlanBlock)
   {
     const double mx = std::fmax(std::fabs(d.vmin[0]), std::fabs(d.vmax[0])), my = std::fmax(std::fabs(d.vmin[1]), std::fabs(d.vmax[1]));
     const double reach = std::ceil(static_cast<double>(d.steps) * std::fabs(d.dt) * std::sqrt(mx * mx + my * my) / c.resolution) + 1.0;
     if (!(reach >= 0.0 && reach <= 4096.0)) return;
     const size_t side = 2 * (static_cast<size_t>(reach) + static_cast<size_t>(f.box)) + 1;
-    const size_t bytes = side * ((side + 63) / 64) * sizeof(unsigned long long);
+    const size_t bytes = side * ((side + 63) / 64) * sizeof(unsigned long long) + flag_bytes;
     if (lds + bytes > kLdsLimit) return;
     win_reach = static_cast<int>(reach);
     lds += bytes;
@@ -418,7 +504,19 @@ hipError_t launch_footprint_validate(const CollisionParams& c, const FootprintAr
 {
   if (P == 0) return hipSuccess;
   const dim3 blocks(static_cast<unsigned>((static_cast<size_t>(P) + kBlock - 1) / kBlock));
-  hipLaunchKernelGGL(footprint_validate_kernel, blocks, dim3(kBlock), 0, s, c, f, d_grid, d_sq, d_x0, d_u, dt, steps, P, d_valid);
+  hipLaunchKernelGGL(footprint_validate_kernel<NoBodies>, blocks, dim3(kBlock), 0, s, c, f, d_grid, d_sq, d_x0, d_u, dt, steps, P,
+                     d_valid, NoBodies{});
+  return hipGetLastError();
+}
+
+hipError_t launch_body_validate(const CollisionParams& c, const FootprintArgs& f, const BodyArgs& a, const int8_t* d_grid,
+                                const int* d_sq, const double* d_x0, const double* d_u, double dt, unsigned steps, unsigned P,
+                                int* d_valid, hipStream_t s)
+{
+  if (P == 0) return hipSuccess;
+  const dim3 blocks(static_cast<unsigned>((static_cast<size_t>(P) + kBlock - 1) / kBlock));
+  hipLaunchKernelGGL(footprint_validate_kernel<BodyArgs>, blocks, dim3(kBlock), 0, s, c, f, d_grid, d_sq, d_x0, d_u, dt, steps, P,
+                     d_valid, a);
   return hipGetLastError();
 }
 
@@ -430,8 +528,21 @@ hipError_t launch_footprint_dwa(const CollisionParams& c, const DwaParams& d, co
   if (P == 0) return hipSuccess;
   const PlanGeometry g(c, d, f);
   if (!g.fits()) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(footprint_dwa_kernel<false>, dim3(P), dim3(g.block), g.lds, s, c, d, f, d_grid, d_sq, d_x0, d_vb, d_vref,
-                     d_xt_ref, n_ref, dt_ref, d_u_opt, d_found, PlanTick{}, g.win_reach);
+  hipLaunchKernelGGL((footprint_dwa_kernel<false, NoBodies>), dim3(P), dim3(g.block), g.lds, s, c, d, f, d_grid, d_sq, d_x0, d_vb,
+                     d_vref, d_xt_ref, n_ref, dt_ref, d_u_opt, d_found, PlanTick{}, g.win_reach, NoBodies{});
+  return hipGetLastError();
+}
+
+hipError_t launch_body_dwa(const CollisionParams& c, const DwaParams& d, const FootprintArgs& f, const BodyArgs& a,
+                           const int8_t* d_grid, const int* d_sq, const double* d_x0, const double* d_vb, const double* d_vref,
+                           const double* d_xt_ref, unsigned n_ref, double dt_ref, unsigned P, double* d_u_opt, int* d_found,
+                           hipStream_t s)
+{
+  if (P == 0) return hipSuccess;
+  const PlanGeometry g(c, d, f, kBodyFlagBytes);
+  if (!g.fits()) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((footprint_dwa_kernel<false, BodyArgs>), dim3(P), dim3(g.block), g.lds, s, c, d, f, d_grid, d_sq, d_x0, d_vb,
+                     d_vref, d_xt_ref, n_ref, dt_ref, d_u_opt, d_found, PlanTick{}, g.win_reach, a);
   return hipGetLastError();
 }
 
@@ -449,9 +560,29 @@ hipError_t launch_footprint_validate_and_dwa_fleet(const CollisionParams& c, con
   const hipError_t e = launch_footprint_validate(c, f, d_grid, d_sq, d_x0, d_u, val_dt, val_steps, P, d_valid, s);
   if (e != hipSuccess) return e;
   const PlanTick ft{ d_valid, d_follow, d_count, d_u, d_source };
-  hipLaunchKernelGGL(footprint_dwa_kernel<true>, dim3(P), dim3(g.block), g.lds, s, c, d, f, d_grid, d_sq, d_x0, d_vb,
+  hipLaunchKernelGGL((footprint_dwa_kernel<true, NoBodies>), dim3(P), dim3(g.block), g.lds, s, c, d, f, d_grid, d_sq, d_x0, d_vb,
                      static_cast<const double*>(nullptr), d_traj, n_ref, dt_ref, static_cast<double*>(nullptr),
-                     static_cast<int*>(nullptr), ft, g.win_reach);
+                     static_cast<int*>(nullptr), ft, g.win_reach, NoBodies{});
+  return hipGetLastError();
+}
+
+// ... with the layer: robot r of the tick is robot r of the layer
+hipError_t launch_body_validate_and_dwa_fleet(const CollisionParams& c, const DwaParams& d, const FootprintArgs& f, const BodyView& v,
+                                              const int8_t* d_grid, const int* d_sq, const double* d_x0, const double* d_vb,
+                                              const double* d_traj, unsigned n_ref, double dt_ref, double val_dt,
+                                              unsigned val_steps, int* d_valid, int* d_follow, unsigned* d_count, double* d_u,
+                                              int* d_source, unsigned P, hipStream_t s)
+{
+  if (P == 0) return hipSuccess;
+  const PlanGeometry g(c, d, f, kBodyFlagBytes);
+  if (!g.fits()) return hipErrorInvalidValue;
+  const BodyArgs a{ v, nullptr, 1 };
+  const hipError_t e = launch_body_validate(c, f, a, d_grid, d_sq, d_x0, d_u, val_dt, val_steps, P, d_valid, s);
+  if (e != hipSuccess) return e;
+  const PlanTick ft{ d_valid, d_follow, d_count, d_u, d_source };
+  hipLaunchKernelGGL((footprint_dwa_kernel<true, BodyArgs>), dim3(P), dim3(g.block), g.lds, s, c, d, f, d_grid, d_sq, d_x0, d_vb,
+                     static_cast<const double*>(nullptr), d_traj, n_ref, dt_ref, static_cast<double*>(nullptr),
+                     static_cast<int*>(nullptr), ft, g.win_reach, a);
   return hipGetLastError();
 }
 }  // namespace eea

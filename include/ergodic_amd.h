@@ -999,6 +999,84 @@ eea_status eea_tick_batch_footprint(eea_engine* e, unsigned B, const eea_batch_i
                                     const eea_collision_cfg* ccfg, const eea_dwa_cfg* dcfg, const eea_footprint* fp,
                                     const int* d_sq, void* stream);
 
+/* ---- body layer: polygon robots as obstacles to one another (additive to ABI 6: detect these entries by symbol) -----------
+ * The fleet layer above makes the robots of a tick obstacles to one another as DISCS; the footprint calls judge a robot by
+ * its polygon but know no other robot.  A body layer joins them: one footprint per layer, shared by all B robots, as
+ * eea_tick_batch_footprint takes one.  No reference counterpart.
+ *
+ * The cell test.  T(cell, pose) is the closed test of the cell's centre against the polygon placed at the pose -- the
+ * products and sums written under "footprint collision" above, in that order, no fused multiply-add -- with the sine and the
+ * cosine the rollouts use.
+ *
+ * Obstacles.  At an update robot j is STAMPED iff it is active (d_mask == NULL or d_mask[j] != 0), its pose is finite, and its
+ * box touches the grid: with fx = floor((px - xmin) / res), fy likewise, box = ceil(r_out / res) + 1, all as doubles,
+ * fx + box >= 0, fx - box <= xsize - 1, fy + box >= 0, fy - box <= ysize - 1.  The body of robot j is the set of IN-GRID
+ * cells c with T(c, pose_j at the update), whatever those cells hold and whatever occupied_threshold is.  Nothing off the grid
+ * is an obstacle: a body that hangs over the edge is its in-grid part.
+ *
+ * The verdict of a pose q that belongs to robot i (d_self[q] = i; in the tick: robot r's poses belong to robot r) is the
+ * footprint's verdict on a grid of robot i's own -- the grid with every cell of every OTHER stamped robot's body occupied:
+ *   the static verdict, OR some in-grid cell c has T(c, q) and T(c, pose_j) for a stamped j != i.
+ * A robot is never its own obstacle.  d_self == NULL or d_self[q] == -1: nobody's body is taken out.  A d_self entry outside
+ * [-1, B) is the caller's error and is not checked.
+ *
+ * Staleness, as in the fleet layer: the others stand still at the poses of the last update for a whole rollout.  Robots whose
+ * bodies share a cell at the update are in collision where they stand: every rollout of either that has not left the overlap
+ * by its first step collides, validate_control rejects every twist that does not, and the dynamic window finds nothing unless
+ * a sample leaves at once.  Keeping the bodies apart is the planner's job from the tick before.
+ *
+ * Composition.  Rollouts, window bounds, costs, the first strict minimum, found and u_opt = 0 are bit for bit those of
+ * eea_footprint_validate_control_batch / eea_footprint_dwa_control_batch.  d_sq (the distance field of the STATIC grid, may be
+ * NULL) never changes an output bit, and neither does any filter inside the layer.  The verdict is pinned wherever no centre
+ * lies within 1e-9 m of a boundary it is tested against: the polygon at q against the occupied centres and the centres of the
+ * others' bodies, and every stamped polygon against the in-grid centres.
+ *
+ * eea_body_layer_read (for tests and tools; synchronises; any pointer may be NULL; it also verifies the guard words the layer
+ * keeps on either side of its maps in device memory and answers EEA_ERR_HIP if one was overwritten):
+ *   h_cover [ysize][xsize] int: the number of stamped robots whose body holds the cell;
+ *   h_near [ysize + 2 box][xsize + 2 box] int over the cells [-box, xsize + box) x [-box, ysize + box): the stamped robots whose
+ *     cell (fx, fy) lies within Chebyshev distance Rn = 2 ceil(r_out / res) + 2 of this one.  near minus the pose's own robot
+ *     (when stamped and within Rn) == 0 proves that no other body shares a cell with a polygon placed in this cell; it is
+ *     used for nothing else;
+ *   h_snapshot [B][5] double: px, py, sine, cosine of the pose the robot was stamped with and 1.0, or five zeros.
+ * flags: EEA_BODY_LAYER_NO_FILTER skips near -- every pose with a non-empty box takes the exact test (so that the filter can
+ * be tested on the device, as d_sq == NULL tests the field).
+ *
+ * An update is stream operations only (one clear, one stamp kernel, two row scans): no host read, no allocation, no
+ * synchronising call; the readers on the same stream see it.  Before the first update no robot is an obstacle.
+ * Refusals, before any HIP call, outputs untouched, the message naming the entry -- creation: NULL cfg / fp / out; the
+ * footprint's and the grid's refusals of eea_footprint_check_batch (EEA_ERR_UNSUPPORTED: xsize * ysize > 2^31, r_out / res >
+ * 1024, a near map above 2^31 cells); B == 0; unknown flag bits.  The batch entries: those of the footprint entries they extend
+ * (NULL l / poses / outputs; d_grid NULL except in eea_body_collision_check_batch, where it means robots only; the dynamic
+ * window's).  eea_tick_batch_bodies: eea_tick_batch_footprint's, in its order; where eea_tick_batch_fleet checks its layer: ccfg
+ * must give the layer's geometry and occupied_threshold, B the layer's B, and the layer must live on the engine's device. */
+#define EEA_BODY_LAYER_NO_FILTER 1u
+typedef struct eea_body_layer eea_body_layer;
+eea_status eea_body_layer_create(int device, const eea_collision_cfg* cfg, const eea_footprint* fp, unsigned B, unsigned flags,
+                                 eea_body_layer** out);
+void eea_body_layer_destroy(eea_body_layer* l);
+/* d_pose [B][3], d_mask [B] (may be NULL: all active) */
+eea_status eea_body_layer_update(eea_body_layer* l, const double* d_pose, const int* d_mask, void* stream);
+eea_status eea_body_layer_read(const eea_body_layer* l, int* h_cover, int* h_near, double* h_snapshot);
+/* box = ceil(r_out / res) + 1 of the layer (-1: NULL) */
+int eea_body_layer_box(const eea_body_layer* l);
+/* eea_footprint_check_batch with the layer; d_grid == NULL: robots only (d_sq is then ignored) */
+eea_status eea_body_collision_check_batch(const eea_body_layer* l, const int8_t* d_grid, const int* d_sq, const double* d_pose,
+                                          const int* d_self, unsigned P, int* d_hit, void* stream);
+/* eea_footprint_validate_control_batch / eea_footprint_dwa_control_batch with the layer; d_self [P] as above */
+eea_status eea_body_validate_control_batch(const eea_body_layer* l, const int8_t* d_grid, const int* d_sq, const double* d_x0,
+                                           const double* d_u, const int* d_self, double dt, double horizon, unsigned P,
+                                           int* d_valid, void* stream);
+eea_status eea_body_dwa_control_batch(const eea_body_layer* l, const eea_dwa_cfg* dcfg, const int8_t* d_grid, const int* d_sq,
+                                      const double* d_x0, const double* d_vb, const double* d_vref, const double* d_xt_ref,
+                                      unsigned n_ref, double dt_ref, const int* d_self, unsigned P, double* d_u_opt, int* d_found,
+                                      void* stream);
+/* eea_tick_batch_footprint with the layer in steps 3 and 4: robot r of the tick is robot r of the layer (updated on the same
+ * stream before) */
+eea_status eea_tick_batch_bodies(eea_engine* e, unsigned B, const eea_batch_io* io, const eea_tick_io* tick,
+                                 const eea_collision_cfg* ccfg, const eea_dwa_cfg* dcfg, const eea_body_layer* l, const int* d_sq,
+                                 void* stream);
+
 /* The collision / DWA / tick / clearance calls keep small device caches between calls (the ring offsets per radii, one
  * inflated-map and one key-map buffer per (device, stream), the span tables of fleet layers that no layer holds any more).  A long-running
  * process that changes streams or map sizes can drop them; synchronises the devices involved.  No reference counterpart. */
