@@ -165,7 +165,9 @@ __device__ __forceinline__ bool resolve_window(const CollisionParams& c, const F
   const float res = static_cast<float>(c.resolution), inv_res = 1.0f / res, fs = static_cast<float>(sn), fc = static_cast<float>(cs);
   const float dx0 = static_cast<float>(static_cast<double>(b.x0) * c.resolution + c.resolution / 2.0 + c.xmin - px);
   constexpr int kRows = 4;  // row words read from LDS before the first of them is looked at
-  for (int k = c0 >> 6; k <= (c1 >> 6); ++k) {  // (one or two words for a box of up to 65 columns)
+  // every word of a window row the box touches: one or two up to 65 columns, eleven at most where the window still fits the LDS
+  // (tests/test_gpu_footprint_edges.py runs one to ten words, c0 on either side of a word seam, every box height modulo kRows)
+  for (int k = c0 >> 6; k <= (c1 >> 6); ++k) {
     const int lo = max(c0 - 64 * k, 0), hi = min(c1 - 64 * k, 63);
     const unsigned long long in_box = (~0ull << lo) & (~0ull >> (63 - hi));
     for (int i0 = b.y0; i0 <= b.y1; i0 += kRows) {
