@@ -541,6 +541,12 @@ class Engine:
         io.d_pose, io.d_ut, io.d_u0, io.d_ck = _ptr(pose), _ptr(ut), _ptr(u0), _ptr(ck)
         check(lib().eea_debug_phase_timing(self.h, B, C.byref(io), C.c_void_p(stream or 0), _ptr(stamps)))
 
+    def _tick(self, symbol, extra, B, coll, dwa, stream, *io_args):
+        """one tick entry: the two structs of io_args (_tick_io), `symbol` with `extra` between the window and the stream"""
+        io, t = self._tick_io(*io_args)
+        check(getattr(lib(), symbol)(self.h, B, C.byref(io), C.byref(t), C.byref(coll) if coll is not None else None, C.byref(dwa),
+                                     *extra, C.c_void_p(stream or 0)))
+
     @staticmethod
     def _tick_io(pose, ut, follow, count, u, vb, grid, traj, valid, skip, val_dt, val_horizon, source, mem_cols, n_mem,
                  mem_stride, status, grid_epoch):
@@ -557,37 +563,30 @@ class Engine:
                    source=None, mem_cols=None, n_mem=None, mem_stride=0, status=None, stream=None, grid_epoch=0):
         """eea_tick_batch: one iteration of Exploration::control's loop body (exploration.hpp:220-279) for B robots.
         coll / dwa: collision_cfg(...) / dwa_cfg(...)"""
-        io, t = self._tick_io(pose, ut, follow, count, u, vb, grid, traj, valid, skip, val_dt, val_horizon, source, mem_cols,
-                              n_mem, mem_stride, status, grid_epoch)
-        check(lib().eea_tick_batch(self.h, B, C.byref(io), C.byref(t), C.byref(coll), C.byref(dwa), C.c_void_p(stream or 0)))
+        self._tick("eea_tick_batch", (), B, coll, dwa, stream, pose, ut, follow, count, u, vb, grid, traj, valid, skip, val_dt,
+                   val_horizon, source, mem_cols, n_mem, mem_stride, status, grid_epoch)
 
     def tick_batch_fleet(self, layer, B, pose, ut, follow, count, u, vb, grid, traj, valid, skip, coll, dwa, val_dt, val_horizon,
                          source=None, mem_cols=None, n_mem=None, mem_stride=0, status=None, stream=None, grid_epoch=0):
         """eea_tick_batch_fleet: tick_batch with the FleetLayer `layer` in validate_control and the dynamic window -- the other
         robots' bodies are obstacles; robot r of the tick is robot r of the layer (updated on the same stream before)"""
-        io, t = self._tick_io(pose, ut, follow, count, u, vb, grid, traj, valid, skip, val_dt, val_horizon, source, mem_cols,
-                              n_mem, mem_stride, status, grid_epoch)
-        check(lib().eea_tick_batch_fleet(self.h, B, C.byref(io), C.byref(t), C.byref(coll), C.byref(dwa),
-                                         layer.h if layer is not None else None, C.c_void_p(stream or 0)))
+        self._tick("eea_tick_batch_fleet", (layer.h if layer is not None else None,), B, coll, dwa, stream, pose, ut, follow, count,
+                   u, vb, grid, traj, valid, skip, val_dt, val_horizon, source, mem_cols, n_mem, mem_stride, status, grid_epoch)
 
     def tick_batch_footprint(self, fp, B, pose, ut, follow, count, u, vb, grid, traj, valid, skip, coll, dwa, val_dt, val_horizon,
                              sq=None, source=None, mem_cols=None, n_mem=None, mem_stride=0, status=None, stream=None):
         """eea_tick_batch_footprint: tick_batch with the polygon base fp (a Footprint) in validate_control and the dynamic
         window; sq: the int32 plane of distance_field for the grid (rebuilt by the caller when the grid changes) or None"""
-        io, t = self._tick_io(pose, ut, follow, count, u, vb, grid, traj, valid, skip, val_dt, val_horizon, source, mem_cols,
-                              n_mem, mem_stride, status, 0)
-        check(lib().eea_tick_batch_footprint(self.h, B, C.byref(io), C.byref(t), C.byref(coll), C.byref(dwa),
-                                             C.byref(fp) if fp is not None else None, _ptr(sq), C.c_void_p(stream or 0)))
+        self._tick("eea_tick_batch_footprint", (C.byref(fp) if fp is not None else None, _ptr(sq)), B, coll, dwa, stream, pose, ut,
+                   follow, count, u, vb, grid, traj, valid, skip, val_dt, val_horizon, source, mem_cols, n_mem, mem_stride, status, 0)
 
     def tick_batch_bodies(self, layer, B, pose, ut, follow, count, u, vb, grid, traj, valid, skip, coll, dwa, val_dt, val_horizon,
                           sq=None, source=None, mem_cols=None, n_mem=None, mem_stride=0, status=None, stream=None):
         """eea_tick_batch_bodies: tick_batch_footprint with the BodyLayer `layer` in validate_control and the dynamic window --
         the other robots' polygon bodies are obstacles; robot r of the tick is robot r of the layer (updated on the same
         stream before).  The footprint is the layer's"""
-        io, t = self._tick_io(pose, ut, follow, count, u, vb, grid, traj, valid, skip, val_dt, val_horizon, source, mem_cols,
-                              n_mem, mem_stride, status, 0)
-        check(lib().eea_tick_batch_bodies(self.h, B, C.byref(io), C.byref(t), C.byref(coll) if coll is not None else None,
-                                          C.byref(dwa), layer.h if layer is not None else None, _ptr(sq), C.c_void_p(stream or 0)))
+        self._tick("eea_tick_batch_bodies", (layer.h if layer is not None else None, _ptr(sq)), B, coll, dwa, stream, pose, ut,
+                   follow, count, u, vb, grid, traj, valid, skip, val_dt, val_horizon, source, mem_cols, n_mem, mem_stride, status, 0)
 
     def rollout_batch(self, B, pose, ut, traj, status=None, stream=None):
         check(lib().eea_rollout_batch(self.h, B, _ptr(pose), _ptr(ut), _ptr(traj), _ptr(status),

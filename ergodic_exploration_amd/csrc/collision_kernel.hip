@@ -586,7 +586,8 @@ hipError_t launch_tick_begin(int* d_follow, unsigned* d_count, int* d_skip, unsi
 // was rejected (one workgroup per robot as above; robots with a valid twist leave at once).  ONE inflated map serves both
 // launches (and, with grid_epoch != 0, the ticks that follow on an unchanged grid).  The cost model takes every robot as
 // one that searches (the worst case: the inflated map pays for itself at a fraction of that).
-hipError_t launch_validate_and_dwa_fleet(const CollisionParams& c, const DwaParams& d, const int8_t* d_grid,
+// layer: null, or the fleet layer in every collision test of both launches (eea_tick_batch_fleet)
+hipError_t launch_validate_and_dwa_fleet(const CollisionParams& c, const DwaParams& d, const FleetView* layer, const int8_t* d_grid,
                                          unsigned long long grid_epoch, const double* d_x0, const double* d_vb,
                                          const double* d_traj, unsigned n_ref, double dt_ref, double val_dt, unsigned val_steps,
                                          int* d_valid, int* d_follow, unsigned* d_count, double* d_u, int* d_source, unsigned P,
@@ -596,34 +597,19 @@ hipError_t launch_validate_and_dwa_fleet(const CollisionParams& c, const DwaPara
   const DwaGeometry g(d);
   if (!g.fits()) return hipErrorInvalidValue;
   const FleetTick ft{ d_valid, d_follow, d_count, d_u, d_source };
+  // both launches in the instance <MAP, LAYER>; view: the kernels' last argument (LayerArg<LAYER>)
+  const auto launch = [&](const HitMap& m, auto map, auto with_layer, const auto& view) {
+    constexpr bool MAP = decltype(map)::value, LAYER = decltype(with_layer)::value;
+    hipLaunchKernelGGL((validate_control_kernel<MAP, LAYER>), dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, s, c, m, d_grid, d_x0,
+                       d_u, val_dt, val_steps, P, d_valid, view);
+    hipLaunchKernelGGL((dwa_control_kernel<MAP, true, LAYER>), dim3(P), dim3(g.block), g.lds, s, c, d, m, d_grid, d_x0, d_vb,
+                       static_cast<const double*>(nullptr), d_traj, n_ref, dt_ref, static_cast<double*>(nullptr),
+                       static_cast<int*>(nullptr), ft, view);
+  };
   return with_map_or_ring(static_cast<size_t>(P) * (val_steps + g.nsamp * d.steps), d.steps, c, d_grid, grid_epoch, s,
                           [&](const HitMap& m, auto map) {
-    hipLaunchKernelGGL(validate_control_kernel<decltype(map)::value>, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, s, c, m,
-                       d_grid, d_x0, d_u, val_dt, val_steps, P, d_valid, NoFleetLayer{});
-    hipLaunchKernelGGL((dwa_control_kernel<decltype(map)::value, true>), dim3(P), dim3(g.block), g.lds, s, c, d, m, d_grid, d_x0,
-                       d_vb, static_cast<const double*>(nullptr), d_traj, n_ref, dt_ref, static_cast<double*>(nullptr),
-                       static_cast<int*>(nullptr), ft, NoFleetLayer{});
-  });
-}
-
-// ... with a fleet layer in every collision test of both launches (eea_tick_batch_fleet)
-hipError_t launch_validate_and_dwa_fleet_layer(const CollisionParams& c, const DwaParams& d, const FleetView& v, const int8_t* d_grid,
-                                               unsigned long long grid_epoch, const double* d_x0, const double* d_vb,
-                                               const double* d_traj, unsigned n_ref, double dt_ref, double val_dt,
-                                               unsigned val_steps, int* d_valid, int* d_follow, unsigned* d_count, double* d_u,
-                                               int* d_source, unsigned P, hipStream_t s)
-{
-  if (P == 0) return hipSuccess;
-  const DwaGeometry g(d);
-  if (!g.fits()) return hipErrorInvalidValue;
-  const FleetTick ft{ d_valid, d_follow, d_count, d_u, d_source };
-  return with_map_or_ring(static_cast<size_t>(P) * (val_steps + g.nsamp * d.steps), d.steps, c, d_grid, grid_epoch, s,
-                          [&](const HitMap& m, auto map) {
-    hipLaunchKernelGGL((validate_control_kernel<decltype(map)::value, true>), dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, s,
-                       c, m, d_grid, d_x0, d_u, val_dt, val_steps, P, d_valid, v);
-    hipLaunchKernelGGL((dwa_control_kernel<decltype(map)::value, true, true>), dim3(P), dim3(g.block), g.lds, s, c, d, m, d_grid,
-                       d_x0, d_vb, static_cast<const double*>(nullptr), d_traj, n_ref, dt_ref, static_cast<double*>(nullptr),
-                       static_cast<int*>(nullptr), ft, v);
+    if (layer != nullptr) launch(m, map, std::true_type{}, *layer);
+    else launch(m, map, std::false_type{}, NoFleetLayer{});
   });
 }
 

@@ -320,9 +320,11 @@ hipError_t launch_dwa_control(const CollisionParams& c, const DwaParams& d, cons
                               const double* d_xt_ref, unsigned n_ref, double dt_ref, unsigned P,
                               double* d_u_opt, int* d_found, hipStream_t s);
 // eea_tick_batch: step 1 (follow counters, skip mask) and steps 3 + 4 (validate_control; the dynamic window where it failed,
-// per robot towards its own twist or along its optTraj, and the state update) of the fleet tick
+// per robot towards its own twist or along its optTraj, and the state update) of the fleet tick.  layer: null, or the fleet
+// layer (below) in every collision test of both steps; robot r of the tick is robot r of the layer
+struct FleetView;
 hipError_t launch_tick_begin(int* d_follow, unsigned* d_count, int* d_skip, unsigned dwa_steps, unsigned P, hipStream_t s);
-hipError_t launch_validate_and_dwa_fleet(const CollisionParams& c, const DwaParams& d, const int8_t* d_grid,
+hipError_t launch_validate_and_dwa_fleet(const CollisionParams& c, const DwaParams& d, const FleetView* layer, const int8_t* d_grid,
                                          unsigned long long grid_epoch, const double* d_x0, const double* d_vb,
                                          const double* d_traj, unsigned n_ref, double dt_ref, double val_dt, unsigned val_steps,
                                          int* d_valid, int* d_follow, unsigned* d_count, double* d_u, int* d_source, unsigned P,
@@ -374,16 +376,19 @@ hipError_t launch_footprint_check(const CollisionParams& c, const FootprintArgs&
 hipError_t launch_footprint_traj_first(const CollisionParams& c, const FootprintArgs& f, const int8_t* d_grid, const int* d_sq,
                                        const double* d_traj, unsigned B, unsigned T, int* d_step, hipStream_t s);
 // ---- footprint planning (footprint_plan_kernel.hip): launch_validate_control / launch_dwa_control /
-// launch_validate_and_dwa_fleet with the footprint's verdict at every step; d_sq as above
-hipError_t launch_footprint_validate(const CollisionParams& c, const FootprintArgs& f, const int8_t* d_grid, const int* d_sq,
-                                     const double* d_x0, const double* d_u, double dt, unsigned steps, unsigned P, int* d_valid,
-                                     hipStream_t s);
-hipError_t launch_footprint_dwa(const CollisionParams& c, const DwaParams& d, const FootprintArgs& f, const int8_t* d_grid,
-                                const int* d_sq, const double* d_x0, const double* d_vb, const double* d_vref,
+// launch_validate_and_dwa_fleet with the footprint's verdict at every step; d_sq as above.  bodies: null, or the body layer
+// (below) in every verdict; in the tick robot r is robot r of the layer
+struct BodyView;
+struct BodyArgs;
+hipError_t launch_footprint_validate(const CollisionParams& c, const FootprintArgs& f, const BodyArgs* bodies, const int8_t* d_grid,
+                                     const int* d_sq, const double* d_x0, const double* d_u, double dt, unsigned steps, unsigned P,
+                                     int* d_valid, hipStream_t s);
+hipError_t launch_footprint_dwa(const CollisionParams& c, const DwaParams& d, const FootprintArgs& f, const BodyArgs* bodies,
+                                const int8_t* d_grid, const int* d_sq, const double* d_x0, const double* d_vb, const double* d_vref,
                                 const double* d_xt_ref, unsigned n_ref, double dt_ref, unsigned P, double* d_u_opt, int* d_found,
                                 hipStream_t s);
 hipError_t launch_footprint_validate_and_dwa_fleet(const CollisionParams& c, const DwaParams& d, const FootprintArgs& f,
-                                                   const int8_t* d_grid, const int* d_sq, const double* d_x0, const double* d_vb,
+                                                   const BodyView* bodies, const int8_t* d_grid, const int* d_sq, const double* d_x0, const double* d_vb,
                                                    const double* d_traj, unsigned n_ref, double dt_ref, double val_dt,
                                                    unsigned val_steps, int* d_valid, int* d_follow, unsigned* d_count, double* d_u,
                                                    int* d_source, unsigned P, hipStream_t s);
@@ -418,12 +423,6 @@ hipError_t launch_fleet_layer_update(const CollisionParams& c, const FleetView& 
 // collisionCheck of P poses with the layer: d_grid may be null (robots only), d_self may be null (no pose is a robot's own)
 hipError_t launch_fleet_collision_check(const CollisionParams& c, const FleetView& v, const int8_t* d_grid, const double* d_pose,
                                         const int* d_self, unsigned P, int* d_hit, hipStream_t s);
-// launch_validate_and_dwa_fleet with the layer in every collision test; robot r of the tick is robot r of the layer
-hipError_t launch_validate_and_dwa_fleet_layer(const CollisionParams& c, const DwaParams& d, const FleetView& v, const int8_t* d_grid,
-                                               unsigned long long grid_epoch, const double* d_x0, const double* d_vb,
-                                               const double* d_traj, unsigned n_ref, double dt_ref, double val_dt,
-                                               unsigned val_steps, int* d_valid, int* d_follow, unsigned* d_count, double* d_u,
-                                               int* d_source, unsigned P, hipStream_t s);
 
 // the layers' in-place inclusive prefix sum along every row of an int32 map [h][w] (fleet_layer_kernel.hip)
 hipError_t launch_fleet_row_scan(int* d_map, int w, int h, hipStream_t s);
@@ -456,19 +455,6 @@ hipError_t launch_body_layer_update(const CollisionParams& c, const FootprintArg
 // the footprint's verdict of P poses on the grid (may be null: robots only) with the bodies of the others
 hipError_t launch_body_check(const CollisionParams& c, const FootprintArgs& f, const BodyArgs& a, const int8_t* d_grid,
                              const int* d_sq, const double* d_pose, unsigned P, int* d_hit, hipStream_t s);
-// launch_footprint_validate / _dwa / _validate_and_dwa_fleet with the layer in every verdict (footprint_plan_kernel.hip)
-hipError_t launch_body_validate(const CollisionParams& c, const FootprintArgs& f, const BodyArgs& a, const int8_t* d_grid,
-                                const int* d_sq, const double* d_x0, const double* d_u, double dt, unsigned steps, unsigned P,
-                                int* d_valid, hipStream_t s);
-hipError_t launch_body_dwa(const CollisionParams& c, const DwaParams& d, const FootprintArgs& f, const BodyArgs& a,
-                           const int8_t* d_grid, const int* d_sq, const double* d_x0, const double* d_vb, const double* d_vref,
-                           const double* d_xt_ref, unsigned n_ref, double dt_ref, unsigned P, double* d_u_opt, int* d_found,
-                           hipStream_t s);
-hipError_t launch_body_validate_and_dwa_fleet(const CollisionParams& c, const DwaParams& d, const FootprintArgs& f, const BodyView& v,
-                                              const int8_t* d_grid, const int* d_sq, const double* d_x0, const double* d_vb,
-                                              const double* d_traj, unsigned n_ref, double dt_ref, double val_dt,
-                                              unsigned val_steps, int* d_valid, int* d_follow, unsigned* d_count, double* d_u,
-                                              int* d_source, unsigned P, hipStream_t s);
 
 // ---- range sensing of a simulated fleet (sense_kernel.hip) -------------------------------
 // every robot's 8 * range_cells rays through d_truth: the cells they cross are copied into d_known, d_ranges [P][8R]

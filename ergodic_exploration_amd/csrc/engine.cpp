@@ -3,6 +3,8 @@
 // runs in the HIP kernels (control_kernel.hip, phik_kernel.hip, collision_kernel.hip); the
 // host code here only prepares their inputs the way the reference's host code does
 // (steps_ truncation, grid coordinates by accumulation, covariance inverse).
+// This file: the entries that take an eea_engine (and the free functions of the controller's classes).  The entries that take
+// a device or a layer are grid_entries.cpp; what both need is entry_util.hpp.
 #include "../../include/ergodic_amd.h"
 
 #include <atomic>
@@ -16,9 +18,19 @@
 #include <string>
 #include <vector>
 
-#include "abi_util.hpp"
-#include "common.hpp"
-#include "footprint_planes.hpp"
+#include "entry_util.hpp"
+
+// (of entry_util.hpp: the buffers of the engine, and what eea_set_target_gain and the ticks ask of their arguments)
+using eea::as;
+using eea::collision_cfg_refusal;
+using eea::collision_params;
+using eea::DevBuf;
+using eea::dwa_window_refusal;
+using eea::footprint_call_refusal;
+using eea::gain_refusal;
+using eea::grid_params;
+using eea::horizon_steps;
+using eea::named;
 
 namespace
 {
@@ -41,60 +53,6 @@ using eea::fail;
 unsigned axis_length(double lower, double upper, double resolution)
 {
   return static_cast<unsigned>(std::round((upper - lower) / resolution));
-}
-
-// Device memory that goes with its owner: a member of the engine (freed by `delete e`, after eea_destroy has stopped
-// everything that reads it) or a local of one call.  Never of static storage duration: a free during static destruction
-// would run after the HIP runtime has gone.
-struct DevBuf
-{
-  void* p = nullptr;
-  size_t cap = 0;
-  DevBuf() = default;
-  DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.detach(); }
-  DevBuf& operator=(DevBuf&& o) noexcept
-  {
-    if (this != &o) {
-      release();
-      cap = o.cap;
-      p = o.detach();
-    }
-    return *this;
-  }
-  ~DevBuf() { release(); }
-  hipError_t reserve(size_t bytes)
-  {
-    if (bytes <= cap) return hipSuccess;
-    release();
-    const hipError_t e = hipMalloc(&p, bytes);
-    if (e == hipSuccess) cap = bytes;
-    return e;
-  }
-  void release()
-  {
-    if (p) (void)hipFree(p);
-    detach();
-  }
-  // the pointer, no longer owned (buffers retired behind an event: sum_workspace)
-  void* detach()
-  {
-    void* const q = p;
-    p = nullptr;
-    cap = 0;
-    return q;
-  }
-};
-
-// device pointers cross the C ABI and sit in DevBuf untyped: as<R>(p) is p as reals of the call's precision
-template <typename R>
-R* as(void* p)
-{
-  return static_cast<R*>(p);
-}
-template <typename R>
-const R* as(const void* p)
-{
-  return static_cast<const R*>(p);
 }
 
 // Accumulated grid coordinates and the cos tables built from them (cx [K][nx], cy [ny][K]) of ONE grid and domain.  The
@@ -861,52 +819,6 @@ eea_status occupancy_rows_impl(eea_engine* e, unsigned nx, unsigned ny_total, un
   EEA_HIP(eea::launch_spatial_coeff_cells<R>(d_occ_rows, nx, nrows, e->K, as<R>(e->tab.cx.p),
                                              as<R>(e->tab.cy.p) + static_cast<size_t>(row0) * e->K, as<R>(e->d_lut.p),
                                              as<R>(e->d_work.p), as<R>(d_raw_out), s, as<R>(d_mass_out)));
-  return EEA_OK;
-}
-
-// DynamicWindow::DynamicWindow (dynamic_window.cpp:71-90) from the C configuration
-eea_status make_dwa_params(const eea_dwa_cfg* dcfg, eea::DwaParams& d)
-{
-  if (dcfg == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null DWA configuration");
-  d.dt = dcfg->dt;
-  d.acc_dt = dcfg->acc_dt;
-  d.acc_lim[0] = dcfg->acc_lim_x;
-  d.acc_lim[1] = dcfg->acc_lim_y;
-  d.acc_lim[2] = dcfg->acc_lim_th;
-  d.vmax[0] = dcfg->max_vel_x;
-  d.vmax[1] = dcfg->max_vel_y;
-  d.vmax[2] = dcfg->max_rot_vel;
-  d.vmin[0] = dcfg->min_vel_x;
-  d.vmin[1] = dcfg->min_vel_y;
-  d.vmin[2] = dcfg->min_rot_vel;
-  // a sample count of 0 is raised to 1 (DynamicWindow::DynamicWindow, dynamic_window.cpp:71-90)
-  d.ns[0] = dcfg->vx_samples ? dcfg->vx_samples : 1;
-  d.ns[1] = dcfg->vy_samples ? dcfg->vy_samples : 1;
-  d.ns[2] = dcfg->vth_samples ? dcfg->vth_samples : 1;
-  d.steps = static_cast<unsigned>(std::abs(dcfg->horizon / dcfg->dt));
-  if (static_cast<size_t>(d.ns[0]) * d.ns[1] * d.ns[2] > 8192) return fail(EEA_ERR_UNSUPPORTED, "more than 8192 DWA samples");
-  return EEA_OK;
-}
-
-// The trajectory objective (dynamic_window.cpp:258-286) reads column round((n_ref - 1) t / tf) of the reference at every
-// rollout step, tf = n_ref dt_ref; the reference's xt_ref.col(j) (:277) is bounds-checked and throws.  The kernel's own
-// expression with t accumulated by repeated += dt, on the host: the call is refused when a step would read outside
-// [0, n_ref - 1] (for robot r that is robot r + 1's trajectory, or memory behind the buffer) or when tf is not positive
-// (dt_ref = 0: the index is NaN).
-eea_status check_reference_index(const eea::DwaParams& d, unsigned n_ref, double dt_ref)
-{
-  const double tf = static_cast<double>(n_ref) * dt_ref;
-  if (!(tf > 0.0)) return fail(EEA_ERR_INVALID_ARGUMENT, "the reference trajectory needs n_ref * dt_ref > 0");
-  const double last = static_cast<double>(n_ref - 1);
-  double t = 0.0;
-  for (unsigned st = 0; st < d.steps; ++st) {
-    const double jj = std::round(last * t / tf);
-    if (!(jj >= 0.0 && jj <= last)) {
-      return fail(EEA_ERR_INVALID_ARGUMENT, "the DWA rollout runs past the reference trajectory (step " + std::to_string(st) +
-                                                " reads column " + std::to_string(jj) + " of " + std::to_string(n_ref) + ")");
-    }
-    t += d.dt;
-  }
   return EEA_OK;
 }
 
@@ -1835,416 +1747,6 @@ eea_status eea_target_fill(int device, unsigned n_gauss, const double* mu, const
   return EEA_OK;
 }
 
-// ---- collision lookups ---------------------------------------------------------------------
-// The checks of an eea_collision_cfg, one refusal each.  Every entry makes the ones it needs, in its own order, before it
-// selects a device, and then takes its parameters (collision_params / grid_params).
-static eea_status cfg_given(const eea_collision_cfg* cfg)
-{
-  return cfg != nullptr ? EEA_OK : fail(EEA_ERR_INVALID_ARGUMENT, "null collision config");
-}
-// Collision::Collision (collision.cpp:46-63)
-static eea_status cfg_radii_ordered(const eea_collision_cfg* cfg)
-{
-  if (!(cfg->search_radius < cfg->boundary_radius)) return EEA_OK;
-  return fail(EEA_ERR_INVALID_ARGUMENT, "Search radius must be at least the same size as the boundary radius");
-}
-static eea_status cfg_threshold_in_range(const eea_collision_cfg* cfg)
-{
-  if (!(cfg->occupied_threshold > 100.0 || cfg->occupied_threshold < 0.0)) return EEA_OK;
-  return fail(EEA_ERR_INVALID_ARGUMENT, "Occupied threshold must be between 0 and 100");
-}
-// (with a size of 0 the reference's gridBounds, grid.cpp:96-100, lets every cell index through)
-static eea_status cfg_has_cells(const eea_collision_cfg* cfg)
-{
-  if (cfg->xsize != 0 && cfg->ysize != 0) return EEA_OK;
-  return fail(EEA_ERR_INVALID_ARGUMENT, "the grid's xsize and ysize must be positive");
-}
-static eea_status cfg_has_resolution(const eea_collision_cfg* cfg)
-{
-  return cfg->resolution > 0.0 ? EEA_OK : fail(EEA_ERR_INVALID_ARGUMENT, "the grid's resolution must be positive");
-}
-// what collisionCheck, validate_control, the dynamic window and a fleet layer ask first: Collision::Collision's own checks
-static eea_status collision_cfg_refusal(const eea_collision_cfg* cfg)
-{
-  eea_status st = cfg_given(cfg);
-  if (st == EEA_OK) st = cfg_radii_ordered(cfg);
-  if (st == EEA_OK) st = cfg_threshold_in_range(cfg);
-  return st;
-}
-// what the clearance and the distance calls ask first: those around a grid the kernels can index
-static eea_status grid_query_cfg_refusal(const eea_collision_cfg* cfg)
-{
-  eea_status st = cfg_given(cfg);
-  if (st == EEA_OK) st = cfg_has_resolution(cfg);
-  if (st == EEA_OK) st = cfg_radii_ordered(cfg);
-  if (st == EEA_OK) st = cfg_threshold_in_range(cfg);
-  if (st == EEA_OK) st = cfg_has_cells(cfg);
-  return st;
-}
-// what the sensor, the gain field and (behind its own arguments) a fleet layer ask of the grid
-static eea_status grid_cfg_refusal(const eea_collision_cfg* cfg)
-{
-  const eea_status st = cfg_has_cells(cfg);
-  return st == EEA_OK ? cfg_has_resolution(cfg) : st;
-}
-
-// the geometry and the threshold of a configuration, the radii 0 (the sensor and the gain field do not read them)
-static eea::CollisionParams grid_params(const eea_collision_cfg* cfg)
-{
-  return eea::CollisionParams{ cfg->xmin, cfg->ymin, cfg->resolution, cfg->xsize, cfg->ysize, 0, 0, 0, cfg->occupied_threshold };
-}
-// ... with CollisionConfig's radii in cells (collision.cpp:130-133)
-static eea::CollisionParams collision_params(const eea_collision_cfg* cfg)
-{
-  eea::CollisionParams c = grid_params(cfg);
-  c.r_bnd = static_cast<int>(std::floor(cfg->boundary_radius / cfg->resolution));
-  c.r_col = static_cast<int>(std::floor((cfg->boundary_radius + cfg->obstacle_threshold) / cfg->resolution));
-  c.r_max = static_cast<int>(std::floor(cfg->search_radius / cfg->resolution));
-  return c;
-}
-
-eea_status eea_collision_check_batch(int device, const eea_collision_cfg* cfg, const int8_t* d_grid,
-                                     const double* d_pose, unsigned P, int* d_hit, void* stream)
-{
-  const eea_status st = collision_cfg_refusal(cfg);
-  if (st != EEA_OK) return st;
-  if (d_grid == nullptr || d_pose == nullptr || d_hit == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
-  const eea::CollisionParams c = collision_params(cfg);
-  EEA_HIP(hipSetDevice(device));
-  EEA_HIP(eea::launch_collision_check(c, d_grid, d_pose, P, d_hit, static_cast<hipStream_t>(stream)));
-  return EEA_OK;
-}
-
-eea_status eea_validate_control_batch(int device, const eea_collision_cfg* cfg, const int8_t* d_grid,
-                                      const double* d_x0, const double* d_u, double dt,
-                                      double horizon, unsigned P, int* d_valid, void* stream)
-{
-  const eea_status st = collision_cfg_refusal(cfg);
-  if (st != EEA_OK) return st;
-  if (d_grid == nullptr || d_x0 == nullptr || d_u == nullptr || d_valid == nullptr) {
-    return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
-  }
-  const eea::CollisionParams c = collision_params(cfg);
-  const unsigned steps = static_cast<unsigned>(std::abs(horizon / dt));  // numerics.hpp:317
-  EEA_HIP(hipSetDevice(device));
-  EEA_HIP(eea::launch_validate_control(c, d_grid, d_x0, d_u, dt, steps, P, d_valid,
-                                       static_cast<hipStream_t>(stream)));
-  return EEA_OK;
-}
-
-eea_status eea_integrate_twist_batch(int device, const double* d_x0, const double* d_u, double dt, unsigned P, double* d_out,
-                                     int normalize_heading, void* stream)
-{
-  if (d_x0 == nullptr || d_u == nullptr || d_out == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
-  EEA_HIP(hipSetDevice(device));
-  EEA_HIP(eea::launch_integrate_twist(d_x0, d_u, dt, P, d_out, normalize_heading != 0, static_cast<hipStream_t>(stream)));
-  return EEA_OK;
-}
-
-// ---- clearance queries: Collision::minDistance / minDirection (collision.cpp:65-124) -----------
-static_assert(sizeof(eea_clearance) == 4 * sizeof(int), "the kernels write an eea_clearance as four ints");
-
-// the checks of the configuration both clearance calls share, before the device is selected: ... and the key bound
-static eea_status clearance_cfg_refusal(const eea_collision_cfg* cfg)
-{
-  const eea_status st = grid_query_cfg_refusal(cfg);
-  if (st != EEA_OK) return st;
-  if (static_cast<unsigned long long>(cfg->xsize) * cfg->ysize > (1ull << 31)) {
-    return fail(EEA_ERR_UNSUPPORTED, "xsize * ysize above 2^31");
-  }
-  if (!eea::clearance_supported(collision_params(cfg))) {
-    return fail(EEA_ERR_UNSUPPORTED, "the search radius is too large in cells: the clearance key (|d|^2, visit index) does not fit 32 bits");
-  }
-  return EEA_OK;
-}
-
-eea_status eea_clearance_batch(int device, const eea_collision_cfg* cfg, const int8_t* d_grid, const double* d_pose, unsigned P,
-                               eea_clearance* d_out, double* d_dmin, double* d_disp, void* stream)
-{
-  const eea_status st = clearance_cfg_refusal(cfg);
-  if (st != EEA_OK) return st;
-  if (d_grid == nullptr || d_pose == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
-  if (d_out == nullptr && d_dmin == nullptr && d_disp == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "no output");
-  if (P == 0) return EEA_OK;
-  const eea::CollisionParams c = collision_params(cfg);
-  EEA_HIP(hipSetDevice(device));
-  EEA_HIP(eea::launch_clearance(c, cfg->boundary_radius, d_grid, d_pose, P, reinterpret_cast<int*>(d_out), d_dmin, d_disp,
-                                static_cast<hipStream_t>(stream)));
-  return EEA_OK;
-}
-
-eea_status eea_clearance_field(int device, const eea_collision_cfg* cfg, const int8_t* d_grid, eea_clearance* d_field,
-                               double* d_dmin, void* stream)
-{
-  const eea_status st = clearance_cfg_refusal(cfg);
-  if (st != EEA_OK) return st;
-  if (d_grid == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
-  if (d_field == nullptr && d_dmin == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "no output");
-  const eea::CollisionParams c = collision_params(cfg);
-  EEA_HIP(hipSetDevice(device));
-  EEA_HIP(eea::launch_clearance(c, cfg->boundary_radius, d_grid, nullptr, static_cast<size_t>(c.xsize) * c.ysize,
-                                reinterpret_cast<int*>(d_field), d_dmin, nullptr, static_cast<hipStream_t>(stream)));
-  return EEA_OK;
-}
-
-// ---- distance field: the exact Euclidean distance transform of the occupied cells (distance_kernel.hip) ----
-// the checks of the configuration the three distance calls share, before the device is selected
-static eea_status distance_cfg_refusal(const eea_collision_cfg* cfg)
-{
-  const eea_status st = grid_query_cfg_refusal(cfg);
-  if (st != EEA_OK) return st;
-  if (cfg->xsize > eea::kDistanceMaxSide || cfg->ysize > eea::kDistanceMaxSide) {
-    return fail(EEA_ERR_UNSUPPORTED, "the distance field takes grids of up to EEA_DISTANCE_MAX_SIDE cells per side");
-  }
-  return EEA_OK;
-}
-
-eea_status eea_distance_field(int device, const eea_collision_cfg* cfg, const int8_t* d_grid, int* d_sq, int* d_nearest, void* stream)
-{
-  const eea_status st = distance_cfg_refusal(cfg);
-  if (st != EEA_OK) return st;
-  const eea::CollisionParams c = collision_params(cfg);
-  if (d_grid == nullptr || d_sq == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
-  EEA_HIP(hipSetDevice(device));
-  EEA_HIP(eea::launch_distance_field(c, d_grid, d_sq, d_nearest, static_cast<hipStream_t>(stream)));
-  return EEA_OK;
-}
-
-eea_status eea_distance_query_batch(int device, const eea_collision_cfg* cfg, const int* d_sq, const int* d_nearest,
-                                    const double* d_pose, unsigned P, eea_clearance* d_out, double* d_dmin, double* d_disp,
-                                    void* stream)
-{
-  const eea_status st = distance_cfg_refusal(cfg);
-  if (st != EEA_OK) return st;
-  const eea::CollisionParams c = collision_params(cfg);
-  if (d_sq == nullptr || d_pose == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
-  if (d_out == nullptr && d_dmin == nullptr && d_disp == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "no output");
-  if (d_nearest == nullptr && (d_out != nullptr || d_disp != nullptr)) {
-    return fail(EEA_ERR_INVALID_ARGUMENT, "d_out and d_disp need the field's d_nearest");
-  }
-  if (P == 0) return EEA_OK;
-  EEA_HIP(hipSetDevice(device));
-  EEA_HIP(eea::launch_distance_query(c, cfg->boundary_radius, d_sq, d_nearest, d_pose, P, reinterpret_cast<int*>(d_out), d_dmin,
-                                     d_disp, static_cast<hipStream_t>(stream)));
-  return EEA_OK;
-}
-
-eea_status eea_distance_traj_min(int device, const eea_collision_cfg* cfg, const int* d_sq, const int* d_nearest,
-                                 const double* d_traj, unsigned B, unsigned T, eea_clearance* d_out, int* d_step, double* d_dmin,
-                                 void* stream)
-{
-  const eea_status st = distance_cfg_refusal(cfg);
-  if (st != EEA_OK) return st;
-  const eea::CollisionParams c = collision_params(cfg);
-  if (d_sq == nullptr || d_traj == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
-  if (d_out == nullptr && d_step == nullptr && d_dmin == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "no output");
-  if (d_nearest == nullptr && d_out != nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "d_out needs the field's d_nearest");
-  if (T == 0 || T > 0x7fffffffu) return fail(EEA_ERR_INVALID_ARGUMENT, "T must be between 1 and 2^31 - 1");
-  if (B == 0) return EEA_OK;
-  EEA_HIP(hipSetDevice(device));
-  EEA_HIP(eea::launch_distance_traj_min(c, cfg->boundary_radius, d_sq, d_nearest, d_traj, B, T, reinterpret_cast<int*>(d_out),
-                                        d_step, d_dmin, static_cast<hipStream_t>(stream)));
-  return EEA_OK;
-}
-
-// ---- footprint collision: a convex polygon base through the distance field (footprint_kernel.hip) ----
-static_assert(sizeof(eea_footprint::x) == sizeof(double) * eea::kFootprintMaxVertices, "the header states the limit");
-
-// the footprint's own refusals (footprint_planes.hpp), before any device
-static eea_status footprint_refusal(const eea_footprint* fp, eea::FootprintPlanes& planes)
-{
-  if (fp == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null footprint");
-  // (n is checked before a vertex is read: the arrays hold EEA_FOOTPRINT_MAX_VERTICES)
-  const eea::FootprintFault fault = eea::footprint_planes(fp->n, fp->x, fp->y, planes);
-  return fault == eea::FootprintFault::none ? EEA_OK : fail(EEA_ERR_INVALID_ARGUMENT, eea::footprint_fault_text(fault));
-}
-
-eea_status eea_footprint_radii(const eea_footprint* fp, double* r_in, double* r_out)
-{
-  eea::FootprintPlanes planes;
-  const eea_status st = footprint_refusal(fp, planes);
-  if (st != EEA_OK) return st;
-  if (r_in != nullptr) *r_in = planes.r_in;
-  if (r_out != nullptr) *r_out = planes.r_out;
-  return EEA_OK;
-}
-
-// the footprint on the grid of cfg (both given), in the header's order, and what the kernels read of the footprint; r_out:
-// the circumscribed radius (may be null)
-static eea_status footprint_on_grid_refusal(const eea_collision_cfg* cfg, const eea_footprint* fp, eea::FootprintArgs& args,
-                                            double* r_out = nullptr)
-{
-  eea::FootprintPlanes planes;
-  eea_status st = footprint_refusal(fp, planes);
-  if (st == EEA_OK) st = grid_cfg_refusal(cfg);
-  if (st != EEA_OK) return st;
-  if (static_cast<unsigned long long>(cfg->xsize) * cfg->ysize > (1ull << 31)) {
-    return fail(EEA_ERR_UNSUPPORTED, "xsize * ysize above 2^31");
-  }
-  if (!eea::footprint_supported(planes, cfg->resolution)) {
-    return fail(EEA_ERR_UNSUPPORTED, "the footprint's circumscribed radius is above 1024 cells");
-  }
-  const eea::FootprintThresholds t = eea::footprint_thresholds(planes.r_in, planes.r_out, cfg->resolution);
-  args = eea::FootprintArgs{};
-  args.n = planes.n;
-  args.sq_hit = t.sq_hit;
-  args.sq_free = t.sq_free;
-  args.box = t.box;
-  args.v_min = eea::blocking_cutoff(cfg->occupied_threshold);
-  std::memcpy(args.nx, planes.nx, sizeof(args.nx));
-  std::memcpy(args.ny, planes.ny, sizeof(args.ny));
-  std::memcpy(args.h, planes.h, sizeof(args.h));
-  if (r_out != nullptr) *r_out = planes.r_out;
-  return EEA_OK;
-}
-
-// the checks the footprint's device calls share
-static eea_status footprint_call_refusal(const eea_collision_cfg* cfg, const eea_footprint* fp, const void* d_grid, const void* d_in,
-                                         const void* d_out, eea::FootprintArgs& args)
-{
-  if (cfg == nullptr || fp == nullptr || d_grid == nullptr || d_in == nullptr || d_out == nullptr) {
-    return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
-  }
-  return footprint_on_grid_refusal(cfg, fp, args);
-}
-
-eea_status eea_footprint_check_batch(int device, const eea_collision_cfg* cfg, const eea_footprint* fp, const int8_t* d_grid,
-                                     const int* d_sq, const double* d_pose, unsigned P, int* d_hit, void* stream)
-{
-  eea::FootprintArgs args;
-  const eea_status st = footprint_call_refusal(cfg, fp, d_grid, d_pose, d_hit, args);
-  if (st != EEA_OK) return st;
-  if (P == 0) return EEA_OK;
-  EEA_HIP(hipSetDevice(device));
-  EEA_HIP(eea::launch_footprint_check(grid_params(cfg), args, d_grid, d_sq, d_pose, P, d_hit, static_cast<hipStream_t>(stream)));
-  return EEA_OK;
-}
-
-eea_status eea_footprint_traj_first(int device, const eea_collision_cfg* cfg, const eea_footprint* fp, const int8_t* d_grid,
-                                    const int* d_sq, const double* d_traj, unsigned B, unsigned T, int* d_step, void* stream)
-{
-  eea::FootprintArgs args;
-  const eea_status st = footprint_call_refusal(cfg, fp, d_grid, d_traj, d_step, args);
-  if (st != EEA_OK) return st;
-  if (T == 0 || T > 0x7fffffffu) return fail(EEA_ERR_INVALID_ARGUMENT, "T must be between 1 and 2^31 - 1");
-  if (B == 0) return EEA_OK;
-  EEA_HIP(hipSetDevice(device));
-  EEA_HIP(eea::launch_footprint_traj_first(grid_params(cfg), args, d_grid, d_sq, d_traj, B, T, d_step,
-                                           static_cast<hipStream_t>(stream)));
-  return EEA_OK;
-}
-
-// ---- footprint planning: the polygon base in validate_control and the dynamic window (footprint_plan_kernel.hip) ----
-eea_status eea_footprint_validate_control_batch(int device, const eea_collision_cfg* cfg, const eea_footprint* fp,
-                                                const int8_t* d_grid, const int* d_sq, const double* d_x0, const double* d_u,
-                                                double dt, double horizon, unsigned P, int* d_valid, void* stream)
-{
-  eea::FootprintArgs args;
-  const eea_status st = footprint_call_refusal(cfg, fp, d_grid, d_x0, d_valid, args);
-  if (st != EEA_OK) return st;
-  if (d_u == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
-  if (P == 0) return EEA_OK;
-  const unsigned steps = static_cast<unsigned>(std::abs(horizon / dt));  // numerics.hpp:317
-  EEA_HIP(hipSetDevice(device));
-  EEA_HIP(eea::launch_footprint_validate(grid_params(cfg), args, d_grid, d_sq, d_x0, d_u, dt, steps, P, d_valid,
-                                         static_cast<hipStream_t>(stream)));
-  return EEA_OK;
-}
-
-eea_status eea_footprint_dwa_control_batch(int device, const eea_collision_cfg* ccfg, const eea_dwa_cfg* dcfg,
-                                           const eea_footprint* fp, const int8_t* d_grid, const int* d_sq, const double* d_x0,
-                                           const double* d_vb, const double* d_vref, const double* d_xt_ref, unsigned n_ref,
-                                           double dt_ref, unsigned P, double* d_u_opt, int* d_found, void* stream)
-{
-  eea::FootprintArgs args;
-  eea_status st = footprint_call_refusal(ccfg, fp, d_grid, d_x0, d_u_opt, args);
-  if (st != EEA_OK) return st;
-  // eea_dwa_control_batch's, in its order
-  if (dcfg == nullptr || d_vb == nullptr || d_found == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
-  if ((d_vref == nullptr) == (d_xt_ref == nullptr)) {
-    return fail(EEA_ERR_INVALID_ARGUMENT, "give either d_vref or d_xt_ref");
-  }
-  if (d_xt_ref != nullptr && n_ref == 0) return fail(EEA_ERR_INVALID_ARGUMENT, "empty reference trajectory");
-  eea::DwaParams d;
-  st = make_dwa_params(dcfg, d);
-  if (st != EEA_OK) return st;
-  if (d_xt_ref != nullptr) {
-    st = check_reference_index(d, n_ref, dt_ref);
-    if (st != EEA_OK) return st;
-  }
-  if (P == 0) return EEA_OK;
-  EEA_HIP(hipSetDevice(device));
-  EEA_HIP(eea::launch_footprint_dwa(grid_params(ccfg), d, args, d_grid, d_sq, d_x0, d_vb, d_vref, d_xt_ref, n_ref, dt_ref, P,
-                                    d_u_opt, d_found, static_cast<hipStream_t>(stream)));
-  return EEA_OK;
-}
-
-void eea_release_collision_caches(void)
-{
-  eea::release_collision_caches();
-  eea::release_clearance_caches();
-  eea::release_fleet_span_cache();  // (the span tables no fleet layer holds)
-}
-
-// ---- range sensing of a simulated fleet ------------------------------------------------------
-unsigned eea_sense_ray_count(unsigned range_cells) { return 8u * range_cells; }
-
-eea_status eea_sense_reveal_batch(int device, const eea_collision_cfg* cfg, unsigned range_cells, const int8_t* d_truth,
-                                  int8_t* d_known, const double* d_pose, const int* d_mask, unsigned P, int* d_ranges,
-                                  void* stream)
-{
-  if (cfg == nullptr || d_truth == nullptr || d_known == nullptr || d_pose == nullptr) {
-    return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
-  }
-  if (d_truth == d_known) return fail(EEA_ERR_INVALID_ARGUMENT, "d_truth and d_known must be different grids");
-  const eea_status st = grid_cfg_refusal(cfg);
-  if (st != EEA_OK) return st;
-  if (range_cells == 0) return fail(EEA_ERR_INVALID_ARGUMENT, "range_cells must be positive");
-  if (range_cells > 1024u) return fail(EEA_ERR_UNSUPPORTED, "range_cells above 1024");
-  if (P == 0) return EEA_OK;
-  const eea::CollisionParams c = grid_params(cfg);
-  EEA_HIP(hipSetDevice(device));
-  EEA_HIP(eea::launch_sense_reveal(c, range_cells, d_truth, d_known, d_pose, d_mask, P, d_ranges,
-                                   static_cast<hipStream_t>(stream)));
-  return EEA_OK;
-}
-
-eea_status eea_grid_census(int device, const eea_collision_cfg* cfg, const int8_t* d_grid, unsigned long long* d_counts,
-                           void* stream)
-{
-  if (cfg == nullptr || d_grid == nullptr || d_counts == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
-  const eea_status st = grid_cfg_refusal(cfg);
-  if (st != EEA_OK) return st;
-  const eea::CollisionParams c = grid_params(cfg);
-  EEA_HIP(hipSetDevice(device));
-  EEA_HIP(eea::launch_grid_census(c, d_grid, d_counts, static_cast<hipStream_t>(stream)));
-  return EEA_OK;
-}
-
-// ---- information-gain target ------------------------------------------------------------------
-// the argument checks eea_sense_gain_field and eea_set_target_gain share (after their null checks), before any HIP call
-static eea_status gain_refusal(const eea_collision_cfg* cfg, unsigned range_cells, unsigned stride)
-{
-  const eea_status st = grid_cfg_refusal(cfg);
-  if (st != EEA_OK) return st;
-  if (range_cells == 0) return fail(EEA_ERR_INVALID_ARGUMENT, "range_cells must be positive");
-  if (stride == 0) return fail(EEA_ERR_INVALID_ARGUMENT, "stride must be positive");
-  if (range_cells > 1024u) return fail(EEA_ERR_UNSUPPORTED, "range_cells above 1024");
-  return EEA_OK;
-}
-
-eea_status eea_sense_gain_field(int device, const eea_collision_cfg* cfg, unsigned range_cells, unsigned stride,
-                                const int8_t* d_known, unsigned* d_gain, void* stream)
-{
-  if (cfg == nullptr || d_known == nullptr || d_gain == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
-  const eea_status st = gain_refusal(cfg, range_cells, stride);
-  if (st != EEA_OK) return st;
-  const eea::CollisionParams c = grid_params(cfg);
-  EEA_HIP(hipSetDevice(device));
-  EEA_HIP(eea::launch_gain_field(c, range_cells, stride, d_known, d_gain, static_cast<hipStream_t>(stream)));
-  return EEA_OK;
-}
-
 eea_status eea_set_target_gain(eea_engine* e, const eea_collision_cfg* cfg, unsigned range_cells, unsigned stride,
                                const int8_t* d_known, double floor, double lx, double ly, unsigned* d_gain, void* stream)
 {
@@ -2293,57 +1795,14 @@ eea_status eea_set_target_gain(eea_engine* e, const eea_collision_cfg* cfg, unsi
 
 }  // extern "C"
 
-// ---- fleet layer: robots as obstacles to one another --------------------------------------------
-struct eea_fleet_layer
+// ---- the fleet tick: one iteration of Exploration<ModelT>::control's loop body for B robots (exploration.hpp:220-279) ----
+// See ergodic_amd.h.  The four entries differ in their obstacle model -- what a pose collides with in steps 3 and 4 -- and each
+// states its own below, top to bottom in the order a caller meets its refusals: tick_arguments_refusal (what every tick asks
+// of its arguments), the model's own refusals and its CollisionParams, then tick_run with the launch of steps 3 and 4.
+// A tick refuses, returns for B == 0 and builds its parameter blocks before the device is touched.
+static eea_status tick_arguments_refusal(const char* entry, const eea_engine* e, const eea_batch_io* io, const eea_tick_io* tick,
+                                         const eea_dwa_cfg* dcfg)
 {
-  int device = 0, body = 0, n_spans = 0;
-  eea::CollisionParams c{};
-  eea::FleetView v{};  // (count / cell point at d_count / d_cell)
-  int* d_count = nullptr;
-  int* d_cell = nullptr;
-};
-
-// ---- body layer: polygon robots as obstacles to one another (body_layer_kernel.hip) ----------------
-struct eea_body_layer
-{
-  int device = 0;
-  unsigned flags = 0;
-  eea_footprint fp{};
-  eea::CollisionParams c{};  // the grid's geometry and threshold (grid_params)
-  eea::FootprintArgs f{};
-  eea::BodyView v{};         // (cover / near / snap point into d_maps / d_snap)
-  int* d_block = nullptr;    // the allocation: kBodyGuard guard words, the maps, kBodyGuard guard words
-  int* d_maps = nullptr;     // cover [ysize][xsize], then near [near_h][near_w]: one clear
-  double* d_snap = nullptr;
-};
-
-// guard words on either side of the maps, written at creation and verified by eea_body_layer_read: a stamp outside the maps
-// is seen by the tests
-constexpr size_t kBodyGuard = 64;
-constexpr int kBodyGuardWord = 0x5a5a5a5a;
-
-// One tick of Exploration<ModelT>::control's loop body for B robots (exploration.hpp:220-279): see ergodic_amd.h.  with_layer: the
-// call is eea_tick_batch_fleet -- `layer` must not be null and is used in steps 3 and 4, and the messages name that entry.
-// foot: the call is eea_tick_batch_footprint -- steps 3 and 4 judge every pose by the polygon base (no layer then)
-// bodies: the call is eea_tick_batch_bodies -- the footprint is the body layer's, and steps 3 and 4 take the other robots'
-// bodies from it
-struct FootprintTick
-{
-  const eea_footprint* fp;
-  const int* d_sq;
-  bool with_bodies = false;
-  const eea_body_layer* bodies = nullptr;
-};
-static eea_status tick_batch_impl(eea_engine* e, unsigned B, const eea_batch_io* io, const eea_tick_io* tick,
-                                  const eea_collision_cfg* ccfg, const eea_dwa_cfg* dcfg, const eea_fleet_layer* layer,
-                                  bool with_layer, void* stream, const FootprintTick* foot = nullptr)
-{
-  // (refusals of several kinds, B == 0 and the parameter blocks come before the device is touched: no shared prologue)
-  const bool with_bodies = foot != nullptr && foot->with_bodies;
-  const char* const entry = with_bodies     ? "eea_tick_batch_bodies"
-                            : foot != nullptr ? "eea_tick_batch_footprint"
-                            : with_layer      ? "eea_tick_batch_fleet"
-                                              : "eea_tick_batch";  // (for the refusal messages)
   if (e == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null engine");
   if (io == nullptr || tick == nullptr || dcfg == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
   if (e->f32) return fail(EEA_ERR_UNSUPPORTED, std::string(entry) + " takes fp64 engines (poses and twists are doubles)");
@@ -2355,41 +1814,19 @@ static eea_status tick_batch_impl(eea_engine* e, unsigned B, const eea_batch_io*
   if (io->d_rec_ready != nullptr || io->d_ck_flag != nullptr) {
     return fail(EEA_ERR_UNSUPPORTED, std::string(entry) + " does not take the device-bound exchange buffers");
   }
-  if (with_layer && layer == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null fleet layer");
-  if (with_bodies && foot->bodies == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, std::string(entry) + ": null body layer");
-  eea::FootprintArgs fargs;
-  if (foot != nullptr) {  // the footprint, the grid's geometry and the cell limits, as eea_footprint_check_batch asks them
-    const eea_status fst = footprint_call_refusal(ccfg, with_bodies ? &foot->bodies->fp : foot->fp, tick->d_grid, io->d_pose,
-                                                  tick->d_valid, fargs);
-    if (fst != EEA_OK) return fst;
-  }
-  if (B == 0 && !with_layer && !with_bodies) return EEA_OK;
-  // (the footprint reads the geometry and occupied_threshold only: the radii are neither read nor checked)
-  eea_status st = foot != nullptr ? EEA_OK : collision_cfg_refusal(ccfg);
-  if (st != EEA_OK) return st;
-  const eea::CollisionParams c = foot != nullptr ? grid_params(ccfg) : collision_params(ccfg);
-  if (with_layer) {
-    if (B != layer->v.B) return fail(EEA_ERR_INVALID_ARGUMENT, "the tick's B is not the fleet layer's");
-    if (!eea::same_params(c, layer->c)) {
-      return fail(EEA_ERR_INVALID_ARGUMENT, "the tick's collision configuration is not the fleet layer's");
-    }
-    if (layer->device != e->cfg.device) return fail(EEA_ERR_INVALID_ARGUMENT, "the fleet layer lives on another device than the engine");
-  }
-  if (with_bodies) {
-    const eea_body_layer* const bl = foot->bodies;
-    if (B != bl->v.B) return fail(EEA_ERR_INVALID_ARGUMENT, std::string(entry) + ": the tick's B is not the body layer's");
-    if (!eea::same_params(c, bl->c)) {
-      return fail(EEA_ERR_INVALID_ARGUMENT, std::string(entry) + ": the tick's grid geometry or occupied_threshold is not the body layer's");
-    }
-    if (bl->device != e->cfg.device) {
-      return fail(EEA_ERR_INVALID_ARGUMENT, std::string(entry) + ": the body layer lives on another device than the engine");
-    }
-  }
-  eea::DwaParams d;
-  st = make_dwa_params(dcfg, d);
-  if (st != EEA_OK) return st;
+  return EEA_OK;
+}
+
+// The rest of a tick whose arguments and obstacle model were accepted: the window's refusals, the target, the device, steps 1
+// and 2, and launch_plan(d, tail...) for steps 3 and 4 -- tail: the arguments every planning launcher ends in (common.hpp:
+// from d_x0 to the stream)
+template <typename LaunchPlan>
+static eea_status tick_run(eea_engine* e, unsigned B, const eea_batch_io* io, const eea_tick_io* tick, const eea_dwa_cfg* dcfg,
+                           void* stream, LaunchPlan&& launch_plan)
+{
   // the dynamic window tracks optTraj(): T columns every cfg.dt (before step 1: a refused tick leaves follow_dwa / i alone)
-  st = check_reference_index(d, static_cast<unsigned>(e->T), e->cfg.dt);
+  eea::DwaParams d;
+  eea_status st = dwa_window_refusal(dcfg, nullptr, tick->d_traj, static_cast<unsigned>(e->T), e->cfg.dt, d);
   if (st != EEA_OK) return st;
   if (!e->have_phik) return fail(EEA_ERR_NO_TARGET, "no target set");
   st = use_device(e);
@@ -2412,340 +1849,85 @@ static eea_status tick_batch_impl(eea_engine* e, unsigned B, const eea_batch_io*
   st = control_batch_impl<double>(e, B, &rio, true, s);
   if (st != EEA_OK) return st;
   // 3. validate_control (:238, numerics.hpp:312-330); 4. the dynamic window where the twist was rejected (:240-277), u /
-  // follow_dwa / i updated in place.  One inflated map for both
-  const unsigned val_steps = static_cast<unsigned>(std::abs(tick->val_horizon / tick->val_dt));
-  if (with_bodies) {
-    EEA_HIP(eea::launch_body_validate_and_dwa_fleet(c, d, fargs, foot->bodies->v, tick->d_grid, foot->d_sq,
-                                                    static_cast<const double*>(io->d_pose), tick->d_vb, tick->d_traj,
-                                                    static_cast<unsigned>(e->T), e->cfg.dt, tick->val_dt, val_steps, tick->d_valid,
-                                                    tick->d_follow_dwa, tick->d_dwa_count, tick->d_u, tick->d_source, B, s));
-    return EEA_OK;
-  }
-  if (foot != nullptr) {  // (tick->grid_epoch is not read: no inflated map)
-    EEA_HIP(eea::launch_footprint_validate_and_dwa_fleet(c, d, fargs, tick->d_grid, foot->d_sq, static_cast<const double*>(io->d_pose),
-                                                         tick->d_vb, tick->d_traj, static_cast<unsigned>(e->T), e->cfg.dt,
-                                                         tick->val_dt, val_steps, tick->d_valid, tick->d_follow_dwa,
-                                                         tick->d_dwa_count, tick->d_u, tick->d_source, B, s));
-    return EEA_OK;
-  }
-  if (with_layer) {
-    EEA_HIP(eea::launch_validate_and_dwa_fleet_layer(c, d, layer->v, tick->d_grid, tick->grid_epoch,
-                                                     static_cast<const double*>(io->d_pose), tick->d_vb, tick->d_traj,
-                                                     static_cast<unsigned>(e->T), e->cfg.dt, tick->val_dt, val_steps, tick->d_valid,
-                                                     tick->d_follow_dwa, tick->d_dwa_count, tick->d_u, tick->d_source, B, s));
-    return EEA_OK;
-  }
-  EEA_HIP(eea::launch_validate_and_dwa_fleet(c, d, tick->d_grid, tick->grid_epoch, static_cast<const double*>(io->d_pose),
-                                             tick->d_vb, tick->d_traj, static_cast<unsigned>(e->T), e->cfg.dt, tick->val_dt,
-                                             val_steps, tick->d_valid, tick->d_follow_dwa, tick->d_dwa_count, tick->d_u,
-                                             tick->d_source, B, s));
+  // follow_dwa / i updated in place
+  EEA_HIP(launch_plan(d, static_cast<const double*>(io->d_pose), tick->d_vb, tick->d_traj, static_cast<unsigned>(e->T), e->cfg.dt,
+                      tick->val_dt, horizon_steps(tick->val_horizon, tick->val_dt), tick->d_valid, tick->d_follow_dwa,
+                      tick->d_dwa_count, tick->d_u, tick->d_source, B, s));
   return EEA_OK;
 }
 
 extern "C" {
 
+// the disc on the static map: Collision::Collision's checks, one inflated map for both steps
 eea_status eea_tick_batch(eea_engine* e, unsigned B, const eea_batch_io* io, const eea_tick_io* tick,
                           const eea_collision_cfg* ccfg, const eea_dwa_cfg* dcfg, void* stream)
 {
-  return tick_batch_impl(e, B, io, tick, ccfg, dcfg, nullptr, false, stream);
+  eea_status st = tick_arguments_refusal("eea_tick_batch", e, io, tick, dcfg);
+  if (st != EEA_OK || B == 0) return st;
+  st = collision_cfg_refusal(ccfg);
+  if (st != EEA_OK) return st;
+  const eea::CollisionParams c = collision_params(ccfg);
+  return tick_run(e, B, io, tick, dcfg, stream, [&](const eea::DwaParams& d, auto... tail) {
+    return eea::launch_validate_and_dwa_fleet(c, d, nullptr, tick->d_grid, tick->grid_epoch, tail...);
+  });
 }
 
+// ... and the other robots' discs: the layer is the tick's in B, configuration and device (B == 0 is not a layer's)
 eea_status eea_tick_batch_fleet(eea_engine* e, unsigned B, const eea_batch_io* io, const eea_tick_io* tick,
                                 const eea_collision_cfg* ccfg, const eea_dwa_cfg* dcfg, const eea_fleet_layer* l, void* stream)
 {
-  return tick_batch_impl(e, B, io, tick, ccfg, dcfg, l, true, stream);
+  eea_status st = tick_arguments_refusal("eea_tick_batch_fleet", e, io, tick, dcfg);
+  if (st != EEA_OK) return st;
+  if (l == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null fleet layer");
+  st = collision_cfg_refusal(ccfg);
+  if (st != EEA_OK) return st;
+  const eea::CollisionParams c = collision_params(ccfg);
+  if (B != l->v.B) return fail(EEA_ERR_INVALID_ARGUMENT, "the tick's B is not the fleet layer's");
+  if (!eea::same_params(c, l->c)) return fail(EEA_ERR_INVALID_ARGUMENT, "the tick's collision configuration is not the fleet layer's");
+  if (l->device != e->cfg.device) return fail(EEA_ERR_INVALID_ARGUMENT, "the fleet layer lives on another device than the engine");
+  return tick_run(e, B, io, tick, dcfg, stream, [&](const eea::DwaParams& d, auto... tail) {
+    return eea::launch_validate_and_dwa_fleet(c, d, &l->v, tick->d_grid, tick->grid_epoch, tail...);
+  });
 }
 
+// the polygon base on the static map: the footprint, the grid's geometry and the cell limits, as eea_footprint_check_batch
+// asks them.  The radii are neither read nor checked, and tick->grid_epoch is not read: no inflated map
 eea_status eea_tick_batch_footprint(eea_engine* e, unsigned B, const eea_batch_io* io, const eea_tick_io* tick,
                                     const eea_collision_cfg* ccfg, const eea_dwa_cfg* dcfg, const eea_footprint* fp,
                                     const int* d_sq, void* stream)
 {
-  const FootprintTick foot{ fp, d_sq };
-  return tick_batch_impl(e, B, io, tick, ccfg, dcfg, nullptr, false, stream, &foot);
+  eea_status st = tick_arguments_refusal("eea_tick_batch_footprint", e, io, tick, dcfg);
+  if (st != EEA_OK) return st;
+  eea::FootprintArgs f;
+  st = footprint_call_refusal(ccfg, fp, tick->d_grid, io->d_pose, tick->d_valid, f);
+  if (st != EEA_OK || B == 0) return st;
+  const eea::CollisionParams c = grid_params(ccfg);
+  return tick_run(e, B, io, tick, dcfg, stream, [&](const eea::DwaParams& d, auto... tail) {
+    return eea::launch_footprint_validate_and_dwa_fleet(c, d, f, nullptr, tick->d_grid, d_sq, tail...);
+  });
 }
 
+// ... and the other robots' polygons: the footprint is the layer's, and the layer is the tick's in B, grid and device
 eea_status eea_tick_batch_bodies(eea_engine* e, unsigned B, const eea_batch_io* io, const eea_tick_io* tick,
                                  const eea_collision_cfg* ccfg, const eea_dwa_cfg* dcfg, const eea_body_layer* l, const int* d_sq,
                                  void* stream)
 {
-  const FootprintTick foot{ nullptr, d_sq, true, l };
-  return tick_batch_impl(e, B, io, tick, ccfg, dcfg, nullptr, false, stream, &foot);
-}
-
-// the message of a refusal, with the entry's name in front
-static eea_status named(const char* entry, eea_status st)
-{
-  if (st != EEA_OK) eea::g_last_error = std::string(entry) + ": " + eea::g_last_error;
-  return st;
-}
-
-eea_status eea_body_layer_create(int device, const eea_collision_cfg* cfg, const eea_footprint* fp, unsigned B, unsigned flags,
-                                 eea_body_layer** out)
-{
-  static const char* const entry = "eea_body_layer_create";
-  if (out == nullptr) return named(entry, fail(EEA_ERR_INVALID_ARGUMENT, "null argument"));
-  *out = nullptr;
-  if (cfg == nullptr || fp == nullptr) return named(entry, fail(EEA_ERR_INVALID_ARGUMENT, "null argument"));
-  eea::FootprintArgs f;
-  eea_status st = named(entry, footprint_on_grid_refusal(cfg, fp, f));
+  static const char* const entry = "eea_tick_batch_bodies";
+  eea_status st = tick_arguments_refusal(entry, e, io, tick, dcfg);
   if (st != EEA_OK) return st;
-  if (B == 0) return named(entry, fail(EEA_ERR_INVALID_ARGUMENT, "a body layer needs at least one robot"));
-  if ((flags & ~EEA_BODY_LAYER_NO_FILTER) != 0u) return named(entry, fail(EEA_ERR_INVALID_ARGUMENT, "unknown flag bits"));
-  // near covers the cells [-box, size + box): box <= 1025
-  const unsigned long long nw = static_cast<unsigned long long>(cfg->xsize) + 2ull * static_cast<unsigned>(f.box);
-  const unsigned long long nh = static_cast<unsigned long long>(cfg->ysize) + 2ull * static_cast<unsigned>(f.box);
-  if (nw > 0x7fffffffull || nh > 0x7fffffffull || nw * nh > (1ull << 31) || B > 0x7fffffffu) {
-    return named(entry, fail(EEA_ERR_UNSUPPORTED, "a body layer of more than 2^31 near cells or robots"));
-  }
-  eea_body_layer* l = new (std::nothrow) eea_body_layer();
-  if (l == nullptr) return named(entry, fail(EEA_ERR_HIP, "out of host memory"));
-  l->device = device;
-  l->flags = flags;
-  l->fp = *fp;
-  l->c = grid_params(cfg);
-  l->f = f;
-  l->v.box = f.box;
-  l->v.Rn = 2 * f.box;  // 2 ceil(r_out / res) + 2
-  l->v.near_w = static_cast<int>(nw);
-  l->v.near_h = static_cast<int>(nh);
-  l->v.B = B;
-  l->v.flags = flags;
-  const size_t n_cover = static_cast<size_t>(cfg->xsize) * cfg->ysize, n_maps = n_cover + static_cast<size_t>(nw * nh);
-  hipError_t err = hipSetDevice(device);
-  if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&l->d_block), sizeof(int) * (n_maps + 2 * kBodyGuard));
-  if (err == hipSuccess) l->d_maps = l->d_block + kBodyGuard;
-  if (err == hipSuccess) err = hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(l->d_block), kBodyGuardWord, n_maps + 2 * kBodyGuard);
-  if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&l->d_snap), sizeof(double) * eea::kBodySnap * static_cast<size_t>(B));
-  // before the first update: no robot is an obstacle
-  if (err == hipSuccess) err = hipMemset(l->d_maps, 0, sizeof(int) * n_maps);
-  if (err == hipSuccess) err = hipMemset(l->d_snap, 0, sizeof(double) * eea::kBodySnap * static_cast<size_t>(B));
-  if (err == hipSuccess) err = hipDeviceSynchronize();
-  if (err != hipSuccess) {
-    (void)hipGetLastError();
-    const std::string msg = std::string(entry) + ": " + std::to_string(n_maps) + " map cells: " + hipGetErrorString(err);
-    eea_body_layer_destroy(l);
-    return fail(EEA_ERR_HIP, msg);
-  }
-  l->v.cover = l->d_maps;
-  l->v.near = l->d_maps + n_cover;
-  l->v.snap = l->d_snap;
-  *out = l;
-  return EEA_OK;
-}
-
-void eea_body_layer_destroy(eea_body_layer* l)
-{
-  if (l == nullptr) return;
-  if ((l->d_block != nullptr || l->d_snap != nullptr) && hipSetDevice(l->device) == hipSuccess) {
-    if (l->d_block != nullptr) (void)hipFree(l->d_block);  // waits for its users
-    if (l->d_snap != nullptr) (void)hipFree(l->d_snap);
-  }
-  delete l;
-}
-
-eea_status eea_body_layer_update(eea_body_layer* l, const double* d_pose, const int* d_mask, void* stream)
-{
-  if (l == nullptr || d_pose == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "eea_body_layer_update: null argument");
-  EEA_HIP(hipSetDevice(l->device));
-  EEA_HIP(eea::launch_body_layer_update(l->c, l->f, l->v, l->d_maps, l->d_snap, d_pose, d_mask, static_cast<hipStream_t>(stream)));
-  return EEA_OK;
-}
-
-eea_status eea_body_layer_read(const eea_body_layer* l, int* h_cover, int* h_near, double* h_snapshot)
-{
-  if (l == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "eea_body_layer_read: null argument");
-  EEA_HIP(hipSetDevice(l->device));
-  EEA_HIP(hipDeviceSynchronize());
-  const size_t n_cover = static_cast<size_t>(l->c.xsize) * l->c.ysize, n_near = static_cast<size_t>(l->v.near_w) * l->v.near_h;
-  int guard[2 * kBodyGuard];
-  EEA_HIP(hipMemcpy(guard, l->d_block, sizeof(int) * kBodyGuard, hipMemcpyDeviceToHost));
-  EEA_HIP(hipMemcpy(guard + kBodyGuard, l->d_maps + n_cover + n_near, sizeof(int) * kBodyGuard, hipMemcpyDeviceToHost));
-  for (size_t k = 0; k < 2 * kBodyGuard; ++k) {
-    if (guard[k] != kBodyGuardWord) return fail(EEA_ERR_HIP, "eea_body_layer_read: a guard word beside the maps was overwritten");
-  }
-  if (h_cover != nullptr) EEA_HIP(hipMemcpy(h_cover, l->v.cover, sizeof(int) * n_cover, hipMemcpyDeviceToHost));
-  if (h_near != nullptr) EEA_HIP(hipMemcpy(h_near, l->v.near, sizeof(int) * n_near, hipMemcpyDeviceToHost));
-  if (h_snapshot != nullptr) {
-    EEA_HIP(hipMemcpy(h_snapshot, l->d_snap, sizeof(double) * eea::kBodySnap * static_cast<size_t>(l->v.B), hipMemcpyDeviceToHost));
-  }
-  return EEA_OK;
-}
-
-int eea_body_layer_box(const eea_body_layer* l) { return l != nullptr ? l->v.box : -1; }
-
-eea_status eea_body_collision_check_batch(const eea_body_layer* l, const int8_t* d_grid, const int* d_sq, const double* d_pose,
-                                          const int* d_self, unsigned P, int* d_hit, void* stream)
-{
-  // (the layer last: every other refusal can be reached without one)
-  if (d_pose == nullptr || d_hit == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "eea_body_collision_check_batch: null argument");
-  if (l == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "eea_body_collision_check_batch: null body layer");
-  if (P == 0) return EEA_OK;
-  EEA_HIP(hipSetDevice(l->device));
-  const eea::BodyArgs a{ l->v, d_self, 0 };
-  EEA_HIP(eea::launch_body_check(l->c, l->f, a, d_grid, d_sq, d_pose, P, d_hit, static_cast<hipStream_t>(stream)));
-  return EEA_OK;
-}
-
-eea_status eea_body_validate_control_batch(const eea_body_layer* l, const int8_t* d_grid, const int* d_sq, const double* d_x0,
-                                           const double* d_u, const int* d_self, double dt, double horizon, unsigned P,
-                                           int* d_valid, void* stream)
-{
-  if (d_grid == nullptr || d_x0 == nullptr || d_valid == nullptr || d_u == nullptr) {
-    return fail(EEA_ERR_INVALID_ARGUMENT, "eea_body_validate_control_batch: null argument");
-  }
-  if (l == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "eea_body_validate_control_batch: null body layer");
-  if (P == 0) return EEA_OK;
-  const unsigned steps = static_cast<unsigned>(std::abs(horizon / dt));  // numerics.hpp:317
-  EEA_HIP(hipSetDevice(l->device));
-  const eea::BodyArgs a{ l->v, d_self, 0 };
-  EEA_HIP(eea::launch_body_validate(l->c, l->f, a, d_grid, d_sq, d_x0, d_u, dt, steps, P, d_valid, static_cast<hipStream_t>(stream)));
-  return EEA_OK;
-}
-
-eea_status eea_body_dwa_control_batch(const eea_body_layer* l, const eea_dwa_cfg* dcfg, const int8_t* d_grid, const int* d_sq,
-                                      const double* d_x0, const double* d_vb, const double* d_vref, const double* d_xt_ref,
-                                      unsigned n_ref, double dt_ref, const int* d_self, unsigned P, double* d_u_opt, int* d_found,
-                                      void* stream)
-{
-  static const char* const entry = "eea_body_dwa_control_batch";
-  if (d_grid == nullptr || d_x0 == nullptr || d_u_opt == nullptr || dcfg == nullptr || d_vb == nullptr || d_found == nullptr) {
-    return named(entry, fail(EEA_ERR_INVALID_ARGUMENT, "null argument"));
-  }
-  if ((d_vref == nullptr) == (d_xt_ref == nullptr)) return named(entry, fail(EEA_ERR_INVALID_ARGUMENT, "give either d_vref or d_xt_ref"));
-  if (d_xt_ref != nullptr && n_ref == 0) return named(entry, fail(EEA_ERR_INVALID_ARGUMENT, "empty reference trajectory"));
-  eea::DwaParams d;
-  eea_status st = named(entry, make_dwa_params(dcfg, d));
-  if (st != EEA_OK) return st;
-  if (d_xt_ref != nullptr) {
-    st = named(entry, check_reference_index(d, n_ref, dt_ref));
-    if (st != EEA_OK) return st;
-  }
   if (l == nullptr) return named(entry, fail(EEA_ERR_INVALID_ARGUMENT, "null body layer"));
-  if (P == 0) return EEA_OK;
-  EEA_HIP(hipSetDevice(l->device));
-  const eea::BodyArgs a{ l->v, d_self, 0 };
-  EEA_HIP(eea::launch_body_dwa(l->c, d, l->f, a, d_grid, d_sq, d_x0, d_vb, d_vref, d_xt_ref, n_ref, dt_ref, P, d_u_opt, d_found,
-                               static_cast<hipStream_t>(stream)));
-  return EEA_OK;
-}
-
-eea_status eea_fleet_layer_create(int device, const eea_collision_cfg* cfg, int body_cells, unsigned B, eea_fleet_layer** out)
-{
-  if (out == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
-  *out = nullptr;
-  eea_status st = collision_cfg_refusal(cfg);
+  eea::FootprintArgs f;
+  st = footprint_call_refusal(ccfg, &l->fp, tick->d_grid, io->d_pose, tick->d_valid, f);
   if (st != EEA_OK) return st;
-  if (B == 0) return fail(EEA_ERR_INVALID_ARGUMENT, "a fleet layer needs at least one robot");
-  if (body_cells < 0) return fail(EEA_ERR_INVALID_ARGUMENT, "the body radius of a fleet layer must be >= 0 cells");
-  st = grid_cfg_refusal(cfg);
-  if (st != EEA_OK) return st;
-  const eea::CollisionParams c = collision_params(cfg);
-  if (c.r_bnd < 0 || c.r_col < 0) return fail(EEA_ERR_INVALID_ARGUMENT, "the collision radii must not be negative");
-  // the reach R' = r_col + body (the span table holds shorts; the padded map grows by R' on every side)
-  if (c.r_col > 127 || body_cells > 127 || c.r_col + body_cells > 127) {
-    return fail(EEA_ERR_UNSUPPORTED, "a fleet layer's reach r_col + body above 127 cells");
+  const eea::CollisionParams c = grid_params(ccfg);
+  if (B != l->v.B) return named(entry, fail(EEA_ERR_INVALID_ARGUMENT, "the tick's B is not the body layer's"));
+  if (!eea::same_params(c, l->c)) {
+    return named(entry, fail(EEA_ERR_INVALID_ARGUMENT, "the tick's grid geometry or occupied_threshold is not the body layer's"));
   }
-  const int R = c.r_col + body_cells;
-  const unsigned long long w = static_cast<unsigned long long>(c.xsize) + 2u * R, h = static_cast<unsigned long long>(c.ysize) + 2u * R;
-  if (w > 0x7fffffffull || h > 0x7fffffffull || w * h > (1ull << 31) || B > 0x7fffffffu) {
-    return fail(EEA_ERR_UNSUPPORTED, "a fleet layer of more than 2^31 centres or robots");
-  }
-  eea_fleet_layer* l = new (std::nothrow) eea_fleet_layer();
-  if (l == nullptr) return fail(EEA_ERR_HIP, "fleet layer: out of host memory");
-  l->device = device;
-  l->body = body_cells;
-  l->c = c;
-  l->v.R = R;
-  l->v.w = static_cast<int>(w);
-  l->v.h = static_cast<int>(h);
-  l->v.B = B;
-  hipError_t err = hipSetDevice(device);
-  if (err == hipSuccess) err = eea::acquire_fleet_spans(device, c, body_cells, &l->v.row_start, &l->v.spans, &l->n_spans);
-  if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&l->d_count), sizeof(int) * static_cast<size_t>(w * h));
-  if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&l->d_cell), sizeof(int) * 2 * static_cast<size_t>(B));
-  // before the first update: no robot is an obstacle
-  if (err == hipSuccess) err = hipMemset(l->d_count, 0, sizeof(int) * static_cast<size_t>(w * h));
-  if (err == hipSuccess) err = hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(l->d_cell), eea::kFleetNotStamped, 2 * static_cast<size_t>(B));
-  if (err == hipSuccess) err = hipDeviceSynchronize();  // (the fills are done when the layer is handed out, whatever stream reads it)
-  if (err != hipSuccess) {
-    (void)hipGetLastError();
-    const std::string msg = std::string("fleet layer of ") + std::to_string(w) + " x " + std::to_string(h) + " centres: " + hipGetErrorString(err);
-    eea_fleet_layer_destroy(l);
-    return fail(EEA_ERR_HIP, msg);
-  }
-  l->v.count = l->d_count;
-  l->v.cell = l->d_cell;
-  *out = l;
-  return EEA_OK;
-}
-
-void eea_fleet_layer_destroy(eea_fleet_layer* l)
-{
-  if (l == nullptr) return;
-  if (l->v.row_start != nullptr) eea::release_fleet_spans(l->device, l->v.row_start);
-  if ((l->d_count != nullptr || l->d_cell != nullptr) && hipSetDevice(l->device) == hipSuccess) {
-    if (l->d_count != nullptr) (void)hipFree(l->d_count);  // waits for its users
-    if (l->d_cell != nullptr) (void)hipFree(l->d_cell);
-  }
-  delete l;
-}
-
-int eea_fleet_layer_reach(const eea_fleet_layer* l) { return l != nullptr ? l->v.R : -1; }
-
-eea_status eea_fleet_layer_update(eea_fleet_layer* l, const double* d_pose, const int* d_mask, void* stream)
-{
-  if (l == nullptr || d_pose == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
-  EEA_HIP(hipSetDevice(l->device));
-  EEA_HIP(eea::launch_fleet_layer_update(l->c, l->v, l->n_spans, l->d_count, l->d_cell, d_pose, d_mask, static_cast<hipStream_t>(stream)));
-  return EEA_OK;
-}
-
-eea_status eea_fleet_layer_read(const eea_fleet_layer* l, int* h_count, int* h_cell)
-{
-  if (l == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
-  EEA_HIP(hipSetDevice(l->device));
-  EEA_HIP(hipDeviceSynchronize());
-  if (h_count != nullptr) EEA_HIP(hipMemcpy(h_count, l->d_count, sizeof(int) * static_cast<size_t>(l->v.w) * l->v.h, hipMemcpyDeviceToHost));
-  if (h_cell != nullptr) EEA_HIP(hipMemcpy(h_cell, l->d_cell, sizeof(int) * 2 * static_cast<size_t>(l->v.B), hipMemcpyDeviceToHost));
-  return EEA_OK;
-}
-
-eea_status eea_fleet_collision_check_batch(const eea_fleet_layer* l, const int8_t* d_grid, const double* d_pose, const int* d_self,
-                                           unsigned P, int* d_hit, void* stream)
-{
-  if (l == nullptr || d_pose == nullptr || d_hit == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
-  EEA_HIP(hipSetDevice(l->device));
-  EEA_HIP(eea::launch_fleet_collision_check(l->c, l->v, d_grid, d_pose, d_self, P, d_hit, static_cast<hipStream_t>(stream)));
-  return EEA_OK;
-}
-
-eea_status eea_dwa_control_batch(int device, const eea_collision_cfg* ccfg, const eea_dwa_cfg* dcfg,
-                                 const int8_t* d_grid, const double* d_x0, const double* d_vb,
-                                 const double* d_vref, const double* d_xt_ref, unsigned n_ref,
-                                 double dt_ref, unsigned P, double* d_u_opt, int* d_found, void* stream)
-{
-  eea_status st = collision_cfg_refusal(ccfg);
-  if (st != EEA_OK) return st;
-  const eea::CollisionParams c = collision_params(ccfg);
-  if (dcfg == nullptr || d_grid == nullptr || d_x0 == nullptr || d_vb == nullptr || d_u_opt == nullptr ||
-      d_found == nullptr) {
-    return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
-  }
-  if ((d_vref == nullptr) == (d_xt_ref == nullptr)) {
-    return fail(EEA_ERR_INVALID_ARGUMENT, "give either d_vref or d_xt_ref");
-  }
-  if (d_xt_ref != nullptr && n_ref == 0) return fail(EEA_ERR_INVALID_ARGUMENT, "empty reference trajectory");
-  eea::DwaParams d;
-  st = make_dwa_params(dcfg, d);
-  if (st != EEA_OK) return st;
-  if (d_xt_ref != nullptr) {
-    st = check_reference_index(d, n_ref, dt_ref);
-    if (st != EEA_OK) return st;
-  }
-  EEA_HIP(hipSetDevice(device));
-  EEA_HIP(eea::launch_dwa_control(c, d, d_grid, d_x0, d_vb, d_vref, d_xt_ref, n_ref, dt_ref, P, d_u_opt,
-                                  d_found, static_cast<hipStream_t>(stream)));
-  return EEA_OK;
+  if (l->device != e->cfg.device) return named(entry, fail(EEA_ERR_INVALID_ARGUMENT, "the body layer lives on another device than the engine"));
+  return tick_run(e, B, io, tick, dcfg, stream, [&](const eea::DwaParams& d, auto... tail) {
+    return eea::launch_footprint_validate_and_dwa_fleet(c, d, f, &l->v, tick->d_grid, d_sq, tail...);
+  });
 }
 
 }  // extern "C"

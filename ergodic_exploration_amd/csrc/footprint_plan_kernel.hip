@@ -498,93 +498,73 @@ struct PlanGeometry
   }
   bool fits() const { return sizeof(double) * nsamp <= kLdsLimit; }  // a larger sample window is refused
 };
+
+// One launch in the instance the call takes: launch(NoBodies{}) without a layer, launch(the BodyArgs) with one -- the view is
+// the kernel's last argument and its type the kernel's last template argument.  The launch error is taken here, behind it.
+template <typename Launch>
+hipError_t with_or_without_bodies(const BodyArgs* bodies, Launch launch)
+{
+  if (bodies != nullptr) launch(*bodies);
+  else launch(NoBodies{});
+  return hipGetLastError();
+}
+// ... and what PlanGeometry keeps behind the window by the same choice
+size_t flag_bytes(const void* bodies) { return bodies != nullptr ? kBodyFlagBytes : 0; }
+
+// footprint_dwa_kernel in the launch geometry g; ft: the tick's bookkeeping (FLEET), PlanTick{} otherwise
+template <bool FLEET>
+hipError_t launch_plan_dwa(const PlanGeometry& g, const CollisionParams& c, const DwaParams& d, const FootprintArgs& f,
+                           const BodyArgs* bodies, const int8_t* d_grid, const int* d_sq, const double* d_x0, const double* d_vb,
+                           const double* d_vref, const double* d_xt_ref, unsigned n_ref, double dt_ref, unsigned P, double* d_u_opt,
+                           int* d_found, const PlanTick& ft, hipStream_t s)
+{
+  return with_or_without_bodies(bodies, [&](const auto& view) {
+    hipLaunchKernelGGL((footprint_dwa_kernel<FLEET, std::decay_t<decltype(view)>>), dim3(P), dim3(g.block), g.lds, s, c, d, f, d_grid,
+                       d_sq, d_x0, d_vb, d_vref, d_xt_ref, n_ref, dt_ref, d_u_opt, d_found, ft, g.win_reach, view);
+  });
+}
 }  // namespace
 
-hipError_t launch_footprint_validate(const CollisionParams& c, const FootprintArgs& f, const int8_t* d_grid, const int* d_sq,
-                                     const double* d_x0, const double* d_u, double dt, unsigned steps, unsigned P, int* d_valid,
-                                     hipStream_t s)
+hipError_t launch_footprint_validate(const CollisionParams& c, const FootprintArgs& f, const BodyArgs* bodies, const int8_t* d_grid,
+                                     const int* d_sq, const double* d_x0, const double* d_u, double dt, unsigned steps, unsigned P,
+                                     int* d_valid, hipStream_t s)
 {
   if (P == 0) return hipSuccess;
   const dim3 blocks(static_cast<unsigned>((static_cast<size_t>(P) + kBlock - 1) / kBlock));
-  hipLaunchKernelGGL(footprint_validate_kernel<NoBodies>, blocks, dim3(kBlock), 0, s, c, f, d_grid, d_sq, d_x0, d_u, dt, steps, P,
-                     d_valid, NoBodies{});
-  return hipGetLastError();
+  return with_or_without_bodies(bodies, [&](const auto& view) {
+    hipLaunchKernelGGL(footprint_validate_kernel<std::decay_t<decltype(view)>>, blocks, dim3(kBlock), 0, s, c, f, d_grid, d_sq, d_x0,
+                       d_u, dt, steps, P, d_valid, view);
+  });
 }
 
-hipError_t launch_body_validate(const CollisionParams& c, const FootprintArgs& f, const BodyArgs& a, const int8_t* d_grid,
-                                const int* d_sq, const double* d_x0, const double* d_u, double dt, unsigned steps, unsigned P,
-                                int* d_valid, hipStream_t s)
-{
-  if (P == 0) return hipSuccess;
-  const dim3 blocks(static_cast<unsigned>((static_cast<size_t>(P) + kBlock - 1) / kBlock));
-  hipLaunchKernelGGL(footprint_validate_kernel<BodyArgs>, blocks, dim3(kBlock), 0, s, c, f, d_grid, d_sq, d_x0, d_u, dt, steps, P,
-                     d_valid, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_footprint_dwa(const CollisionParams& c, const DwaParams& d, const FootprintArgs& f, const int8_t* d_grid,
-                                const int* d_sq, const double* d_x0, const double* d_vb, const double* d_vref,
+hipError_t launch_footprint_dwa(const CollisionParams& c, const DwaParams& d, const FootprintArgs& f, const BodyArgs* bodies,
+                                const int8_t* d_grid, const int* d_sq, const double* d_x0, const double* d_vb, const double* d_vref,
                                 const double* d_xt_ref, unsigned n_ref, double dt_ref, unsigned P, double* d_u_opt, int* d_found,
                                 hipStream_t s)
 {
   if (P == 0) return hipSuccess;
-  const PlanGeometry g(c, d, f);
+  const PlanGeometry g(c, d, f, flag_bytes(bodies));
   if (!g.fits()) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((footprint_dwa_kernel<false, NoBodies>), dim3(P), dim3(g.block), g.lds, s, c, d, f, d_grid, d_sq, d_x0, d_vb,
-                     d_vref, d_xt_ref, n_ref, dt_ref, d_u_opt, d_found, PlanTick{}, g.win_reach, NoBodies{});
-  return hipGetLastError();
-}
-
-hipError_t launch_body_dwa(const CollisionParams& c, const DwaParams& d, const FootprintArgs& f, const BodyArgs& a,
-                           const int8_t* d_grid, const int* d_sq, const double* d_x0, const double* d_vb, const double* d_vref,
-                           const double* d_xt_ref, unsigned n_ref, double dt_ref, unsigned P, double* d_u_opt, int* d_found,
-                           hipStream_t s)
-{
-  if (P == 0) return hipSuccess;
-  const PlanGeometry g(c, d, f, kBodyFlagBytes);
-  if (!g.fits()) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((footprint_dwa_kernel<false, BodyArgs>), dim3(P), dim3(g.block), g.lds, s, c, d, f, d_grid, d_sq, d_x0, d_vb,
-                     d_vref, d_xt_ref, n_ref, dt_ref, d_u_opt, d_found, PlanTick{}, g.win_reach, a);
-  return hipGetLastError();
+  return launch_plan_dwa<false>(g, c, d, f, bodies, d_grid, d_sq, d_x0, d_vb, d_vref, d_xt_ref, n_ref, dt_ref, P, d_u_opt, d_found,
+                                PlanTick{}, s);
 }
 
 // steps 3 and 4 of a fleet tick with the footprint: validate_control of every robot's twist, then the dynamic window of the
-// robots whose twist was rejected
+// robots whose twist was rejected.  With a layer, robot r of the tick is robot r of the layer
 hipError_t launch_footprint_validate_and_dwa_fleet(const CollisionParams& c, const DwaParams& d, const FootprintArgs& f,
-                                                   const int8_t* d_grid, const int* d_sq, const double* d_x0, const double* d_vb,
-                                                   const double* d_traj, unsigned n_ref, double dt_ref, double val_dt,
-                                                   unsigned val_steps, int* d_valid, int* d_follow, unsigned* d_count, double* d_u,
-                                                   int* d_source, unsigned P, hipStream_t s)
+                                                   const BodyView* bodies, const int8_t* d_grid, const int* d_sq, const double* d_x0,
+                                                   const double* d_vb, const double* d_traj, unsigned n_ref, double dt_ref,
+                                                   double val_dt, unsigned val_steps, int* d_valid, int* d_follow, unsigned* d_count,
+                                                   double* d_u, int* d_source, unsigned P, hipStream_t s)
 {
   if (P == 0) return hipSuccess;
-  const PlanGeometry g(c, d, f);
+  const PlanGeometry g(c, d, f, flag_bytes(bodies));
   if (!g.fits()) return hipErrorInvalidValue;
-  const hipError_t e = launch_footprint_validate(c, f, d_grid, d_sq, d_x0, d_u, val_dt, val_steps, P, d_valid, s);
+  const BodyArgs own{ bodies != nullptr ? *bodies : BodyView{}, nullptr, 1 };
+  const BodyArgs* const a = bodies != nullptr ? &own : nullptr;
+  const hipError_t e = launch_footprint_validate(c, f, a, d_grid, d_sq, d_x0, d_u, val_dt, val_steps, P, d_valid, s);
   if (e != hipSuccess) return e;
-  const PlanTick ft{ d_valid, d_follow, d_count, d_u, d_source };
-  hipLaunchKernelGGL((footprint_dwa_kernel<true, NoBodies>), dim3(P), dim3(g.block), g.lds, s, c, d, f, d_grid, d_sq, d_x0, d_vb,
-                     static_cast<const double*>(nullptr), d_traj, n_ref, dt_ref, static_cast<double*>(nullptr),
-                     static_cast<int*>(nullptr), ft, g.win_reach, NoBodies{});
-  return hipGetLastError();
-}
-
-// ... with the layer: robot r of the tick is robot r of the layer
-hipError_t launch_body_validate_and_dwa_fleet(const CollisionParams& c, const DwaParams& d, const FootprintArgs& f, const BodyView& v,
-                                              const int8_t* d_grid, const int* d_sq, const double* d_x0, const double* d_vb,
-                                              const double* d_traj, unsigned n_ref, double dt_ref, double val_dt,
-                                              unsigned val_steps, int* d_valid, int* d_follow, unsigned* d_count, double* d_u,
-                                              int* d_source, unsigned P, hipStream_t s)
-{
-  if (P == 0) return hipSuccess;
-  const PlanGeometry g(c, d, f, kBodyFlagBytes);
-  if (!g.fits()) return hipErrorInvalidValue;
-  const BodyArgs a{ v, nullptr, 1 };
-  const hipError_t e = launch_body_validate(c, f, a, d_grid, d_sq, d_x0, d_u, val_dt, val_steps, P, d_valid, s);
-  if (e != hipSuccess) return e;
-  const PlanTick ft{ d_valid, d_follow, d_count, d_u, d_source };
-  hipLaunchKernelGGL((footprint_dwa_kernel<true, BodyArgs>), dim3(P), dim3(g.block), g.lds, s, c, d, f, d_grid, d_sq, d_x0, d_vb,
-                     static_cast<const double*>(nullptr), d_traj, n_ref, dt_ref, static_cast<double*>(nullptr),
-                     static_cast<int*>(nullptr), ft, g.win_reach, a);
-  return hipGetLastError();
+  return launch_plan_dwa<true>(g, c, d, f, a, d_grid, d_sq, d_x0, d_vb, nullptr, d_traj, n_ref, dt_ref, P, nullptr, nullptr,
+                               PlanTick{ d_valid, d_follow, d_count, d_u, d_source }, s);
 }
 }  // namespace eea

@@ -107,7 +107,7 @@ void checks()
 {
   views_of_one_walk();
   for (const Set& s : kSets) {
-    // the radii in cells as csrc/engine.cpp derives them (collision.cpp:130-133)
+    // the radii in cells as csrc/entry_util.hpp derives them (collision.cpp:130-133)
     one_set(static_cast<int>(std::floor(s.boundary / s.resolution)), static_cast<int>(std::floor((s.boundary + s.obstacle) / s.resolution)),
             static_cast<int>(std::floor(s.search / s.resolution)), s.n_off);
   }

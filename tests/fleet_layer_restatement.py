@@ -13,7 +13,7 @@ COLL_S = (0.2, 0.4, 0.1, 0.8)     # small robots: boundary 0.2 m, search 0.4 m, 
 
 
 def radii(coll, res):
-    """(r_bnd, r_col, r_max) in cells, the library's formula (csrc/engine.cpp collision_params, collision.cpp:130-133)"""
+    """(r_bnd, r_col, r_max) in cells, the library's formula (csrc/entry_util.hpp collision_params, collision.cpp:130-133)"""
     return (int(math.floor(coll[0] / res)), int(math.floor((coll[0] + coll[2]) / res)), int(math.floor(coll[1] / res)))
 
 

@@ -176,6 +176,152 @@ def test_tick_argument_errors():
     e32.close()
 
 
+TICK_ENTRIES = ["eea_tick_batch", "eea_tick_batch_fleet", "eea_tick_batch_footprint", "eea_tick_batch_bodies"]
+
+
+@pytest.mark.parametrize("entry", TICK_ENTRIES)
+def test_tick_refusals_in_order(entry):
+    """Every refusal of the four tick entries, in the order a caller meets them, with its whole message; the rows marked "+"
+    have a second fault that a later refusal would name.  After every refused call follow_dwa, dwa_count, valid, skip and u hold
+    their sentinels.  B == 0 is EEA_OK and writes nothing for the two entries without a layer, and is not the layer's B for the
+    other two.  No call reaches a kernel but the good tick at the end, which shows that the arguments were otherwise valid."""
+    import ctypes as C
+    from tests import footprint_restatement as fr
+    L = capi.lib()
+    B = 8
+    lim = np.array([1.0, 1.0, 2.0])
+
+    def engine(precision=capi.PREC_F64, domain=True):
+        e = capi.Engine(capi.make_config(capi.MODEL_OMNI, 0.1, 5.0, 0.1, 1.0, 10, np.diag([1.0, 1.0, 2.0]), -lim, lim, precision=precision))
+        e.set_target_gaussians([[2.5, 2.5], [8.5, 2.5]], [[1.5, 1.5], [1.5, 1.5]])
+        if domain:
+            e.config_domain((-1.0, 11.0, -1.0, 5.0))
+        return e
+
+    eng, e32, no_target = engine(), engine(capi.PREC_F32), engine(domain=False)
+    T = eng.T
+    cfg = lambda res=0.05, xs=240, ys=120, coll=COLL: capi.make_collision_cfg(-1.0, -1.0, res, xs, ys, *coll)
+    dwa = lambda **kw: capi.DwaCfg(*[kw.get(n, v) for (n, _), v in zip(capi.DwaCfg._fields_, DWA["omni"])])
+    good, omni, rect = cfg(), dwa(), capi.Footprint.of(fr.FOOTPRINTS["rect"])
+    wide, long_ = dwa(vx_samples=17, vy_samples=17, vth_samples=29), dwa(horizon=6.0)    # 8381 samples; 60 steps past T = 50
+    fleet, bodies = capi.FleetLayer(good, 14, B), capi.BodyLayer(good, rect, B)
+    with_layer = entry in ("eea_tick_batch_fleet", "eea_tick_batch_bodies")
+    polygon = entry in ("eea_tick_batch_footprint", "eea_tick_batch_bodies")
+    fill = lambda v: torch.full((B,), v, dtype=torch.int32, device="cuda")
+    f64 = lambda *shape: torch.full(shape, 7.0, dtype=torch.float64, device="cuda")
+    buf = dict(pose=torch.tensor([[3.0, 2.0, 0.5]] * B, dtype=torch.float64, device="cuda"),
+               ut=torch.zeros((B, T, 3), dtype=torch.float64, device="cuda"), follow=fill(1), count=fill(3), u=f64(B, 3), vb=f64(B, 3),
+               grid=torch.zeros((120, 240), dtype=torch.int8, device="cuda"), traj=f64(B, T, 3), valid=fill(-1), skip=fill(-1))
+    flag = torch.zeros(4, dtype=torch.int32, device="cuda")
+    layers = {}
+    if with_layer and torch.cuda.device_count() > 1:
+        layers["elsewhere"] = capi.FleetLayer(good, 14, B, device=1) if entry == "eea_tick_batch_fleet" else capi.BodyLayer(good, rect, B, device=1)
+    sentinels = dict(follow=1, count=3, valid=-1, skip=-1, u=7.0)
+    ref = lambda s: None if s is None else C.byref(s)
+
+    def tick(e=eng, n=B, io=True, tick=True, ccfg=good, dcfg=omni, layer=True, fp=rect, missing=None, ready=None, ck_flag=None):
+        b = dict(buf, **{missing: None}) if missing else buf
+        bio, tio = capi.Engine._tick_io(b["pose"], b["ut"], b["follow"], b["count"], b["u"], b["vb"], b["grid"], b["traj"], b["valid"],
+                                        b["skip"], 0.1, 0.5, None, None, None, 0, None, 0)
+        bio.d_rec_ready, bio.d_ck_flag = capi._ptr(ready), capi._ptr(ck_flag)
+        head = (e.h, n, ref(bio) if io else None, ref(tio) if tick else None, ref(ccfg), ref(dcfg))
+        if with_layer:
+            own = fleet if entry == "eea_tick_batch_fleet" else bodies
+            handle = None if layer is None else (own if layer is True else layers[layer]).h
+        if entry == "eea_tick_batch":
+            return L.eea_tick_batch(*head, None)
+        if entry == "eea_tick_batch_fleet":
+            return L.eea_tick_batch_fleet(*head, handle, None)
+        if entry == "eea_tick_batch_footprint":
+            return L.eea_tick_batch_footprint(*head, ref(fp), None, None)
+        return L.eea_tick_batch_bodies(*head, handle, None, None)
+
+    INV, UNS, NO_TARGET = capi.ERR_INVALID_ARGUMENT, capi.ERR_UNSUPPORTED, capi.ERR_NO_TARGET
+    F32 = entry + " takes fp64 engines (poses and twists are doubles)"
+    EXCHANGE = entry + " does not take the device-bound exchange buffers"
+    NO_LAYER = {"eea_tick_batch_fleet": "null fleet layer", "eea_tick_batch_bodies": "eea_tick_batch_bodies: null body layer"}.get(entry)
+    OTHER_B = {"eea_tick_batch_fleet": "the tick's B is not the fleet layer's",
+               "eea_tick_batch_bodies": "eea_tick_batch_bodies: the tick's B is not the body layer's"}.get(entry)
+    OTHER_CFG = {"eea_tick_batch_fleet": "the tick's collision configuration is not the fleet layer's",
+                 "eea_tick_batch_bodies": "eea_tick_batch_bodies: the tick's grid geometry or occupied_threshold is not the body layer's"}.get(entry)
+    ELSEWHERE = {"eea_tick_batch_fleet": "the fleet layer lives on another device than the engine",
+                 "eea_tick_batch_bodies": "eea_tick_batch_bodies: the body layer lives on another device than the engine"}.get(entry)
+    RADII = "Search radius must be at least the same size as the boundary radius"
+    THRESHOLD = "Occupied threshold must be between 0 and 100"
+    RESOLUTION = "the grid's resolution must be positive"
+    SAMPLES = "more than 8192 DWA samples"
+    # 60 steps of 0.1 s along optTraj's 50 columns every 0.1 s: t = 5.1 s asks for column round(49 * 5.1 / 5.0) = 50
+    PAST = "the DWA rollout runs past the reference trajectory (step 51 reads column 50.000000 of 50)"
+    swapped, over = cfg(coll=(1.0, 0.7, 0.2, 0.8)), cfg(coll=(0.7, 1.0, 0.2, 101.0))
+    # what the layer compares: the disc's radii too, the polygon's geometry and threshold only
+    other = cfg(ys=119) if polygon else cfg(coll=(0.3, 2.0, 0.1, 0.8))
+    r_out = float(np.hypot(0.45, 0.25))
+
+    rows = [("no io", dict(io=False), INV, "null argument"), ("no tick", dict(tick=False), INV, "null argument"),
+            ("no window", dict(dcfg=None), INV, "null argument"), ("+ no io, an fp32 engine", dict(io=False, e=e32), INV, "null argument"),
+            ("an fp32 engine", dict(e=e32), UNS, F32), ("+ an fp32 engine, no grid", dict(e=e32, missing="grid"), UNS, F32)]
+    rows += [("no " + m, dict(missing=m), INV, "null tick buffer") for m in ("pose", "ut", "follow", "count", "u", "vb", "grid", "traj", "valid", "skip")]
+    rows += [("+ no skip, d_rec_ready", dict(missing="skip", ready=flag), INV, "null tick buffer"),
+             ("d_rec_ready", dict(ready=flag), UNS, EXCHANGE), ("d_ck_flag", dict(ck_flag=flag), UNS, EXCHANGE)]
+    if with_layer:
+        rows += [("+ d_ck_flag, no layer", dict(ck_flag=flag, layer=None), UNS, EXCHANGE), ("no layer", dict(layer=None), INV, NO_LAYER),
+                 ("+ no layer, no configuration", dict(layer=None, ccfg=None), INV, NO_LAYER)]
+    if polygon:
+        rows += [("no configuration", dict(ccfg=None), INV, "null argument"), ("no cells", dict(ccfg=cfg(xs=0)), INV, "the grid's xsize and ysize must be positive"),
+                 ("+ no cells, resolution 0", dict(ccfg=cfg(xs=0, res=0.0)), INV, "the grid's xsize and ysize must be positive"),
+                 ("resolution 0", dict(ccfg=cfg(res=0.0)), INV, RESOLUTION), ("+ resolution 0, no robot", dict(ccfg=cfg(res=0.0), n=0), INV, RESOLUTION),
+                 ("2^31 + 65536 cells", dict(ccfg=cfg(xs=1 << 16, ys=(1 << 15) + 1)), UNS, "xsize * ysize above 2^31"),
+                 ("1024.5 cells of radius", dict(ccfg=cfg(res=r_out / 1024.5)), UNS, "the footprint's circumscribed radius is above 1024 cells"),
+                 ("+ 1024.5 cells of radius, 8381 samples", dict(ccfg=cfg(res=r_out / 1024.5), dcfg=wide), UNS,
+                  "the footprint's circumscribed radius is above 1024 cells")]
+    if entry == "eea_tick_batch_footprint":
+        rows += [("no footprint", dict(fp=None), INV, "null argument"), ("+ no footprint, no cells", dict(fp=None, ccfg=cfg(xs=0)), INV, "null argument"),
+                 ("two vertices", dict(fp=capi.Footprint.of(fr.FOOTPRINTS["rect"][:2])), INV, "a footprint has 3 to 16 vertices"),
+                 ("clockwise", dict(fp=capi.Footprint.of(fr.FOOTPRINTS["rect"][::-1])), INV, "the footprint must be strictly convex and counter-clockwise"),
+                 ("+ clockwise, resolution 0", dict(fp=capi.Footprint.of(fr.FOOTPRINTS["rect"][::-1]), ccfg=cfg(res=0.0)), INV,
+                  "the footprint must be strictly convex and counter-clockwise")]
+    if not with_layer:   # B == 0 comes before the radii, the window and the target are looked at
+        rows += [("no robot", dict(n=0), 0, None), ("no robot, 8381 samples", dict(n=0, dcfg=wide), 0, None),
+                 ("no robot, no target", dict(n=0, e=no_target), 0, None)]
+    if entry == "eea_tick_batch":
+        rows += [("no robot, no configuration", dict(n=0, ccfg=None), 0, None)]
+    if not polygon:
+        rows += [("no configuration", dict(ccfg=None), INV, "null collision config"), ("swapped radii", dict(ccfg=swapped), INV, RADII),
+                 ("+ swapped radii, threshold 101", dict(ccfg=cfg(coll=(1.0, 0.7, 0.2, 101.0))), INV, RADII),
+                 ("threshold 101", dict(ccfg=over), INV, THRESHOLD), ("+ threshold 101, 8381 samples", dict(ccfg=over, dcfg=wide), INV, THRESHOLD)]
+    if entry == "eea_tick_batch_fleet":
+        rows += [("+ threshold 101, no robot", dict(ccfg=over, n=0), INV, THRESHOLD)]
+    if with_layer:
+        rows += [("no robot", dict(n=0), INV, OTHER_B), ("one robot less", dict(n=B - 1), INV, OTHER_B),
+                 ("+ one robot less, another configuration", dict(n=B - 1, ccfg=other), INV, OTHER_B),
+                 ("another configuration", dict(ccfg=other), INV, OTHER_CFG), ("+ another configuration, 8381 samples", dict(ccfg=other, dcfg=wide), INV, OTHER_CFG)]
+        if entry == "eea_tick_batch_bodies":
+            rows += [("another origin", dict(ccfg=capi.make_collision_cfg(-1.0, -1.05, 0.05, 240, 120, *COLL)), INV, OTHER_CFG),
+                     ("another threshold", dict(ccfg=cfg(coll=(0.7, 1.0, 0.2, 0.5))), INV, OTHER_CFG)]
+        if layers:
+            rows += [("a layer of another device", dict(layer="elsewhere"), INV, ELSEWHERE),
+                     ("+ a layer of another device, 8381 samples", dict(layer="elsewhere", dcfg=wide), INV, ELSEWHERE)]
+    rows += [("8381 samples", dict(dcfg=wide), UNS, SAMPLES), ("+ 8381 samples, 60 steps", dict(dcfg=dwa(horizon=6.0, vx_samples=17, vy_samples=17, vth_samples=29)), UNS, SAMPLES),
+             ("60 steps", dict(dcfg=long_), INV, PAST), ("+ 60 steps, no target", dict(dcfg=long_, e=no_target), INV, PAST),
+             ("no target", dict(e=no_target), NO_TARGET, "no target set")]
+
+    for what, kw, status, text in rows:
+        got = tick(**kw)
+        assert got == status, (what, got, L.eea_last_error())
+        assert text is None or L.eea_last_error() == text.encode(), (what, L.eea_last_error())
+        torch.cuda.synchronize()
+        for name, v in sentinels.items():
+            assert bool((buf[name] == v).all()), (what, name)
+    # the tick itself (the polygon ticks read neither the radii nor the threshold's range)
+    assert tick(ccfg=cfg(coll=(1.0, 0.7, 0.2, 0.8)) if polygon else good) == 0, L.eea_last_error()
+    torch.cuda.synchronize()
+    assert bool(((buf["valid"] == 0) | (buf["valid"] == 1)).all()) and bool((buf["skip"] != -1).all())
+    for layer in [fleet, bodies] + list(layers.values()):
+        layer.close()
+    for e in (eng, e32, no_target):
+        e.close()
+
+
 def test_tick_is_refused_when_the_dynamic_window_outruns_opt_traj():
     """Step 4 tracks optTraj(): T columns every dt.  An engine horizon of 1.0 (T = 10) under the cart's DWA horizon of 2.0
     would read column 17 of 10 -- the next robot's trajectory, memory behind the buffer for the last robot -- where the

@@ -1,6 +1,6 @@
 """What every entry that takes an eea_collision_cfg answers to a malformed one BEFORE it selects a device: the status, the
 text of eea_last_error and -- by the configurations with two faults -- which refusal comes first.  No GPU: every buffer is a
-host array that nothing may touch.  The entries compose the same few checks (csrc/engine.cpp: cfg_given, cfg_radii_ordered,
+host array that nothing may touch.  The entries compose the same few checks (csrc/entry_util.hpp: cfg_given, cfg_radii_ordered,
 cfg_threshold_in_range, cfg_has_cells, cfg_has_resolution) in different orders; the table below pins each order as it is.
 A configuration an entry does not refuse before the device has no row for that entry."""
 import ctypes as C

@@ -39,7 +39,7 @@ def test_map_table_policy(program):
 @pytest.mark.parametrize("coll", [COLL, COLL2])
 def test_ring_offsets_are_the_oracles_dilation(program, coll):
     """One occupied cell in the middle of a 41 x 41 grid at 0.1 m: the oracle's collisionCheck at the centre of every cell
-    is "(occupied cell - this cell) is one of ring_offsets" (the radii in cells as csrc/engine.cpp derives them)"""
+    is "(occupied cell - this cell) is one of ring_offsets" (the radii in cells as csrc/entry_util.hpp derives them)"""
     r_bnd, r_col, r_max = (math.floor(coll[0] / RES), math.floor((coll[0] + coll[2]) / RES), math.floor(coll[1] / RES))
     out = subprocess.run([program, str(r_bnd), str(r_col), str(r_max)], capture_output=True, text=True, timeout=60)
     assert out.returncode == 0, (out.stdout, out.stderr)
