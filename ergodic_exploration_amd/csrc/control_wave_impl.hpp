@@ -119,6 +119,24 @@ __device__ __forceinline__ double fma_k<double>(double v, int k, double acc)
   return d;
 }
 
+// min(max(u, lo), hi) with wavefront-uniform limits: fp64 takes them from scalar register pairs.  Left to the compiler every
+// limit is first quieted into a vector register pair (v_max_f64 v, s, s: fmax / fmin canonicalise their operands) -- six more
+// instructions per clamped control; v_max_f64 / v_min_f64 quiet their own inputs, and the value is the same for every finite,
+// infinite and quiet-NaN limit (a NaN limit is ignored, a NaN u becomes lo: as fmin(fmax(u, lo), hi))
+template <typename R>
+__device__ __forceinline__ R clamp_uniform(R u, R lo, R hi)
+{
+  return fmin(fmax(u, lo), hi);
+}
+template <>
+__device__ __forceinline__ double clamp_uniform<double>(double u, double lo, double hi)
+{
+  double a, d;
+  asm("v_max_f64 %0, %1, %2" : "=v"(a) : "v"(u), "s"(lo));
+  asm("v_min_f64 %0, %1, %2" : "=v"(d) : "v"(a), "s"(hi));
+  return d;
+}
+
 // v_permlane32_swap (gfx950): from_lower = v of lane l - 32 in the upper 32 lanes, from_upper = v of lane l + 32 in the
 // lower 32 lanes (probed: the builtin returns { [a.lower, b.lower], [a.upper, b.upper] })
 __device__ __forceinline__ void half_swap(double v, double& from_lower, double& from_upper)
@@ -980,10 +998,55 @@ __global__ __launch_bounds__(WPB* kWave, waves_per_simd(KC, sizeof(R))) void con
     // Rollout points, software-pipelined as below: the operands of a pass (12 reads) are read first, then the tile is
     // free and the recurrence + stores of the NEXT pass are issued between the matrix instructions of the first
     // 16-row group (pinned with scheduling barriers); the second group is skipped when it holds no valid point.
+    // fp64, K = 5 / 10 (kTrim): the entry of a staging half-pass without its selects, copies and index arithmetic.
+    //  * ONE exchange per slot serves both tiles: v_permlane32_swap with (cos a, cos b) as its two operands leaves
+    //    [cos a of lanes 0..31 | cos b of lanes 0..31] in the first -- the lower tile's cosines as stage_cos hands them
+    //    out -- and [cos a of lanes 32..63 | cos b of lanes 32..63] in the second: the upper tile's, with the lower lanes on
+    //    the x rows and the upper lanes on the y rows.  Both tiles are then staged through st_lower: the same values in
+    //    the same LDS words as through st_upper with the lane halves' roles exchanged, and no select on the lane half.
+    //  * the row's validity is one compare: the step counts of the two lanes whose points this lane stages are formed
+    //    once per step (opaque, so that the compare is not folded back into the arithmetic of cnt_of per half-pass).
+    //    cnt_of <= S: `j + 1 < cnt_lo` implies j + 1 < S.
+    constexpr bool kTrim = sizeof(R) == 8 && (KC == 10 || KC == 5);
+    int cnt_lo = cnt_of(row), cnt_hi = cnt_of(row + 32);
+    if constexpr (kTrim) asm volatile("" : "+v"(cnt_lo), "+v"(cnt_hi));
+    R* const st_second = kTrim ? st_lower : st_upper;  // where the tile of lanes 32..63 is staged from
+    //  * a half whose 32 rows are all valid (wavefront-uniform: the last lane of the half owns the step) starts its
+    //    recurrence from (1, c) as they are -- no select; only a partly valid half forms the zero rows
+    const int cnt_31 = cnt_of(31), cnt_63 = cnt_of(63);
+    auto tab1_init_half = [&](R c, bool valid, bool full) {
+      if constexpr (kTrim) {
+        Tab1 t;
+        t.two = c + c;
+        if (full) {  // wavefront-uniform
+          t.a = R(1);
+          t.b = c;
+        } else {
+          asm volatile("; partly valid half");  // (keeps the branch: folded into selects it is what it replaces)
+          t.a = valid ? R(1) : R(0);
+          t.b = valid ? c : R(0);
+        }
+        return t;
+      } else {
+        return tab1_init(c, valid);
+      }
+    };
+    auto stage_cos_slot = [&](R ca, R cb, R& c_lower, R& c_upper) {
+      if constexpr (kTrim) {
+        const unsigned al = static_cast<unsigned>(__double2loint(ca)), ah = static_cast<unsigned>(__double2hiint(ca));
+        const unsigned bl = static_cast<unsigned>(__double2loint(cb)), bh = static_cast<unsigned>(__double2hiint(cb));
+        const auto rl = __builtin_amdgcn_permlane32_swap(al, bl, false, false);
+        const auto rh = __builtin_amdgcn_permlane32_swap(ah, bh, false, false);
+        c_lower = __hiloint2double(static_cast<int>(rh[0]), static_cast<int>(rl[0]));
+        c_upper = __hiloint2double(static_cast<int>(rh[1]), static_cast<int>(rl[1]));
+      } else {
+        stage_cos(ca, cb, c_lower, c_upper);
+      }
+    };
     R cl, cu;
-    stage_cos(c1x[0], c1y[0], cl, cu);
+    stage_cos_slot(c1x[0], c1y[0], cl, cu);
     {
-      Tab1 u = tab1_init(cl, 0 < cnt_of(row));
+      Tab1 u = tab1_init_half(cl, 0 < cnt_lo, 0 < cnt_31);
 #pragma unroll
       for (int q = 0; q < kPairs; ++q) {
         tab1_store(u, st_lower, 2 * q);
@@ -1024,9 +1087,9 @@ __global__ __launch_bounds__(WPB* kWave, waves_per_simd(KC, sizeof(R))) void con
         read_operands4();  // rows of lanes 0..31, step j
         lds_fence();       // operands in registers: the tile is free
         {
-          Tab1 u = tab1_init(cu, j < cnt_of(row + 32));
+          Tab1 u = tab1_init_half(cu, j < cnt_hi, j < cnt_63);
           operands4_ready();
-          mma4_group_staging(0, u, st_upper, nl > 32);  // (no point in lanes 32..63: no upper half-pass, below, and no tile for it)
+          mma4_group_staging(0, u, st_second, nl > 32);  // (no point in lanes 32..63: no upper half-pass, below, and no tile for it)
           if (nl > 16) mma4_group(1);
         }
         // A last slot with no point in lanes 32..63 (wavefront-uniform: slot 3 of T = 193 .. 200) has no upper half-pass:
@@ -1038,8 +1101,8 @@ __global__ __launch_bounds__(WPB* kWave, waves_per_simd(KC, sizeof(R))) void con
         lds_fence();
         {
           const int jn = (j + 1 < kMaxS) ? j + 1 : j;
-          stage_cos(c1x[jn], c1y[jn], cl, cu);
-          Tab1 u = tab1_init(cl, (j + 1 < S) && (j + 1 < cnt_of(row)));
+          stage_cos_slot(c1x[jn], c1y[jn], cl, cu);
+          Tab1 u = tab1_init_half(cl, (kTrim || j + 1 < S) && (j + 1 < cnt_lo), j + 1 < cnt_31);
           operands4_ready();
           if (nl > 32) {
             mma4_group_staging(0, u, st_lower);
@@ -1734,6 +1797,22 @@ __global__ __launch_bounds__(WPB* kWave, waves_per_simd(KC, sizeof(R))) void con
         vyr[j] = ok ? bq : R(0);
       }
     }
+    // fp64, K = 5 / 10, INSTEAD of the loop above (whose loads are then dead; it keeps its text for the other instances: wrapped
+    // into the else of this test it compiled to another schedule in three fp32 instances): the lane's successors are
+    // consecutive -- ONE address, the slots at immediate offsets, and the loads under the lane mask of the steps that have a
+    // successor inside the horizon instead of index and value selects
+    if constexpr (sizeof(R) == 8 && (KC == 10 || KC == 5)) {
+      const R* const ut_next = ut_again + 3 * static_cast<ptrdiff_t>(i0 + 1);
+      const int n_next = min(cnt, T - 1 - i0);
+#pragma unroll
+      for (int j = 0; j < kMaxS; ++j) {
+        vxr[j] = vyr[j] = R(0);
+        if (j < n_next) {
+          vxr[j] = ut_next[3 * j];
+          if (MODEL == kModelOmni) vyr[j] = ut_next[3 * j + 1];
+        }
+      }
+    }
   }
   R r0[kMaxS], r1[kMaxS];  // inclusive suffix within the lane, then the co-state after step j
   R tot0, tot1, tot2;      // the wavefront totals of the three co-state scans (wavefront-uniform)
@@ -1779,8 +1858,15 @@ __global__ __launch_bounds__(WPB* kWave, waves_per_simd(KC, sizeof(R))) void con
         a12 = vxr[j] * cth[j];
       }
       // rho_{i+1} = rho_i - dt g_i (rows 0,1)
-      const R sE = a02 * (r0[j] - dt * g0[j]) + a12 * (r1[j] - dt * g1[j]);
-      const R sG = a02 * g0[j] + a12 * g1[j];
+      // (two-product sites, pinned like those of the forward half: the a12 product is rounded, the a02 product fused)
+      R sE, sG;
+      if constexpr (sizeof(R) == 8) {
+        sE = mul_add(a02, r0[j] - dt * g0[j], a12, r1[j] - dt * g1[j]);
+        sG = mul_add(a02, g0[j], a12, g1[j]);
+      } else {
+        sE = a02 * (r0[j] - dt * g0[j]) + a12 * (r1[j] - dt * g1[j]);
+        sG = a02 * g0[j] + a12 * g1[j];
+      }
       // zero controls beyond the horizon give a02 = a12 = 0 there; slots beyond S never parked a heading (garbage)
       const R qv = (j < S) ? dt * (sE + p.half_dt * sG) : R(0);
       s2 += qv;
@@ -1806,34 +1892,49 @@ __global__ __launch_bounds__(WPB* kWave, waves_per_simd(KC, sizeof(R))) void con
   const bool nan_free = __all((fabs(tot0) < inf_r) && (fabs(tot1) < inf_r) && (fabs(tot2) < inf_r));
   auto update_controls = [&](auto fast_tag) {
   constexpr bool kFast = decltype(fast_tag)::value;
+  // the lane's steps are consecutive: ONE address for ut and one for the hand-over, the slots at immediate offsets
+  // (fp64, K = 5 / 10, like the scalar-limit clamp below: the other instances keep their text, and with it their registers
+  // and the compiler's choices)
+  constexpr bool kLaneBase = sizeof(R) == 8 && (KC == 10 || KC == 5);
+  R* const ut_lane = kLaneBase ? ut + 3 * static_cast<ptrdiff_t>(i0) : ut;
+  R* const sm_lane = kLaneBase ? sm + i0 : sm;
+  // SimpleCart's -v1 = -0.0, in a register pair once per step (the product with Rinv stays: Rinv may be anything)
+  R neg_zero = R(-0.0);
+  if (kLaneBase && MODEL == kModelSimpleCart) asm volatile("" : "+v"(neg_zero));
 #pragma unroll
   for (int j = 0; j < kMaxS; ++j) {
     if (j < cnt) {
       const int i = i0 + j;
       R v0, v1, v2;
       if (MODEL == kModelOmni) {  // omni.hpp:205-212
-        v0 = cth[j] * r0[j] + sth[j] * r1[j];
+        if constexpr (sizeof(R) == 8) v0 = mul_add(cth[j], r0[j], sth[j], r1[j]);  // (pinned: sth r1 is rounded)
+        else v0 = cth[j] * r0[j] + sth[j] * r1[j];
         v1 = -sth[j] * r0[j] + cth[j] * r1[j];
         v2 = r2[j];
       } else {  // cart.hpp:194-203: B^T rho has an exact zero in row 1
-        v0 = cth[j] * r0[j] + sth[j] * r1[j];
+        if constexpr (sizeof(R) == 8) v0 = mul_add(cth[j], r0[j], sth[j], r1[j]);
+        else v0 = cth[j] * r0[j] + sth[j] * r1[j];
         v1 = R(0);
         v2 = r2[j];
       }
-      const R n0 = -v0, n1 = -v1, n2 = -v2;
+      const R n0 = -v0, n1 = (kLaneBase && MODEL == kModelSimpleCart) ? neg_zero : -v1, n2 = -v2;
       R u[3];
 #pragma unroll
       for (int r = 0; r < 3; ++r) {
-        const R ur = (p.Rinv[r] * n0 + p.Rinv[r + 3] * n1) + p.Rinv[r + 6] * n2;
-        u[r] = kFast ? fmin(fmax(ur, p.umin[r]), p.umax[r]) : clamp_std(ur, p.umin[r], p.umax[r]);
+        R ur;  // (fp64, pinned: Rinv[r] n0 is rounded, the other two products are fused)
+        if constexpr (sizeof(R) == 8) ur = __builtin_fma(p.Rinv[r + 6], n2, __builtin_fma(p.Rinv[r + 3], n1, p.Rinv[r] * n0));
+        else ur = (p.Rinv[r] * n0 + p.Rinv[r + 3] * n1) + p.Rinv[r + 6] * n2;
+        if constexpr (kLaneBase) u[r] = kFast ? clamp_uniform<R>(ur, p.umin[r], p.umax[r]) : clamp_std(ur, p.umin[r], p.umax[r]);
+        else u[r] = kFast ? fmin(fmax(ur, p.umin[r]), p.umax[r]) : clamp_std(ur, p.umin[r], p.umax[r]);
       }
-      ut[3 * i + 0] = u[0];
-      ut[3 * i + 1] = u[1];
-      ut[3 * i + 2] = u[2];
+      const int e = kLaneBase ? j : i;  // element of the lane's run / of the horizon
+      ut_lane[3 * e + 0] = u[0];
+      ut_lane[3 * e + 1] = u[1];
+      ut_lane[3 * e + 2] = u[2];
       if (step + 1 < n_steps) {  // wavefront-uniform: hand-over to the next step
-        sm[0 * kMaxS * kWave + i] = u[0];
-        sm[1 * kMaxS * kWave + i] = u[1];
-        sm[2 * kMaxS * kWave + i] = u[2];
+        sm_lane[0 * kMaxS * kWave + e] = u[0];
+        sm_lane[1 * kMaxS * kWave + e] = u[1];
+        sm_lane[2 * kMaxS * kWave + e] = u[2];
       }
       if (STAGES && p.rhot != nullptr) {
         R* const o = p.rhot + 3 * (static_cast<size_t>(T) * b + i);
@@ -1841,7 +1942,7 @@ __global__ __launch_bounds__(WPB* kWave, waves_per_simd(KC, sizeof(R))) void con
         o[1] = r1[j];
         o[2] = r2[j];
       }
-      if (i == 0) {
+      if (kLaneBase ? (j == 0 && i0 == 0) : (i == 0)) {  // step 0 of the horizon
         R* const o = p.u0 + 3 * (static_cast<size_t>(step) * p.u0_step_stride + b);
         o[0] = u[0];
         o[1] = u[1];
