@@ -276,6 +276,11 @@ def lib():
         L.eea_sense_gain_field.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
         L.eea_set_target_gain.argtypes = [C.c_void_p, C.POINTER(CollisionCfg), C.c_uint, C.c_uint, C.c_void_p, C.c_double,
                                           C.c_double, C.c_double, C.c_void_p, C.c_void_p]
+        L.eea_sense_mi_table.argtypes = [C.POINTER(CollisionCfg), C.c_double, C.c_void_p, C.c_void_p]
+        L.eea_sense_mi_field.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_uint, C.c_uint, C.c_double, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]
+        L.eea_set_target_mi.argtypes = [C.c_void_p, C.POINTER(CollisionCfg), C.c_uint, C.c_uint, C.c_double, C.c_void_p, C.c_double,
+                                        C.c_double, C.c_double, C.c_void_p, C.c_void_p]
         if hasattr(L, "eea_body_layer_create"):   # additive to ABI 6 as well
             L.eea_body_layer_create.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.POINTER(Footprint), C.c_uint, C.c_uint,
                                                 C.POINTER(C.c_void_p)]
@@ -395,6 +400,13 @@ class Engine:
         the integer field"""
         check(lib().eea_set_target_gain(self.h, C.byref(cfg), int(range_cells), int(stride), _ptr(known), float(floor), lx, ly,
                                         _ptr(gain), C.c_void_p(stream or 0)))
+
+    def set_target_mi(self, cfg, range_cells, stride, known, lx, ly, p_unknown=0.5, floor=0.0, mi=None, stream=None):
+        """eea_set_target_mi: the mutual-information field of the int8 device grid `known` (eea_sense_mi_field) + floor on the
+        candidates -> phi_k, all on `stream` without a host wait; mi (optional, device double [ysize][xsize]) receives the
+        field"""
+        check(lib().eea_set_target_mi(self.h, C.byref(cfg), int(range_cells), int(stride), float(p_unknown), _ptr(known),
+                                      float(floor), lx, ly, _ptr(mi), C.c_void_p(stream or 0)))
 
     def spatial_coeff_occupancy_rows(self, nx, ny_total, row0, nrows, occ_rows, lx, ly, out_sums, stream=None):
         """un-normalised coefficient sums of the occupancy rows [row0, row0+nrows) (device int8 tensor)"""
@@ -819,6 +831,23 @@ def sense_gain_field(cfg, range_cells, stride, known, gain, device=0, stream=Non
     through the int8 device grid `known`, counted per beam, + 1 for an unknown own cell; 0 elsewhere; asynchronous"""
     check(lib().eea_sense_gain_field(device, C.byref(cfg), int(range_cells), int(stride), _ptr(known), _ptr(gain),
                                      C.c_void_p(stream or 0)))
+
+
+def sense_mi_table(cfg, p_unknown):
+    """eea_sense_mi_table: (h, pass), two float64 arrays of 256: entry v + 128 holds h(v) / pass(v) of the int8 cell value v at
+    cfg's occupied_threshold and the probability p_unknown of an unknown cell -- the doubles the field entries use.  Host only"""
+    import numpy as np
+    h, pass_ = np.empty(256, dtype=np.float64), np.empty(256, dtype=np.float64)
+    check(lib().eea_sense_mi_table(C.byref(cfg), float(p_unknown), h.ctypes.data_as(C.c_void_p), pass_.ctypes.data_as(C.c_void_p)))
+    return h, pass_
+
+
+def sense_mi_field(cfg, range_cells, stride, known, mi, p_unknown=0.5, device=0, stream=None):
+    """eea_sense_mi_field: mi (device double [ysize][xsize], every element overwritten) = per candidate cell (both indices
+    multiples of stride, the cell not blocking) the Shannon mutual information between the map and the sensor's
+    8 * range_cells ideal beams cast from there through the int8 device grid `known`; +0.0 elsewhere; asynchronous"""
+    check(lib().eea_sense_mi_field(device, C.byref(cfg), int(range_cells), int(stride), float(p_unknown), _ptr(known), _ptr(mi),
+                                   C.c_void_p(stream or 0)))
 
 
 def stream_wait_flag(flag, seq, timeouts=None, stream=None):

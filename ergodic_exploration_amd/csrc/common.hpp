@@ -475,6 +475,19 @@ template <typename R>
 hipError_t launch_gain_values(const CollisionParams& c, unsigned stride, const int8_t* d_known, const unsigned* d_gain, double floor,
                               R* d_values, hipStream_t s);
 
+// ---- mutual-information field of a known grid (mi_kernel.hip) -----------------------------
+// h256 / pass256 [256], entry v + 128: h(v) and pass(v) of eea_sense_mi_table; host only, the one place a log is evaluated
+void mi_table256(double occupied_threshold, double p_unknown, double* h256, double* pass256);
+// d_mi [ysize][xsize] = per candidate cell (both indices multiples of stride, the cell not blocking) h(own) + the sum over the
+// sensor's 8 * range_cells rays of sum_s reach_s h(v_s), reach_s = prod_{l < s} pass(v_l); +0.0 elsewhere.  The table of the
+// launch is mi_table256's, carried as a kernel argument
+hipError_t launch_mi_field(const CollisionParams& c, unsigned range_cells, unsigned stride, double p_unknown, const int8_t* d_known,
+                           double* d_mi, hipStream_t s);
+// d_values [ysize][xsize] = (R)(mi + floor) on the candidates whose cell does not block, 0 elsewhere
+template <typename R>
+hipError_t launch_mi_values(const CollisionParams& c, unsigned stride, const int8_t* d_known, const double* d_mi, double floor,
+                            R* d_values, hipStream_t s);
+
 // ======================================================================================
 // device helpers
 // ======================================================================================

@@ -151,7 +151,8 @@ struct eea_engine
   hipStream_t rebuild_stream = nullptr;
   bool rebuild_pending = false;
   DevBuf d_lut, d_raw, d_occ;  // occupancy targets: decode table, un-normalised sums, staged cells
-  DevBuf d_gain, d_gain_val;   // eea_set_target_gain: the integer field (when the caller passes no buffer), its value grid
+  // eea_set_target_gain / eea_set_target_mi: the field (uint32 / double; when the caller passes no buffer), its value grid
+  DevBuf d_gain, d_gain_val;
 
   // eea_records_field's OWN tables, apart from the phi_k path's: a field on another grid never evicts tab / d_work and adds no
   // wait to a rebuild
@@ -1747,42 +1748,45 @@ eea_status eea_target_fill(int device, unsigned n_gauss, const double* mu, const
   return EEA_OK;
 }
 
-eea_status eea_set_target_gain(eea_engine* e, const eea_collision_cfg* cfg, unsigned range_cells, unsigned stride,
-                               const int8_t* d_known, double floor, double lx, double ly, unsigned* d_gain, void* stream)
+}  // extern "C"
+
+// What eea_set_target_gain and eea_set_target_mi share behind the checks of their field's arguments: the refusals of the target
+// (floor, domain, 2^31 cells), the engine's workspaces and bookkeeping, and field -> value grid -> the launches of
+// eea_spatial_coeff_rows (whole grid) and eea_set_phik_from_sums: the same bits.  field_and_values(real, field, d_values, s)
+// enqueues the field into `field` -- d_field, or the engine's workspace when that is null -- and its value grid into d_values.
+template <typename Cell, typename FieldAndValues>
+static eea_status target_from_field(eea_engine* e, const eea::CollisionParams& c, const char* what, double floor, double lx,
+                                    double ly, Cell* d_field, void* stream, FieldAndValues field_and_values)
 {
-  if (e == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null engine");
-  if (cfg == nullptr || d_known == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
-  eea_status st = gain_refusal(cfg, range_cells, stride);
-  if (st != EEA_OK) return st;
-  const eea::CollisionParams c = grid_params(cfg);
   if (!(floor >= 0.0) || !std::isfinite(floor)) return fail(EEA_ERR_INVALID_ARGUMENT, "floor must be finite and >= 0");
-  if (!(lx > 0.0 && ly > 0.0)) return fail(EEA_ERR_INVALID_ARGUMENT, "bad gain target domain");
+  if (!(lx > 0.0 && ly > 0.0)) return fail(EEA_ERR_INVALID_ARGUMENT, std::string("bad ") + what + " target domain");
   const size_t P = static_cast<size_t>(c.xsize) * c.ysize;
-  if (P > (static_cast<size_t>(1) << 31)) return fail(EEA_ERR_UNSUPPORTED, "a gain target of more than 2^31 cells");
-  st = enter_target(e, nullptr);
+  if (P > (static_cast<size_t>(1) << 31)) {
+    return fail(EEA_ERR_UNSUPPORTED, std::string("a ") + what + " target of more than 2^31 cells");
+  }
+  eea_status st = enter_target(e, nullptr);
   if (st != EEA_OK) return st;
   hipStream_t s = static_cast<hipStream_t>(stream);
   // the engine's workspaces: a first call, or a growing one, waits for the device before it replaces them
-  const size_t need_gain = d_gain != nullptr ? 0 : sizeof(unsigned) * P, need_val = e->rs * P, need_raw = e->rs * e->K2;
-  if (need_gain > e->d_gain.cap || need_val > e->d_gain_val.cap || need_raw > e->d_raw.cap) {
+  const size_t need_field = d_field != nullptr ? 0 : sizeof(Cell) * P, need_val = e->rs * P, need_raw = e->rs * e->K2;
+  if (need_field > e->d_gain.cap || need_val > e->d_gain_val.cap || need_raw > e->d_raw.cap) {
     EEA_HIP(hipDeviceSynchronize());
-    EEA_HIP(e->d_gain.reserve(need_gain));
+    EEA_HIP(e->d_gain.reserve(need_field));
     EEA_HIP(e->d_gain_val.reserve(need_val));
     EEA_HIP(e->d_raw.reserve(need_raw));
   }
-  unsigned* const gain = d_gain != nullptr ? d_gain : static_cast<unsigned*>(e->d_gain.p);
+  Cell* const field = d_field != nullptr ? d_field : static_cast<Cell*>(e->d_gain.p);
   e->nx = c.xsize;
   e->ny = c.ysize;
   e->have_fill_grid = false;
-  // gain -> value grid -> the launches of eea_spatial_coeff_rows (whole grid) and eea_set_phik_from_sums: the same bits
   st = by_precision(e, [&](auto r) {
     using R = decltype(r);
     eea_status st2 = upload_axes_and_tables<R>(e, c.xsize, c.ysize, lx, ly, s);
     if (st2 != EEA_OK) return st2;
     st2 = reserve_tile_work<R>(e, c.xsize, c.ysize, c.ysize);
     if (st2 != EEA_OK) return st2;
-    EEA_HIP(eea::launch_gain_field(c, range_cells, stride, d_known, gain, s));
-    EEA_HIP(eea::launch_gain_values<R>(c, stride, d_known, gain, floor, as<R>(e->d_gain_val.p), s));
+    st2 = field_and_values(r, field, e->d_gain_val.p, s);
+    if (st2 != EEA_OK) return st2;
     EEA_HIP(eea::launch_spatial_coeff<R>(as<R>(e->d_gain_val.p), c.xsize, c.ysize, e->K, as<R>(e->tab.cx.p), as<R>(e->tab.cy.p),
                                          as<R>(e->d_work.p), as<R>(e->d_raw.p), s));
     EEA_HIP(eea::launch_normalise_by_first<R>(as<R>(e->d_raw.p), e->K2, as<R>(e->d_phik.p), s));
@@ -1791,6 +1795,42 @@ eea_status eea_set_target_gain(eea_engine* e, const eea_collision_cfg* cfg, unsi
   if (st != EEA_OK) return st;
   commit_phik(e, lx, ly);
   return EEA_OK;
+}
+
+extern "C" {
+
+eea_status eea_set_target_gain(eea_engine* e, const eea_collision_cfg* cfg, unsigned range_cells, unsigned stride,
+                               const int8_t* d_known, double floor, double lx, double ly, unsigned* d_gain, void* stream)
+{
+  if (e == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null engine");
+  if (cfg == nullptr || d_known == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  const eea_status st = gain_refusal(cfg, range_cells, stride);
+  if (st != EEA_OK) return st;
+  const eea::CollisionParams c = grid_params(cfg);
+  return target_from_field(e, c, "gain", floor, lx, ly, d_gain, stream, [&](auto r, unsigned* gain, void* d_values, hipStream_t s) {
+    using R = decltype(r);
+    EEA_HIP(eea::launch_gain_field(c, range_cells, stride, d_known, gain, s));
+    EEA_HIP(eea::launch_gain_values<R>(c, stride, d_known, gain, floor, as<R>(d_values), s));
+    return EEA_OK;
+  });
+}
+
+eea_status eea_set_target_mi(eea_engine* e, const eea_collision_cfg* cfg, unsigned range_cells, unsigned stride, double p_unknown,
+                             const int8_t* d_known, double floor, double lx, double ly, double* d_mi, void* stream)
+{
+  if (e == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null engine");
+  if (cfg == nullptr || d_known == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  eea_status st = gain_refusal(cfg, range_cells, stride);
+  if (st == EEA_OK) st = eea::p_unknown_refusal(p_unknown);
+  if (st != EEA_OK) return st;
+  const eea::CollisionParams c = grid_params(cfg);
+  return target_from_field(e, c, "mutual-information", floor, lx, ly, d_mi, stream,
+                           [&](auto r, double* mi, void* d_values, hipStream_t s) {
+                             using R = decltype(r);
+                             EEA_HIP(eea::launch_mi_field(c, range_cells, stride, p_unknown, d_known, mi, s));
+                             EEA_HIP(eea::launch_mi_values<R>(c, stride, d_known, mi, floor, as<R>(d_values), s));
+                             return EEA_OK;
+                           });
 }
 
 }  // extern "C"

@@ -257,6 +257,13 @@ inline eea_status gain_refusal(const eea_collision_cfg* cfg, unsigned range_cell
   return EEA_OK;
 }
 
+// what the mutual-information entries ask of the probability of an unknown cell: inside (0, 1)
+inline eea_status p_unknown_refusal(double p_unknown)
+{
+  if (p_unknown > 0.0 && p_unknown < 1.0) return EEA_OK;  // (NaN and the infinities fail both)
+  return fail(EEA_ERR_INVALID_ARGUMENT, "p_unknown must lie inside (0, 1)");
+}
+
 // the message of a refusal, with the entry's name in front
 inline eea_status named(const char* entry, eea_status st)
 {

@@ -3,8 +3,8 @@
 // (sense_rays.hpp: the reveal's rays, steps, disc and blocking rule) would cross when cast from there through `known` itself,
 // counted per beam, plus one if the cell itself is unknown.  Integers only, no atomics, every element of d_gain written once.
 //
-//  - a workgroup of 256 threads owns a tile of 32 x 8 candidates, A LANE IS A CANDIDATE: the ray geometry (q, s, dx, dy and
-//    the remainder recurrence) does not depend on the lane and stays in scalar registers; per step a lane reads one cell at its
+//  - a workgroup of 256 threads owns a tile of 32 x 8 candidates (the tiling is gain_tile.hpp's, shared with mi_kernel.hip),
+//    A LANE IS A CANDIDATE: the ray geometry (q, s, dx, dy and the remainder recurrence) does not depend on the lane and stays in scalar registers; per step a lane reads one cell at its
 //    own base plus a uniform offset, adds `alive & unknown` and clears `alive` on a cell that ends the ray.  A ray ends for the
 //    wavefront where it leaves the disc or no lane is alive.  No cross-lane reduction.
 //  - LDS form: the union of the tile's windows, (31 stride + 1 + 2R) x (7 stride + 1 + 2R) cells, is staged as one byte per
@@ -20,67 +20,17 @@
 #include <cstdint>
 
 #include "common.hpp"
+#include "gain_tile.hpp"
 #include "sense_rays.hpp"
 
 namespace eea
 {
 namespace
 {
-constexpr int kGainBlock = 256, kGainTX = 32, kGainTY = 8;  // a 32-lane LDS group is one row of 32 candidates
-constexpr unsigned kGainMaxBlocks = 1u << 16;                // workgroups per launch; they stride over the tiles past that
-constexpr size_t kGainLdsMax = 64u * 1024u;
-constexpr int kGainChunk = 4;  // steps of a ray whose cells are read before the first is used
-static_assert(kGainTX * kGainTY == kGainBlock, "a lane per candidate");
-
-struct GainParams
+struct GainParams : CandidateGrid
 {
-  CollisionParams c;  // the geometry (the radii are not read)
-  int R;
-  int cutoff;  // a cell blocks a ray iff cell >= cutoff (128: no cell does)
-  unsigned stride;
-  const int8_t* known;
   unsigned* gain;
-  unsigned ncx, ncy;  // candidate columns and rows: ceil(xsize / stride), ceil(ysize / stride)
-  unsigned tiles_x;
-  unsigned long long tiles;
-  int W, H;  // the LDS window (LDS form)
 };
-
-struct Tile
-{
-  unsigned long long cx0, cy0;  // first candidate column / row
-  bool in;                      // this lane's candidate exists
-  unsigned i0, j0;              // ... its cell
-};
-__device__ __forceinline__ Tile tile_of(const GainParams& p, unsigned long long t)
-{
-  Tile k;
-  k.cx0 = (t % p.tiles_x) * kGainTX;
-  k.cy0 = (t / p.tiles_x) * kGainTY;
-  const unsigned long long cx = k.cx0 + (threadIdx.x % kGainTX), cy = k.cy0 + (threadIdx.x / kGainTX);
-  k.in = cx < p.ncx && cy < p.ncy;
-  k.j0 = k.in ? static_cast<unsigned>(cx * p.stride) : 0u;
-  k.i0 = k.in ? static_cast<unsigned>(cy * p.stride) : 0u;
-  return k;
-}
-
-// zeroes the cells of the tile's footprint that are no candidates; the candidates are stored by their lanes
-__device__ __forceinline__ void zero_off_lattice(const GainParams& p, const Tile& k)
-{
-  if (p.stride == 1u) return;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long x0 = k.cx0 * p.stride, y0 = k.cy0 * p.stride;  // (on the grid: the tile has a candidate)
-  unsigned long long w = static_cast<unsigned long long>(kGainTX) * p.stride, h = static_cast<unsigned long long>(kGainTY) * p.stride;
-  if (w > p.c.xsize - x0) w = p.c.xsize - x0;
-  if (h > p.c.ysize - y0) h = p.c.ysize - y0;
-  for (unsigned long long ry = wave; ry < h; ry += kGainBlock / 64) {
-    const bool lattice_row = static_cast<unsigned>(ry) % p.stride == 0u;
-    unsigned* const row = p.gain + (y0 + ry) * p.c.xsize + x0;
-    for (unsigned long long rx = lane; rx < w; rx += 64) {
-      if (!(lattice_row && static_cast<unsigned>(rx) % p.stride == 0u)) row[rx] = 0u;
-    }
-  }
-}
 
 __global__ __launch_bounds__(kGainBlock) void gain_field_lds_kernel(const GainParams p)
 {
@@ -107,7 +57,7 @@ __global__ __launch_bounds__(kGainBlock) void gain_field_lds_kernel(const GainPa
         srow[wx] = b;
       }
     }
-    zero_off_lattice(p, k);
+    zero_off_lattice(p, k, p.gain);
     __syncthreads();
     const unsigned own = s_win[base];  // (inside the window for every lane, candidate or not)
     const bool cand = k.in && (own & 5u) == 0u;  // a robot cannot stand in a blocking cell
@@ -147,7 +97,7 @@ __global__ __launch_bounds__(kGainBlock) void gain_field_global_kernel(const Gai
   const int R = p.R;
   for (unsigned long long t = blockIdx.x; t < p.tiles; t += gridDim.x) {
     const Tile k = tile_of(p, t);
-    zero_off_lattice(p, k);
+    zero_off_lattice(p, k, p.gain);
     if (!k.in) continue;
     const size_t g0 = static_cast<size_t>(k.i0) * p.c.xsize + k.j0;
     const int own = p.known[g0];
@@ -183,37 +133,16 @@ __global__ __launch_bounds__(kGainBlock) void gain_values_kernel(const int8_t* _
   }
 }
 
-// whether the tile's window fits the LDS a launch may ask for (*bytes: its size); otherwise the march runs in global memory
-bool window_fits_lds(unsigned range_cells, unsigned stride, size_t* bytes)
-{
-  const unsigned long long W = static_cast<unsigned long long>(kGainTX - 1) * stride + 1u + 2ull * range_cells;
-  const unsigned long long H = static_cast<unsigned long long>(kGainTY - 1) * stride + 1u + 2ull * range_cells;
-  if (stride > kGainLdsMax || W * H > kGainLdsMax) return false;
-  *bytes = static_cast<size_t>(W * H);
-  return true;
-}
 }  // namespace
 
 hipError_t launch_gain_field(const CollisionParams& c, unsigned range_cells, unsigned stride, const int8_t* d_known, unsigned* d_gain,
                              hipStream_t s)
 {
   GainParams p;
-  p.c = c;
-  p.R = static_cast<int>(range_cells);
-  p.cutoff = blocking_cutoff(c.occupied_threshold);
-  p.stride = stride;
-  p.known = d_known;
-  p.gain = d_gain;
-  p.ncx = (c.xsize - 1u) / stride + 1u;
-  p.ncy = (c.ysize - 1u) / stride + 1u;
-  p.tiles_x = (p.ncx - 1u) / kGainTX + 1u;
-  p.tiles = static_cast<unsigned long long>(p.tiles_x) * ((p.ncy - 1u) / kGainTY + 1u);
-  p.W = p.H = 0;
-  const unsigned blocks = p.tiles < kGainMaxBlocks ? static_cast<unsigned>(p.tiles) : kGainMaxBlocks;
   size_t lds = 0;
-  if (window_fits_lds(range_cells, stride, &lds)) {
-    p.W = (kGainTX - 1) * static_cast<int>(stride) + 1 + 2 * p.R;
-    p.H = (kGainTY - 1) * static_cast<int>(stride) + 1 + 2 * p.R;
+  const unsigned blocks = candidate_grid(c, range_cells, stride, d_known, 0, p, &lds);
+  p.gain = d_gain;
+  if (lds != 0) {
     hipLaunchKernelGGL(gain_field_lds_kernel, dim3(blocks), dim3(kGainBlock), lds, s, p);
   } else {
     hipLaunchKernelGGL(gain_field_global_kernel, dim3(blocks), dim3(kGainBlock), 0, s, p);

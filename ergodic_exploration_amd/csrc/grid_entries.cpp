@@ -1,5 +1,5 @@
 // C ABI (include/ergodic_amd.h) of the entries that take a device or a layer and no engine: collision, clearance and distance
-// queries, the footprint and its planning entries, the range sensor, the census, the gain field, and the two layers with their
+// queries, the footprint and its planning entries, the range sensor, the census, the gain and mutual-information fields, and the two layers with their
 // batch entries.  Argument checking (entry_util.hpp) and kernel dispatch; every refusal comes before the device is selected.
 #include "../../include/ergodic_amd.h"
 
@@ -285,6 +285,29 @@ eea_status eea_sense_gain_field(int device, const eea_collision_cfg* cfg, unsign
   const eea::CollisionParams c = grid_params(cfg);
   EEA_HIP(hipSetDevice(device));
   EEA_HIP(eea::launch_gain_field(c, range_cells, stride, d_known, d_gain, static_cast<hipStream_t>(stream)));
+  return EEA_OK;
+}
+
+// ---- mutual-information target ----------------------------------------------------------------
+eea_status eea_sense_mi_table(const eea_collision_cfg* cfg, double p_unknown, double* h256, double* pass256)
+{
+  if (cfg == nullptr || h256 == nullptr || pass256 == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  const eea_status st = eea::p_unknown_refusal(p_unknown);
+  if (st != EEA_OK) return st;
+  eea::mi_table256(cfg->occupied_threshold, p_unknown, h256, pass256);
+  return EEA_OK;
+}
+
+eea_status eea_sense_mi_field(int device, const eea_collision_cfg* cfg, unsigned range_cells, unsigned stride, double p_unknown,
+                              const int8_t* d_known, double* d_mi, void* stream)
+{
+  if (cfg == nullptr || d_known == nullptr || d_mi == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  eea_status st = gain_refusal(cfg, range_cells, stride);
+  if (st == EEA_OK) st = eea::p_unknown_refusal(p_unknown);
+  if (st != EEA_OK) return st;
+  const eea::CollisionParams c = grid_params(cfg);
+  EEA_HIP(hipSetDevice(device));
+  EEA_HIP(eea::launch_mi_field(c, range_cells, stride, p_unknown, d_known, d_mi, static_cast<hipStream_t>(stream)));
   return EEA_OK;
 }
 

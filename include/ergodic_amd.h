@@ -753,7 +753,8 @@ eea_status eea_grid_census(int device, const eea_collision_cfg* cfg, const int8_
  * What a scan from each cell of the KNOWN grid would reveal, as the target phi_k: the exact, integer form of the reference's
  * description (README.md:74-76: information obtained by "simulating a 360 degree range finder", "zero after the robot has fully
  * explored the space") with the sensor eea_sense_reveal_batch defines.  It is not FCMI (no noise model, no expectation over
- * measurements): a count of the unknown cells the sensor's beams would cross.  Against the entropy() surrogate of
+ * measurements): a count of the unknown cells the sensor's beams would cross (the expectation over measurements, for an ideal
+ * beam, is eea_sense_mi_field below).  Against the entropy() surrogate of
  * eea_set_target_occupancy: an unknown cell no ray can reach attracts nobody, the field is zero once nothing is left to see,
  * and the re-target needs no host wait.
  * eea_sense_gain_field: d_known (int8 [ysize][xsize], read only) -> d_gain (uint32 [ysize][xsize], EVERY element overwritten).
@@ -788,6 +789,58 @@ eea_status eea_sense_gain_field(int device, const eea_collision_cfg* cfg, unsign
                                 const int8_t* d_known, unsigned* d_gain, void* stream);
 eea_status eea_set_target_gain(eea_engine* e, const eea_collision_cfg* cfg, unsigned range_cells, unsigned stride,
                                const int8_t* d_known, double floor, double lx, double ly, unsigned* d_gain, void* stream);
+
+/* ---- mutual-information target of an exploring fleet (additive to ABI 6: detect these entries by symbol) ------------------------
+ * The information a scan from each cell of the KNOWN grid is EXPECTED to yield, as the target phi_k: the Shannon mutual
+ * information between the map and an ideal (noise-free) beam, taken over every outcome of the beam -- the quantity entropy()
+ * (numerics.hpp:164-179) and the reference's README.md:74-76 describe, which is zero once the map is known.  Against the count of
+ * eea_sense_gain_field it reads the occupancy probabilities 1 .. 99 of a SLAM grid, and an unknown cell behind forty others is
+ * worth less than one at the frontier, because a beam will hardly get that far.  It is not the FSMI paper's estimator: there is
+ * no sensor-noise kernel.  OccupancyMapper stays out as well.
+ * Rays, step offsets d(m, s), the disc test, the grid test, blocks(cell) = !(cell / 100.0 < occupied_threshold) and the candidate
+ * lattice are exactly those of eea_sense_reveal_batch / eea_sense_gain_field above.  Per int8 cell value v, with
+ * 0 < p_unknown < 1:
+ *   o(v)    = p_unknown if v < 0, else (double)min(v, 100) / 100.0;
+ *   h(v)    = 0.0 if o is 0 or 1, else -o log(o) - (1.0 - o) log(1.0 - o) (natural log, double, on the host: entropy()'s formula
+ *             without its 1e-3 / 0.7 clamps);
+ *   pass(v) = 0.0 if blocks(v), else 1.0 - o(v).  blocks looks at the cell VALUE: at a threshold >= 0 an unknown cell never
+ *             blocks, whatever p_unknown is.
+ * Per candidate (i0, j0) (i0 % stride == 0 && j0 % stride == 0) whose own cell does not block, all in fp64, every product and
+ * sum rounded on its own, in exactly this order:
+ *   total = h(own)
+ *   for q = 0 .. 8R - 1:                      (ray order)
+ *     reach = 1.0; beam = 0.0                 (the robot's own cell never attenuates its rays)
+ *     for the steps s = 1, 2, .. ray q makes through `known` (it ends leaving the disc or the grid):
+ *       beam  = beam + reach * h(v_s)
+ *       reach = reach * pass(v_s)             (a blocking cell contributes, then ends the ray: reach becomes +0.0)
+ *     total = total + beam
+ *   mi[i0][j0] = total
+ * Every other element (off the lattice, or a blocking own cell) gets +0.0; EVERY element of d_mi is overwritten.
+ * This IS the mutual information: for a beam through independent cells the measurement Z is the index of the first occupied
+ * cell or "none", a function of the map, so I(M; Z) = H(Z) = sum_s (prod_{l < s} (1 - o_l)) h(o_s) (the chain rule over "does
+ * the beam end at cell s, given it got there"); enumerating all 2^n maps of n = 1, 3, 6 cells agrees to 2e-16 (tests/test_mi.py
+ * repeats that in exact fractions).  The hard stop at blocks() cells keeps the beam consistent with the reveal's sensor and the
+ * planner's notion of an obstacle.  Once reach is +0.0 every further term is +0.0 and x + 0.0 == x bitwise for x >= 0: marching
+ * a dead ray on, or stopping, changes no bit.  The largest value is ln 2 (8 R^2 + 1).
+ * eea_sense_mi_table: a pure host function, no HIP call: entry v + 128 of h256 / pass256 (256 doubles each) receives h(v) /
+ * pass(v) for v = -128 .. 127, of cfg only occupied_threshold is read.  It is the one place a log is evaluated, and the field
+ * entries use exactly these doubles (the launch carries them): the field is held to bits independently of anybody's libm.
+ * EEA_ERR_INVALID_ARGUMENT: cfg, h256 or pass256 null; p_unknown not finite or outside (0, 1).
+ * eea_sense_mi_field: d_known (int8 [ysize][xsize], read only) -> d_mi (double [ysize][xsize]).  A pure function of (known, cfg,
+ * R, stride, p_unknown); no atomics.  Asynchronous on `stream`: reads nothing of the device on the host, allocates nothing and
+ * makes no synchronising call.  Before any HIP call -- the errors of eea_sense_gain_field (d_mi in d_gain's place), then
+ * EEA_ERR_INVALID_ARGUMENT: p_unknown not finite or outside (0, 1).  range_cells > 1024 is EEA_ERR_UNSUPPORTED.
+ * eea_set_target_mi: that field -> phi_k of engine e, all on `stream`, as eea_set_target_gain does it for the count:
+ * v[i][j] = (real)(mi[i][j] + floor) on the candidates whose cell does not block, 0 elsewhere; phi_k is BITWISE what
+ * eea_spatial_coeff_rows (whole grid) followed by eea_set_phik_from_sums give for v: the same launches.  d_mi (optional) receives
+ * the field.  Workspaces (shared with eea_set_target_gain), the repeated call that neither allocates nor waits, the engine's
+ * bookkeeping and the refusals (e null; floor; lx, ly; xsize * ysize > 2^31) are eea_set_target_gain's; with floor == 0 and a
+ * fully known map phi_k is non-finite (0 / 0), as there.  eea_abi_version() stays 6. */
+eea_status eea_sense_mi_table(const eea_collision_cfg* cfg, double p_unknown, double* h256, double* pass256);
+eea_status eea_sense_mi_field(int device, const eea_collision_cfg* cfg, unsigned range_cells, unsigned stride, double p_unknown,
+                              const int8_t* d_known, double* d_mi, void* stream);
+eea_status eea_set_target_mi(eea_engine* e, const eea_collision_cfg* cfg, unsigned range_cells, unsigned stride, double p_unknown,
+                             const int8_t* d_known, double floor, double lx, double ly, double* d_mi, void* stream);
 
 /* ---- fleet layer: the robots of a fleet as obstacles to one another (additive to ABI 6: detect these entries by symbol) --------
  * eea_tick_batch validates every twist against the occupancy grid only: the robots of a tick drive through one another.  A
