@@ -64,6 +64,13 @@ class CollisionCfg(C.Structure):
                 ("occupied_threshold", C.c_double)]
 
 
+class EvidenceCfg(C.Structure):
+    """eea_evidence_cfg: w_occ / w_free evidence units for a hit / a miss, e_clip the clamp at publication, quantum log-odds per
+    unit, thr_miss / thr_false the sensor's error probabilities times 2^32, (seed_lo, seed_hi) the key of the noise stream"""
+    _fields_ = [("w_occ", C.c_int), ("w_free", C.c_int), ("e_clip", C.c_int), ("quantum", C.c_double),
+                ("thr_miss", C.c_uint32), ("thr_false", C.c_uint32), ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32)]
+
+
 class Clearance(C.Structure):
     """eea_clearance: msg (COLLISION_*), sqrd_obs, dx, dy -- crash: 0, 0, 0; none: -1, 0, 0"""
     _fields_ = [("msg", C.c_int), ("sqrd_obs", C.c_int), ("dx", C.c_int), ("dy", C.c_int)]
@@ -273,6 +280,11 @@ def lib():
         L.eea_sense_reveal_batch.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p]
         L.eea_grid_census.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.eea_evidence_table.argtypes = [C.POINTER(EvidenceCfg), C.c_void_p]
+        L.eea_sense_observe_batch.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.POINTER(EvidenceCfg), C.c_uint, C.c_uint, C.c_uint,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p]
+        L.eea_evidence_publish.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.POINTER(EvidenceCfg), C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]
         L.eea_sense_gain_field.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
         L.eea_set_target_gain.argtypes = [C.c_void_p, C.POINTER(CollisionCfg), C.c_uint, C.c_uint, C.c_void_p, C.c_double,
                                           C.c_double, C.c_double, C.c_void_p, C.c_void_p]
@@ -823,6 +835,32 @@ def grid_census(cfg, grid, counts, device=0, stream=None):
     """eea_grid_census: counts [3] (device, 64-bit integers) = unknown cells (< 0), known cells below the occupied threshold,
     blocking cells of the int8 device grid; asynchronous"""
     check(lib().eea_grid_census(device, C.byref(cfg), _ptr(grid), _ptr(counts), C.c_void_p(stream or 0)))
+
+
+def evidence_table(ecfg):
+    """eea_evidence_table: int8 array of 2 e_clip + 1: entry e + e_clip is the occupancy probability (1 .. 99) eea_evidence_publish
+    writes for e evidence units -- the bytes the device looks up.  Host only"""
+    import numpy as np
+    table = np.empty(2 * min(max(int(ecfg.e_clip), 0), 1024) + 1, dtype=np.int8)   # (an e_clip outside 1 .. 1024 is refused)
+    check(lib().eea_evidence_table(C.byref(ecfg), table.ctypes.data_as(C.c_void_p)))
+    return table
+
+
+def sense_observe_batch(cfg, ecfg, range_cells, scan, truth, evid, pose, ranges=None, mask=None, robot0=0, device=0, stream=None):
+    """eea_sense_observe_batch: one noisy scan (number `scan`) of the P robots of pose [P][3], robot b being robot0 + b of the
+    fleet, through the int8 grid truth, fused into evid (int32 [ysize][xsize], in place: + w_occ on a touched cell that appears
+    blocking, - w_free on every other touched cell); ranges [P][8 * range_cells] int32 (optional): the step at which a ray met a
+    cell that appeared blocking or -1; mask [P] int32 (optional): robots with 0 are left out.  Device tensors; asynchronous"""
+    check(lib().eea_sense_observe_batch(device, C.byref(cfg), C.byref(ecfg), int(range_cells), int(scan), int(robot0), _ptr(truth),
+                                        _ptr(evid), _ptr(pose), _ptr(mask), int(pose.shape[0]), _ptr(ranges),
+                                        C.c_void_p(stream or 0)))
+
+
+def evidence_publish(cfg, ecfg, evid, known, counts=None, device=0, stream=None):
+    """eea_evidence_publish: known (int8 [ysize][xsize], every element overwritten) = -1 where evid is 0, else the table's
+    probability of the clamped evidence; counts [3] (device, 64-bit integers, optional): eea_grid_census of known; asynchronous"""
+    check(lib().eea_evidence_publish(device, C.byref(cfg), C.byref(ecfg), _ptr(evid), _ptr(known), _ptr(counts),
+                                     C.c_void_p(stream or 0)))
 
 
 def sense_gain_field(cfg, range_cells, stride, known, gain, device=0, stream=None):

@@ -465,6 +465,28 @@ hipError_t launch_sense_reveal(const CollisionParams& c, unsigned range_cells, c
 hipError_t launch_grid_census(const CollisionParams& c, const int8_t* d_grid, unsigned long long* d_counts, hipStream_t s);
 // (a cell blocks a ray iff cell >= blocking_cutoff(occupied_threshold), above)
 
+// ---- evidence grid: noisy scans fused into occupancy probabilities (evidence_kernel.hip) ----
+// eea_evidence_cfg, checked (entry_util.hpp: evidence_cfg_refusal)
+struct EvidenceParams
+{
+  int w_occ, w_free, e_clip;
+  double quantum;
+  uint32_t thr_miss, thr_false, seed_lo, seed_hi;
+};
+constexpr unsigned kEvidenceMaxR = 127;     // the observe kernel's LDS window, (2R + 1)^2 bytes, must fit 64 KB
+constexpr int kEvidenceMaxClip = 1024;      // the table of a publish launch: 2 * 1024 + 1 bytes in the kernel arguments
+// table [2 e_clip + 1], entry e + e_clip = clamp(floor(100 sigma(e quantum) + 0.5), 1, 99); host only, the one place an exp is
+// evaluated
+void evidence_table(const EvidenceParams& ev, int8_t* table);
+// one noisy scan of every robot's 8 * range_cells rays through d_truth, added into d_evid [ysize][xsize] (atomics: integers)
+hipError_t launch_evidence_observe(const CollisionParams& c, const EvidenceParams& ev, unsigned range_cells, unsigned scan,
+                                   unsigned robot0, const int8_t* d_truth, int32_t* d_evid, const double* d_pose, const int* d_mask,
+                                   unsigned P, int* d_ranges, hipStream_t s);
+// d_known [ysize][xsize] = -1 where d_evid is 0, else the table's byte of the clamped evidence; d_counts [3] (optional): the
+// census of d_known.  The table of the launch is evidence_table's, carried as a kernel argument
+hipError_t launch_evidence_publish(const CollisionParams& c, const EvidenceParams& ev, const int32_t* d_evid, int8_t* d_known,
+                                   unsigned long long* d_counts, hipStream_t s);
+
 // ---- information-gain field of a known grid (gain_kernel.hip) -----------------------------
 // d_gain [ysize][xsize] = per candidate cell (both indices multiples of stride, the cell not blocking) the unknown cells the
 // sensor's 8 * range_cells rays would cross from there through d_known, per beam, + 1 for an unknown own cell; 0 elsewhere

@@ -264,6 +264,19 @@ inline eea_status p_unknown_refusal(double p_unknown)
   return fail(EEA_ERR_INVALID_ARGUMENT, "p_unknown must lie inside (0, 1)");
 }
 
+// what the evidence entries ask of an eea_evidence_cfg (given), before any HIP call; `ev`: what the kernels read of it
+inline eea_status evidence_cfg_refusal(const eea_evidence_cfg* ecfg, eea::EvidenceParams& ev)
+{
+  if (ecfg->w_occ < 1 || ecfg->w_occ > 32767 || ecfg->w_free < 1 || ecfg->w_free > 32767) {
+    return fail(EEA_ERR_INVALID_ARGUMENT, "w_occ and w_free must lie in 1 .. 32767");
+  }
+  if (ecfg->e_clip < 1 || ecfg->e_clip > eea::kEvidenceMaxClip) return fail(EEA_ERR_INVALID_ARGUMENT, "e_clip must lie in 1 .. 1024");
+  if (!(std::isfinite(ecfg->quantum) && ecfg->quantum > 0.0)) return fail(EEA_ERR_INVALID_ARGUMENT, "quantum must be finite and positive");
+  ev = eea::EvidenceParams{ ecfg->w_occ, ecfg->w_free, ecfg->e_clip, ecfg->quantum, ecfg->thr_miss, ecfg->thr_false, ecfg->seed_lo,
+                            ecfg->seed_hi };
+  return EEA_OK;
+}
+
 // the message of a refusal, with the entry's name in front
 inline eea_status named(const char* entry, eea_status st)
 {

@@ -1,5 +1,5 @@
 // C ABI (include/ergodic_amd.h) of the entries that take a device or a layer and no engine: collision, clearance and distance
-// queries, the footprint and its planning entries, the range sensor, the census, the gain and mutual-information fields, and the two layers with their
+// queries, the footprint and its planning entries, the range sensor, the census, the evidence grid, the gain and mutual-information fields, and the two layers with their
 // batch entries.  Argument checking (entry_util.hpp) and kernel dispatch; every refusal comes before the device is selected.
 #include "../../include/ergodic_amd.h"
 
@@ -272,6 +272,58 @@ eea_status eea_grid_census(int device, const eea_collision_cfg* cfg, const int8_
   const eea::CollisionParams c = grid_params(cfg);
   EEA_HIP(hipSetDevice(device));
   EEA_HIP(eea::launch_grid_census(c, d_grid, d_counts, static_cast<hipStream_t>(stream)));
+  return EEA_OK;
+}
+
+// ---- evidence grid: noisy scans fused into occupancy probabilities (evidence_kernel.hip) ----------
+eea_status eea_evidence_table(const eea_evidence_cfg* ecfg, int8_t* table)
+{
+  if (ecfg == nullptr || table == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  eea::EvidenceParams ev;
+  const eea_status st = evidence_cfg_refusal(ecfg, ev);
+  if (st != EEA_OK) return st;
+  eea::evidence_table(ev, table);
+  return EEA_OK;
+}
+
+eea_status eea_sense_observe_batch(int device, const eea_collision_cfg* cfg, const eea_evidence_cfg* ecfg, unsigned range_cells,
+                                   unsigned scan, unsigned robot0, const int8_t* d_truth, int32_t* d_evid, const double* d_pose,
+                                   const int* d_mask, unsigned P, int* d_ranges, void* stream)
+{
+  if (cfg == nullptr || ecfg == nullptr || d_truth == nullptr || d_evid == nullptr || d_pose == nullptr) {
+    return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  }
+  eea_status st = grid_cfg_refusal(cfg);
+  if (st != EEA_OK) return st;
+  if (range_cells == 0) return fail(EEA_ERR_INVALID_ARGUMENT, "range_cells must be positive");
+  eea::EvidenceParams ev;
+  st = evidence_cfg_refusal(ecfg, ev);
+  if (st != EEA_OK) return st;
+  if (range_cells > eea::kEvidenceMaxR) {
+    return fail(EEA_ERR_UNSUPPORTED, "range_cells above 127: the scan's window of (2R + 1)^2 bytes must fit the 64 KB of LDS");
+  }
+  if (P == 0) return EEA_OK;
+  const eea::CollisionParams c = grid_params(cfg);
+  EEA_HIP(hipSetDevice(device));
+  EEA_HIP(eea::launch_evidence_observe(c, ev, range_cells, scan, robot0, d_truth, d_evid, d_pose, d_mask, P, d_ranges,
+                                       static_cast<hipStream_t>(stream)));
+  return EEA_OK;
+}
+
+eea_status eea_evidence_publish(int device, const eea_collision_cfg* cfg, const eea_evidence_cfg* ecfg, const int32_t* d_evid,
+                                int8_t* d_known, unsigned long long* d_counts, void* stream)
+{
+  if (cfg == nullptr || ecfg == nullptr || d_evid == nullptr || d_known == nullptr) {
+    return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  }
+  eea_status st = grid_cfg_refusal(cfg);
+  if (st != EEA_OK) return st;
+  eea::EvidenceParams ev;
+  st = evidence_cfg_refusal(ecfg, ev);
+  if (st != EEA_OK) return st;
+  const eea::CollisionParams c = grid_params(cfg);
+  EEA_HIP(hipSetDevice(device));
+  EEA_HIP(eea::launch_evidence_publish(c, ev, d_evid, d_known, d_counts, static_cast<hipStream_t>(stream)));
   return EEA_OK;
 }
 

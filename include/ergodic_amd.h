@@ -749,6 +749,62 @@ eea_status eea_sense_reveal_batch(int device, const eea_collision_cfg* cfg, unsi
 eea_status eea_grid_census(int device, const eea_collision_cfg* cfg, const int8_t* d_grid, unsigned long long* d_counts,
                            void* stream);
 
+/* ---- evidence grid: the fleet's NOISY scans fused into occupancy probabilities (additive to ABI 6: detect these entries by symbol)
+ * eea_sense_reveal_batch copies the truth: a cell of `known` is -1 or exact.  Here the same sensor is noisy, every scan is evidence
+ * in integer log-odds units, and a publication step turns the evidence into the int8 probabilities 1 .. 99 that the tick, the
+ * census, the gain count and eea_sense_mi_field read.  It is NOT a port of OccupancyMapper: updateCell (mapping.cpp:341-348) rounds
+ * every single update through int8 with a truncating cast, so its grid depends on the order of every beam of every robot.  This
+ * grid is ORDER-FREE -- commutative integer adds, a counter-based noise stream, every output a pure function of its inputs -- and
+ * claims no parity with mapping.cpp; it borrows the sensor-model constants (prob_occ_ 0.90, prob_free_ 0.35, prior 0.5,
+ * mapping.cpp:66-74) and the formula logOdds2Prob (mapping.cpp:51-54).
+ * The rays and step offsets d(m, s), the disc test and the grid test, blocks(v) = !(v / 100.0 < occupied_threshold), the robot's
+ * cell with the off-grid rule, and the mask are exactly those of eea_sense_reveal_batch above.  cfg's radii are not read.
+ * eea_evidence_cfg: w_occ / w_free (1 .. 32767): the evidence units added for a hit / subtracted for a miss; e_clip (1 .. 1024):
+ * the evidence is clamped to [-e_clip, e_clip] AT PUBLICATION ONLY (the grid itself keeps counting); quantum (finite, > 0): log-odds
+ * per unit; thr_miss / thr_false: probabilities thr / 2^32 -- a truly blocking cell is missed with thr_miss, a non-blocking cell
+ * raises a false alarm with thr_false; (seed_lo, seed_hi): the key of the noise stream.
+ * eea_evidence_table: a pure host function, no HIP call.  table has 2 e_clip + 1 bytes; entry e + e_clip =
+ * clamp(floor(100.0 * sigma(e * quantum) + 0.5), 1, 99) with sigma(l) = 1.0 - 1.0 / (1.0 + exp(l)) in double: to nearest, not the
+ * reference's truncation (which would leave its own 0.90 at the mercy of the last bit of exp).  The one place an exp is evaluated;
+ * the device only looks these bytes up.
+ * eea_sense_observe_batch: ONE noisy scan of every robot, fused into d_evid (int32 [ysize][xsize]; the caller zeroes it once).
+ *   what a scan sees: for robot b let g = robot0 + b; for the grid cell (i, j) let r be word j & 3 of Philox4x32-10 (the replay
+ *     memory's generator) at the counter (j >> 2, i, g, scan) under the key (seed_lo, seed_hi).  The cell APPEARS BLOCKING in this
+ *     robot's scan iff blocks(truth[i][j]) ? !(r < thr_miss) : (r < thr_false).  One outcome per (robot, scan, cell), whichever
+ *     ray reaches the cell; the robot's own cell never appears blocking;
+ *   the rays march exactly as in the reveal with "blocks" replaced by "appears blocking".  A cell is TOUCHED if it is the robot's
+ *     own cell or a ray visits it (the cell that ends a ray included).  d_ranges [P][eea_sense_ray_count(R)] (optional) receives
+ *     the step of the ending cell or -1; a robot off the grid gets a row of -1, a masked-out one is not written;
+ *   fusion: each robot adds +w_occ to every touched cell that appears blocking and -w_free to every other touched cell, at most
+ *     once per cell per scan however many of its rays cross the cell.  Plain two's-complement int32 adds: the result is a pure
+ *     function of (truth, evid before, poses, mask, cfgs, R, scan, robot0) and does not depend on the order of robots, rays,
+ *     workgroups or calls -- one call over P robots equals calls over its parts with robot0 advanced.  Keeping
+ *     scans * robots * max(w_occ, w_free) below 2^31 is the CALLER's business.
+ *   Asynchronous on `stream`: no host read, no allocation, no synchronising call; P == 0 is EEA_OK with nothing launched.
+ * eea_evidence_publish: EVERY element of d_known (int8 [ysize][xsize]) is overwritten with
+ *   e == 0 ? -1 : table[clamp(e, -e_clip, e_clip) + e_clip],   e = d_evid[i][j], table = eea_evidence_table's:
+ * evidence that cancels to zero is the prior again, "unknown", which eea_sense_mi_field prices with p_unknown.  d_counts [3]
+ * (optional) receives what eea_grid_census gives on the published grid, in the same launch sequence.  The launch carries the
+ * table's <= 2049 bytes in its arguments: asynchronous on `stream`, no host wait, no allocation.
+ * Before any HIP call -- EEA_ERR_INVALID_ARGUMENT: cfg, ecfg, table, d_truth, d_evid, d_pose or d_known null; xsize or ysize 0;
+ * resolution <= 0; range_cells == 0; w_occ or w_free outside 1 .. 32767; e_clip outside 1 .. 1024; quantum not finite or <= 0.
+ * EEA_ERR_UNSUPPORTED: range_cells > 127 (only the LDS form is built: the scan's window of (2R + 1)^2 bytes must fit 64 KB).
+ * eea_abi_version() stays 6. */
+typedef struct {
+  int w_occ, w_free;            /* 1 .. 32767: evidence units added for a hit, subtracted for a miss */
+  int e_clip;                   /* 1 .. 1024: evidence is clamped to [-e_clip, e_clip] at publication only */
+  double quantum;               /* finite, > 0: log-odds per unit */
+  uint32_t thr_miss, thr_false; /* probability = thr / 2^32; a truly blocking cell is missed with thr_miss,
+                                   a non-blocking cell raises a false alarm with thr_false */
+  uint32_t seed_lo, seed_hi;
+} eea_evidence_cfg;
+eea_status eea_evidence_table(const eea_evidence_cfg* ecfg, int8_t* table);
+eea_status eea_sense_observe_batch(int device, const eea_collision_cfg* cfg, const eea_evidence_cfg* ecfg, unsigned range_cells,
+                                   unsigned scan, unsigned robot0, const int8_t* d_truth, int32_t* d_evid, const double* d_pose,
+                                   const int* d_mask, unsigned P, int* d_ranges, void* stream);
+eea_status eea_evidence_publish(int device, const eea_collision_cfg* cfg, const eea_evidence_cfg* ecfg, const int32_t* d_evid,
+                                int8_t* d_known, unsigned long long* d_counts, void* stream);
+
 /* ---- information-gain target of an exploring fleet (additive to ABI 6: detect these entries by symbol) -------------------------
  * What a scan from each cell of the KNOWN grid would reveal, as the target phi_k: the exact, integer form of the reference's
  * description (README.md:74-76: information obtained by "simulating a 360 degree range finder", "zero after the robot has fully
