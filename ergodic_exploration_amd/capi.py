@@ -79,6 +79,8 @@ class Clearance(C.Structure):
 COLLISION_CRASH, COLLISION_OBSTACLE, COLLISION_NONE = 0, 1, 2   # CollisionMsg (collision.hpp:55-60)
 COLLISION_OFF_GRID = 3       # the distance queries only: the pose's cell is not on the grid
 DISTANCE_MAX_SIDE = 8192     # EEA_DISTANCE_MAX_SIDE
+GEODESIC_TILE_X, GEODESIC_TILE_Y = 32, 32           # EEA_GEODESIC_TILE_X / _Y: the tile of the geodesic field's rounds
+GEODESIC_UNKNOWN_BLOCKS, GEODESIC_CONTINUE = 1, 2   # EEA_GEODESIC_*: flags of geodesic_field
 FOOTPRINT_MAX_VERTICES = 16  # EEA_FOOTPRINT_MAX_VERTICES
 
 
@@ -243,6 +245,14 @@ def lib():
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             L.eea_distance_traj_min.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint,
                                                 C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "eea_geodesic_field"):    # additive to ABI 6 as well
+            L.eea_geodesic_ws_bytes.argtypes = [C.POINTER(CollisionCfg), C.POINTER(C.c_size_t)]
+            L.eea_geodesic_field.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_void_p, C.c_void_p, C.c_int, C.c_uint, C.c_void_p,
+                                             C.c_uint, C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.eea_geodesic_path_batch.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_void_p, C.c_void_p, C.c_uint, C.c_uint,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p]
+            L.eea_set_target_reachable.argtypes = [C.c_void_p, C.POINTER(CollisionCfg), C.c_int, C.c_void_p, C.c_uint, C.c_void_p,
+                                                   C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p]
         if hasattr(L, "eea_footprint_check_batch"):   # additive to ABI 6 as well
             L.eea_footprint_radii.argtypes = [C.POINTER(Footprint), C.POINTER(C.c_double), C.POINTER(C.c_double)]
             L.eea_footprint_check_batch.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.POINTER(Footprint), C.c_void_p, C.c_void_p,
@@ -419,6 +429,13 @@ class Engine:
         field"""
         check(lib().eea_set_target_mi(self.h, C.byref(cfg), int(range_cells), int(stride), float(p_unknown), _ptr(known),
                                       float(floor), lx, ly, _ptr(mi), C.c_void_p(stream or 0)))
+
+    def set_target_reachable(self, cfg, kind, field, stride, known, geo, lx, ly, floor=0.0, stream=None):
+        """eea_set_target_reachable: field (kind 0: the uint32 field of sense_gain_field, 1: the double field of sense_mi_field)
+        + floor on the candidates of the int8 device grid `known` that do not block and have geo >= 0 (geodesic_field) -> phi_k,
+        all on `stream` without a host wait"""
+        check(lib().eea_set_target_reachable(self.h, C.byref(cfg), int(kind), _ptr(field), int(stride), _ptr(known), _ptr(geo),
+                                             float(floor), lx, ly, C.c_void_p(stream or 0)))
 
     def spatial_coeff_occupancy_rows(self, nx, ny_total, row0, nrows, occ_rows, lx, ly, out_sums, stream=None):
         """un-normalised coefficient sums of the occupancy rows [row0, row0+nrows) (device int8 tensor)"""
@@ -755,6 +772,34 @@ def distance_traj_min(cfg, sq, nearest, traj, out=None, step=None, dmin=None, de
     tensors; asynchronous"""
     check(lib().eea_distance_traj_min(device, C.byref(cfg), _ptr(sq), _ptr(nearest), _ptr(traj), int(traj.shape[0]),
                                       int(traj.shape[1]), _ptr(out), _ptr(step), _ptr(dmin), C.c_void_p(stream or 0)))
+
+
+def geodesic_ws_bytes(cfg):
+    """eea_geodesic_ws_bytes: the bytes of workspace geodesic_field needs for the grid of cfg; host only"""
+    n = C.c_size_t()
+    check(lib().eea_geodesic_ws_bytes(C.byref(cfg), C.byref(n)))
+    return n.value
+
+
+def geodesic_field(cfg, grid, geo, ws, state, pose=None, cells=None, sq=None, clear_sq=0, flags=0, max_rounds=0, device=0,
+                   stream=None):
+    """eea_geodesic_field: geo int32 [ysize][xsize] = the 5-7 chamfer cost of the cheapest move sequence through traversable
+    cells of the int8 device grid from the cells of pose [P][3] and / or the row-major indices cells (int32), -1 where there is
+    none.  sq: the int32 plane of distance_field for the same grid (cells within clear_sq of an occupied one are not
+    traversable) or None; ws: geodesic_ws_bytes(cfg) bytes; state: uint32 [4] (final, rounds that changed something, accepted
+    sources, 0).  max_rounds == 0 runs to the end and waits on the stream; max_rounds > 0 enqueues at most that many rounds
+    and does not wait.  Device tensors"""
+    check(lib().eea_geodesic_field(device, C.byref(cfg), _ptr(grid), _ptr(sq), int(clear_sq), int(flags), _ptr(pose),
+                                   0 if pose is None else int(pose.shape[0]), _ptr(cells), 0 if cells is None else int(cells.shape[0]),
+                                   int(max_rounds), _ptr(geo), _ptr(ws), _ptr(state), C.c_void_p(stream or 0)))
+
+
+def geodesic_path_batch(cfg, geo, pose, path, length=None, device=0, stream=None):
+    """eea_geodesic_path_batch: path float64 [P][n_steps][3] = the descent of geo from each pose of pose [P][3] as way-points
+    (cell centres, the heading of the move), padded with the last one -- the layout xt_ref of dwa_control_batch reads; length:
+    int32 [P] (moves written, -1: the pose is off the grid or unreachable) or None.  Device tensors; asynchronous"""
+    check(lib().eea_geodesic_path_batch(device, C.byref(cfg), _ptr(geo), _ptr(pose), int(pose.shape[0]), int(path.shape[1]),
+                                        _ptr(path), _ptr(length), C.c_void_p(stream or 0)))
 
 
 def footprint_radii(fp):

@@ -510,6 +510,37 @@ template <typename R>
 hipError_t launch_mi_values(const CollisionParams& c, unsigned stride, const int8_t* d_known, const double* d_mi, double floor,
                             R* d_values, hipStream_t s);
 
+// ---- geodesic field: 5-7 chamfer shortest paths through traversable cells (geodesic_kernel.hip) ----
+// a workgroup owns a tile of kGeodesicTileX x kGeodesicTileY cells (the header publishes both)
+constexpr unsigned kGeodesicTileX = 32, kGeodesicTileY = 32;
+// the largest xsize * ysize: 7 * cells stays inside int
+constexpr unsigned long long kGeodesicMaxCells = 1ull << 26;
+// rounds the waiting form enqueues between two looks at the state
+constexpr unsigned kGeodesicBatch = 16;
+size_t geodesic_ws_bytes(unsigned xsize, unsigned ysize);
+// what a call reads of its arguments beside the buffers
+struct GeodesicArgs
+{
+  int clear_sq;
+  bool unknown_blocks, keep_field;  // EEA_GEODESIC_UNKNOWN_BLOCKS, EEA_GEODESIC_CONTINUE
+  unsigned P, n_cells;
+};
+// traversability plane, tile flags and round words into d_ws, d_geo = -1 (unless keep_field), the sources seeded, d_state =
+// {0, 0, accepted sources, 0}: the state before round 0
+hipError_t launch_geodesic_begin(const CollisionParams& c, const GeodesicArgs& a, const int8_t* d_grid, const int* d_sq,
+                                 const double* d_pose, const int* d_cells, int* d_geo, void* d_ws, unsigned* d_state, hipStream_t s);
+// rounds first .. first + count - 1, one launch each, then d_state[0] / [1] brought up to date
+hipError_t launch_geodesic_rounds(const CollisionParams& c, unsigned first, unsigned count, int* d_geo, void* d_ws, unsigned* d_state,
+                                  hipStream_t s);
+// d_path [P][n_steps][3], d_len [P] (may be null): the descent of d_geo from each pose of d_pose [P][3]
+hipError_t launch_geodesic_path(const CollisionParams& c, const int* d_geo, const double* d_pose, unsigned P, unsigned n_steps,
+                                double* d_path, int* d_len, hipStream_t s);
+// d_values [ysize][xsize] = (R)((double)field + floor) on the candidates whose cell does not block and has d_geo >= 0, 0
+// elsewhere; kind 0: d_field is uint32, 1: double
+template <typename R>
+hipError_t launch_reachable_values(const CollisionParams& c, int kind, const void* d_field, unsigned stride, const int8_t* d_known,
+                                   const int* d_geo, double floor, R* d_values, hipStream_t s);
+
 // ======================================================================================
 // device helpers
 // ======================================================================================

@@ -1833,6 +1833,24 @@ eea_status eea_set_target_mi(eea_engine* e, const eea_collision_cfg* cfg, unsign
                            });
 }
 
+// the target of a field the caller already has (kind 0: the gain count, 1: the mutual information), on the candidates that
+// d_geo reaches: no field launch, the value grid of geodesic_kernel.hip, then the launches the two entries above share
+eea_status eea_set_target_reachable(eea_engine* e, const eea_collision_cfg* cfg, int kind, const void* d_field, unsigned stride,
+                                    const int8_t* d_known, const int* d_geo, double floor, double lx, double ly, void* stream)
+{
+  if (e == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null engine");
+  const eea_status st = eea::reachable_refusal(cfg, kind, d_field, stride, d_known, d_geo);
+  if (st != EEA_OK) return st;
+  const eea::CollisionParams c = grid_params(cfg);
+  // (the field is the caller's and read only: no workspace is taken for it)
+  return target_from_field(e, c, "reachable", floor, lx, ly, static_cast<const char*>(d_field), stream,
+                           [&](auto r, const char*, void* d_values, hipStream_t s) {
+                             using R = decltype(r);
+                             EEA_HIP(eea::launch_reachable_values<R>(c, kind, d_field, stride, d_known, d_geo, floor, as<R>(d_values), s));
+                             return EEA_OK;
+                           });
+}
+
 }  // extern "C"
 
 // ---- the fleet tick: one iteration of Exploration<ModelT>::control's loop body for B robots (exploration.hpp:220-279) ----

@@ -257,6 +257,36 @@ inline eea_status gain_refusal(const eea_collision_cfg* cfg, unsigned range_cell
   return EEA_OK;
 }
 
+// what the three geodesic entries ask of the configuration, before the device is selected: the distance calls' checks, then
+// the limits that keep 7 * cells inside an int
+inline eea_status geodesic_cfg_refusal(const eea_collision_cfg* cfg)
+{
+  const eea_status st = grid_query_cfg_refusal(cfg);
+  if (st != EEA_OK) return st;
+  if (cfg->xsize > eea::kDistanceMaxSide || cfg->ysize > eea::kDistanceMaxSide) {
+    return fail(EEA_ERR_UNSUPPORTED, "the geodesic field takes grids of up to EEA_DISTANCE_MAX_SIDE cells per side");
+  }
+  if (static_cast<unsigned long long>(cfg->xsize) * cfg->ysize > eea::kGeodesicMaxCells) {
+    return fail(EEA_ERR_UNSUPPORTED, "the geodesic field takes grids of up to 2^26 cells");
+  }
+  return EEA_OK;
+}
+
+// the argument checks of eea_set_target_reachable before the target's own (target_from_field): eea_set_target_gain's without a
+// range, and the field it is handed
+inline eea_status reachable_refusal(const eea_collision_cfg* cfg, int kind, const void* d_field, unsigned stride, const void* d_known,
+                                    const void* d_geo)
+{
+  if (cfg == nullptr || d_known == nullptr || d_field == nullptr || d_geo == nullptr) {
+    return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  }
+  const eea_status st = grid_cfg_refusal(cfg);
+  if (st != EEA_OK) return st;
+  if (stride == 0) return fail(EEA_ERR_INVALID_ARGUMENT, "stride must be positive");
+  if (kind != 0 && kind != 1) return fail(EEA_ERR_INVALID_ARGUMENT, "kind must be 0 (gain field) or 1 (mutual-information field)");
+  return EEA_OK;
+}
+
 // what the mutual-information entries ask of the probability of an unknown cell: inside (0, 1)
 inline eea_status p_unknown_refusal(double p_unknown)
 {

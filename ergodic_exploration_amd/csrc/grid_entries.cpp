@@ -1,8 +1,9 @@
 // C ABI (include/ergodic_amd.h) of the entries that take a device or a layer and no engine: collision, clearance and distance
-// queries, the footprint and its planning entries, the range sensor, the census, the evidence grid, the gain and mutual-information fields, and the two layers with their
+// queries, the geodesic field and its paths, the footprint and its planning entries, the range sensor, the census, the evidence grid, the gain and mutual-information fields, and the two layers with their
 // batch entries.  Argument checking (entry_util.hpp) and kernel dispatch; every refusal comes before the device is selected.
 #include "../../include/ergodic_amd.h"
 
+#include <cstdint>
 #include <new>
 #include <string>
 
@@ -154,6 +155,69 @@ eea_status eea_distance_traj_min(int device, const eea_collision_cfg* cfg, const
   EEA_HIP(hipSetDevice(device));
   EEA_HIP(eea::launch_distance_traj_min(c, cfg->boundary_radius, d_sq, d_nearest, d_traj, B, T, reinterpret_cast<int*>(d_out),
                                         d_step, d_dmin, static_cast<hipStream_t>(stream)));
+  return EEA_OK;
+}
+
+// ---- geodesic field: 5-7 chamfer shortest paths through traversable cells (geodesic_kernel.hip) ----
+eea_status eea_geodesic_ws_bytes(const eea_collision_cfg* cfg, size_t* bytes)
+{
+  const eea_status st = geodesic_cfg_refusal(cfg);
+  if (st != EEA_OK) return st;
+  if (bytes == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  *bytes = eea::geodesic_ws_bytes(cfg->xsize, cfg->ysize);
+  return EEA_OK;
+}
+
+eea_status eea_geodesic_field(int device, const eea_collision_cfg* cfg, const int8_t* d_grid, const int* d_sq, int clear_sq,
+                              unsigned flags, const double* d_pose, unsigned P, const int* d_cells, unsigned n_cells,
+                              unsigned max_rounds, int* d_geo, void* d_ws, unsigned* d_state, void* stream)
+{
+  const eea_status st = geodesic_cfg_refusal(cfg);
+  if (st != EEA_OK) return st;
+  if (d_grid == nullptr || d_geo == nullptr || d_ws == nullptr || d_state == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  if ((flags & ~static_cast<unsigned>(EEA_GEODESIC_UNKNOWN_BLOCKS | EEA_GEODESIC_CONTINUE)) != 0u) {
+    return fail(EEA_ERR_INVALID_ARGUMENT, "unknown flag bits");
+  }
+  if (clear_sq < 0) return fail(EEA_ERR_INVALID_ARGUMENT, "clear_sq must be >= 0");
+  if (reinterpret_cast<uintptr_t>(d_ws) % 4u != 0u) return fail(EEA_ERR_INVALID_ARGUMENT, "d_ws must be 4-byte aligned");
+  eea::GeodesicArgs a;
+  a.clear_sq = clear_sq;
+  a.unknown_blocks = (flags & EEA_GEODESIC_UNKNOWN_BLOCKS) != 0u;
+  a.keep_field = (flags & EEA_GEODESIC_CONTINUE) != 0u;
+  a.P = d_pose != nullptr ? P : 0u;
+  a.n_cells = d_cells != nullptr ? n_cells : 0u;
+  if (a.P == 0u && a.n_cells == 0u && !a.keep_field) return fail(EEA_ERR_INVALID_ARGUMENT, "the geodesic field needs a source list");
+  const eea::CollisionParams c = grid_params(cfg);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  EEA_HIP(hipSetDevice(device));
+  EEA_HIP(eea::launch_geodesic_begin(c, a, d_grid, d_sq, d_pose, d_cells, d_geo, d_ws, d_state, s));
+  if (max_rounds != 0u) {
+    EEA_HIP(eea::launch_geodesic_rounds(c, 0u, max_rounds, d_geo, d_ws, d_state, s));
+    return EEA_OK;
+  }
+  // the waiting form: a look at d_state[0] behind every batch of rounds.  A round that is not the last lowers a cell, and a
+  // cell takes finitely many values: the cap below is never met by a field that converges as it must
+  const unsigned long long cap = static_cast<unsigned long long>(c.xsize) * c.ysize + eea::kGeodesicBatch;
+  for (unsigned long long first = 0; first < cap; first += eea::kGeodesicBatch) {
+    unsigned final_field = 0u;
+    EEA_HIP(eea::launch_geodesic_rounds(c, static_cast<unsigned>(first), eea::kGeodesicBatch, d_geo, d_ws, d_state, s));
+    EEA_HIP(hipMemcpyAsync(&final_field, d_state, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    EEA_HIP(hipStreamSynchronize(s));
+    if (final_field != 0u) return EEA_OK;
+  }
+  return fail(EEA_ERR_HIP, "eea_geodesic_field: the rounds did not reach a fixed point");
+}
+
+eea_status eea_geodesic_path_batch(int device, const eea_collision_cfg* cfg, const int* d_geo, const double* d_pose, unsigned P,
+                                   unsigned n_steps, double* d_path, int* d_len, void* stream)
+{
+  const eea_status st = geodesic_cfg_refusal(cfg);
+  if (st != EEA_OK) return st;
+  if (d_geo == nullptr || d_pose == nullptr || d_path == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  if (n_steps == 0u) return fail(EEA_ERR_INVALID_ARGUMENT, "n_steps must be positive");
+  if (P == 0u) return EEA_OK;
+  EEA_HIP(hipSetDevice(device));
+  EEA_HIP(eea::launch_geodesic_path(grid_params(cfg), d_geo, d_pose, P, n_steps, d_path, d_len, static_cast<hipStream_t>(stream)));
   return EEA_OK;
 }
 

@@ -1029,6 +1029,81 @@ eea_status eea_distance_traj_min(int device, const eea_collision_cfg* cfg, const
                                  const double* d_traj, unsigned B, unsigned T, eea_clearance* d_out, int* d_step, double* d_dmin,
                                  void* stream);
 
+/* ---- geodesic field: shortest paths through free space (additive to ABI 6: detect these entries by symbol) ---------------
+ * No reference counterpart.  Every other distance here is straight-line; these give the cost of getting somewhere: the
+ * shortest-path distance through traversable cells from a set of source cells, as a field on the grid.  Seeded from the
+ * fleet's poses it is a reachability mask for the targets (eea_set_target_reachable); seeded from goal cells, descending it
+ * gives a detour path in the layout the dynamic window's trajectory mode reads (eea_geodesic_path_batch).  Grid, the cell of
+ * a pose (world2Grid, x86 wrap included), gridBounds and blocks(v) = !(v / 100.0 < occupied_threshold) as everywhere else.
+ * Integers with a unique answer: bit-reproducible.
+ *   traversable   a cell (i, j) in the grid with !blocks(grid[i][j]); with EEA_GEODESIC_UNKNOWN_BLOCKS also grid[i][j] >= 0;
+ *                 with d_sq != NULL also d_sq[i][j] == -1 || d_sq[i][j] > clear_sq.  d_sq is eea_distance_field's plane of the
+ *                 same grid, clear_sq >= 0 a squared cell radius (r_col^2 for the disc, ceil(r_out / res)^2 for a polygon).
+ *   moves         the four axis moves cost 5, the four diagonal moves cost 7 (the 5-7 chamfer).  A move goes only INTO a
+ *                 traversable cell; a diagonal move also needs both cells it passes between to be traversable (no corner
+ *                 cutting).
+ *   sources       the cells of d_pose [P][3] (poses failing gridBounds are skipped) and / or the row-major indices d_cells
+ *                 [n_cells] (negative or out-of-range ones are skipped).  A source's own cell is seeded with 0 whenever it is in
+ *                 the grid and does not block: the unknown test and the clearance test are waived for it (a robot is where it
+ *                 is, and must be able to leave a tight spot).  Nothing moves into a non-traversable source cell.
+ *   field         geo[i][j] (int32) = the cost of the cheapest move sequence from any source cell to (i, j); -1 where there is
+ *                 none (blocking cells, non-traversable non-source cells, cells cut off from every source, every cell when no
+ *                 source is accepted).  EVERY element is overwritten.
+ * Limits: xsize * ysize <= 2^26 (7 * cells < 2^31) and sides of at most EEA_DISTANCE_MAX_SIDE, else EEA_ERR_UNSUPPORTED.
+ * The build works on tiles of EEA_GEODESIC_TILE_X x EEA_GEODESIC_TILE_Y cells, in rounds of one launch each: a tile whose
+ * neighbourhood changed in the round before is relaxed to its own fixed point, values only go down, and every value ever
+ * written is the cost of a real move sequence.  Nothing waits inside a kernel.
+ * eea_geodesic_ws_bytes: host only; the bytes d_ws must hold for the grid of cfg (positive, monotone in the grid's size).  d_ws
+ *   is device memory aligned to 4 bytes (any allocation's start is); its contents mean nothing between calls.
+ * eea_geodesic_field: d_state [4] (uint32, device) receives [0] 1 if the field is final, else 0; [1] the number of rounds that
+ *   changed something; [2] the number of accepted sources (entries of the two lists, not distinct cells); [3] 0.
+ *   max_rounds > 0: at most that many rounds are enqueued on `stream`; nothing of the device is read on the host, nothing is
+ *     allocated and no synchronising call is made; a round that finds nothing pending exits at once.  If the budget runs out
+ *     first d_state[0] = 0, every element of d_geo is -1 or the cost of a real move sequence (>= the final value), and no
+ *     element that is -1 in the final field holds anything else.
+ *   max_rounds == 0: the call runs to the end and WAITS on `stream` for it: it reads d_state[0] on the host after every
+ *     16 rounds (as eea_set_target_occupancy, this form is not for a loop that must not wait).
+ *   EEA_GEODESIC_CONTINUE: d_geo is taken as it stands -- valid when it comes from an earlier call with the same or a smaller
+ *     traversable set and the same or fewer sources (this call's are the same or more) --, the sources are seeded again and every
+ *     tile is pending; it ends at the same bits as a fresh call.  d_state counts this call's rounds.
+ *   Before the device is selected, with no output touched -- EEA_ERR_INVALID_ARGUMENT: cfg, d_grid, d_geo, d_ws or d_state null;
+ *   no source list with entries (d_pose null or P == 0, and d_cells null or n_cells == 0) without EEA_GEODESIC_CONTINUE;
+ *   clear_sq < 0; unknown flag bits; d_ws not 4-byte aligned; the configuration errors of the distance calls.  EEA_ERR_UNSUPPORTED: the limits above.
+ * eea_geodesic_path_batch: per pose of d_pose [P][3], from d_geo alone, d_path [P][n_steps][3] (the layout d_xt_ref of the
+ *   three dynamic-window entries reads) and d_len [P] (may be NULL).  With c the pose's cell: if c is off the grid or
+ *   geo[c] < 0, len = -1 and all n_steps rows hold the pose itself.  Otherwise, until geo[c] == 0 or n_steps way-points are
+ *   written: among the eight moves tried in the order (di, dj) = (0,+1) (+1,0) (0,-1) (-1,0) (+1,+1) (+1,-1) (-1,-1) (-1,+1)
+ *   take the first whose target n has geo[n] >= 0 and geo[n] + cost == geo[c] (for a diagonal both passed-between cells must have
+ *   geo >= 0 as well); the way-point is the centre of n, x = (double)(j * res) + res / 2.0 + xmin and likewise y, with the
+ *   heading of the move, atan2(di, dj) as one of eight literal doubles k pi / 4 in [-pi, pi) (0, pi/2, -pi, -pi/2, pi/4, 3pi/4,
+ *   -3pi/4, -pi/4 in the order above; no atan2 runs on the device); c = n.  In a final field such a move exists for every
+ *   reachable non-source cell; where a field that is not final has none the walk ends.  Rows past the end repeat the last
+ *   way-point -- before any way-point: the centre of the pose's own cell with the pose's heading, so a pose on a source cell
+ *   gets n_steps such rows and len 0.  len = the number of moves written, <= n_steps.  One lane per pose; asynchronous on
+ *   `stream`.  P == 0 is EEA_OK.  EEA_ERR_INVALID_ARGUMENT: cfg, d_geo, d_pose or d_path null; n_steps == 0; the configuration
+ *   errors above.  EEA_ERR_UNSUPPORTED: the limits above.
+ * eea_set_target_reachable: phi_k of engine e from a field the caller already has, restricted to reachable cells.  kind 0:
+ *   d_field is the uint32 field of eea_sense_gain_field; kind 1: the double field of eea_sense_mi_field.  The value grid is
+ *   v[i][j] = (real)((double)field[i][j] + floor) on the candidates (both indices multiples of stride) whose cell of d_known does
+ *   not block and has d_geo[i][j] >= 0, 0 elsewhere; phi_k is BITWISE what eea_spatial_coeff_rows (whole grid) followed by
+ *   eea_set_phik_from_sums give for v: the launches of eea_set_target_gain, on `stream`, in both engine precisions.  Workspaces,
+ *   the repeated call that neither allocates nor waits, the engine's bookkeeping and the refusals (e, cfg or d_known null;
+ *   xsize or ysize 0; resolution <= 0; stride == 0; floor; lx, ly; xsize * ysize > 2^31) are eea_set_target_gain's, and
+ *   EEA_ERR_INVALID_ARGUMENT: d_field or d_geo null, kind outside {0, 1}.  With floor > 0 and a fully explored map the target is
+ *   uniform over the reachable candidates only; with nothing reachable phi_k is non-finite, as an all-zero grid is there.
+ * eea_abi_version() stays 6. */
+#define EEA_GEODESIC_TILE_X 32 /* the build's tile, published so that tests can size scenes from it */
+#define EEA_GEODESIC_TILE_Y 32
+enum { EEA_GEODESIC_UNKNOWN_BLOCKS = 1, EEA_GEODESIC_CONTINUE = 2 };
+eea_status eea_geodesic_ws_bytes(const eea_collision_cfg* cfg, size_t* bytes);
+eea_status eea_geodesic_field(int device, const eea_collision_cfg* cfg, const int8_t* d_grid, const int* d_sq, int clear_sq,
+                              unsigned flags, const double* d_pose, unsigned P, const int* d_cells, unsigned n_cells,
+                              unsigned max_rounds, int* d_geo, void* d_ws, unsigned* d_state, void* stream);
+eea_status eea_geodesic_path_batch(int device, const eea_collision_cfg* cfg, const int* d_geo, const double* d_pose, unsigned P,
+                                   unsigned n_steps, double* d_path, int* d_len, void* stream);
+eea_status eea_set_target_reachable(eea_engine* e, const eea_collision_cfg* cfg, int kind, const void* d_field, unsigned stride,
+                                    const int8_t* d_known, const int* d_geo, double floor, double lx, double ly, void* stream);
+
 /* ---- footprint collision: a convex polygon base, checked through the distance field ----------------------------------
  * No reference counterpart (the reference README lists "model the robot's base as a polygon for collision detection" and "use
  * a distance field for detecting obstacle cells" under "Future Improvements").  Every other collision call treats the robot
