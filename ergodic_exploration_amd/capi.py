@@ -253,6 +253,16 @@ def lib():
                                                   C.c_void_p, C.c_void_p, C.c_void_p]
             L.eea_set_target_reachable.argtypes = [C.c_void_p, C.POINTER(CollisionCfg), C.c_int, C.c_void_p, C.c_uint, C.c_void_p,
                                                    C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p]
+        if hasattr(L, "eea_geodesic_partition"):    # additive to ABI 6 as well
+            L.eea_partition_ws_bytes.argtypes = [C.POINTER(CollisionCfg), C.POINTER(C.c_size_t)]
+            L.eea_geodesic_partition.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_void_p, C.c_void_p, C.c_int, C.c_uint,
+                                                 C.c_void_p, C.c_uint, C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]
+            L.eea_partition_goals.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_int, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_uint, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]
+            L.eea_partition_path_batch.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint,
+                                                   C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
         if hasattr(L, "eea_footprint_check_batch"):   # additive to ABI 6 as well
             L.eea_footprint_radii.argtypes = [C.POINTER(Footprint), C.POINTER(C.c_double), C.POINTER(C.c_double)]
             L.eea_footprint_check_batch.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.POINTER(Footprint), C.c_void_p, C.c_void_p,
@@ -800,6 +810,44 @@ def geodesic_path_batch(cfg, geo, pose, path, length=None, device=0, stream=None
     int32 [P] (moves written, -1: the pose is off the grid or unreachable) or None.  Device tensors; asynchronous"""
     check(lib().eea_geodesic_path_batch(device, C.byref(cfg), _ptr(geo), _ptr(pose), int(pose.shape[0]), int(path.shape[1]),
                                         _ptr(path), _ptr(length), C.c_void_p(stream or 0)))
+
+
+def partition_ws_bytes(cfg):
+    """eea_partition_ws_bytes: the bytes of workspace geodesic_partition needs for the grid of cfg; host only"""
+    n = C.c_size_t()
+    check(lib().eea_partition_ws_bytes(C.byref(cfg), C.byref(n)))
+    return n.value
+
+
+def geodesic_partition(cfg, grid, geo, owner, ws, state, pose=None, cells=None, sq=None, clear_sq=0, flags=0, max_rounds=0,
+                       device=0, stream=None):
+    """eea_geodesic_partition: geodesic_field's geo int32 [ysize][xsize] for the same arguments, and owner int32 [ysize][xsize]
+    = the label of the source that reaches the cell most cheaply (pose q has label q, cell k label P + k; the smallest label
+    among those at that cost), -1 where geo is -1.  ws: partition_ws_bytes(cfg) bytes, 8-byte aligned; state, max_rounds, flags
+    as geodesic_field (GEODESIC_CONTINUE rebuilds from geo AND owner).  Device tensors"""
+    check(lib().eea_geodesic_partition(device, C.byref(cfg), _ptr(grid), _ptr(sq), int(clear_sq), int(flags), _ptr(pose),
+                                       0 if pose is None else int(pose.shape[0]), _ptr(cells),
+                                       0 if cells is None else int(cells.shape[0]), int(max_rounds), _ptr(geo), _ptr(owner), _ptr(ws),
+                                       _ptr(state), C.c_void_p(stream or 0)))
+
+
+def partition_goals(cfg, kind, field, stride, known, geo, owner, goal_cell, goal_score, area, w_field=1.0, w_cost=0.0, device=0,
+                    stream=None):
+    """eea_partition_goals: per label r < len(goal_cell): area uint32 [n] = the cells owner r holds; goal_cell int32 [n] = the
+    candidate of r (owner r, on the stride lattice, not blocking in the int8 grid `known`, field > 0) with the greatest
+    w_field * field - w_cost * geo, the lowest index on a tie, -1 for none; goal_score float64 [n] = that score or 0.0.  kind 0:
+    field is the uint32 field of sense_gain_field, 1: the double field of sense_mi_field.  Device tensors; asynchronous"""
+    check(lib().eea_partition_goals(device, C.byref(cfg), int(kind), _ptr(field), int(stride), _ptr(known), _ptr(geo), _ptr(owner),
+                                    int(goal_cell.shape[0]), float(w_field), float(w_cost), _ptr(goal_cell), _ptr(goal_score),
+                                    _ptr(area), C.c_void_p(stream or 0)))
+
+
+def partition_path_batch(cfg, geo, owner, pose, goal_cell, path, length=None, device=0, stream=None):
+    """eea_partition_path_batch: path float64 [P][n_steps][3] = robot q's way from its own cell to goal_cell[q] inside its own
+    region of owner (way-points as geodesic_path_batch's, headings of the forward moves), padded with the last one; length: int32
+    [P] (moves written, -1: no such way) or None.  Device tensors; asynchronous"""
+    check(lib().eea_partition_path_batch(device, C.byref(cfg), _ptr(geo), _ptr(owner), _ptr(pose), int(pose.shape[0]),
+                                         _ptr(goal_cell), int(path.shape[1]), _ptr(path), _ptr(length), C.c_void_p(stream or 0)))
 
 
 def footprint_radii(fp):

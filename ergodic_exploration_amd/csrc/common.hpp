@@ -541,6 +541,27 @@ template <typename R>
 hipError_t launch_reachable_values(const CollisionParams& c, int kind, const void* d_field, unsigned stride, const int8_t* d_known,
                                    const int* d_geo, double floor, R* d_values, hipStream_t s);
 
+// ---- geodesic partition: the field with the label of the cheapest source per cell, goals and paths (partition_kernel.hip) ----
+// the workspace holds a 64-bit key per cell beside the geodesic field's planes; d_ws is 8-byte aligned
+size_t partition_ws_bytes(unsigned xsize, unsigned ysize);
+// traversability plane, key plane (all ones, or with keep_field rebuilt from d_geo / d_owner), tile flags and round words into
+// d_ws, the sources seeded with their labels, d_state = {0, 0, accepted sources, 0}: the state before round 0
+hipError_t launch_partition_begin(const CollisionParams& c, const GeodesicArgs& a, const int8_t* d_grid, const int* d_sq,
+                                  const double* d_pose, const int* d_cells, const int* d_geo, const int* d_owner, void* d_ws,
+                                  unsigned* d_state, hipStream_t s);
+// rounds first .. first + count - 1, one launch each, d_state[0] / [1] brought up to date, the key plane unpacked into d_geo /
+// d_owner
+hipError_t launch_partition_rounds(const CollisionParams& c, unsigned first, unsigned count, int* d_geo, int* d_owner, void* d_ws,
+                                   unsigned* d_state, hipStream_t s);
+// per label < n_labels: d_area, and the candidate of the greatest score w_field * field - w_cost * geo (lowest index on a tie)
+// into d_goal_cell / d_goal_score; kind 0: d_field is uint32, 1: double
+hipError_t launch_partition_goals(const CollisionParams& c, int kind, const void* d_field, unsigned stride, const int8_t* d_known,
+                                  const int* d_geo, const int* d_owner, unsigned n_labels, double w_field, double w_cost,
+                                  int* d_goal_cell, double* d_goal_score, unsigned* d_area, hipStream_t s);
+// d_path [P][n_steps][3], d_len [P] (may be null): robot q's way from its own cell to d_goal_cell[q] inside its region
+hipError_t launch_partition_path(const CollisionParams& c, const int* d_geo, const int* d_owner, const double* d_pose, unsigned P,
+                                 const int* d_goal_cell, unsigned n_steps, double* d_path, int* d_len, hipStream_t s);
+
 // ======================================================================================
 // device helpers
 // ======================================================================================

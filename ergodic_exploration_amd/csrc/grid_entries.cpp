@@ -1,5 +1,5 @@
 // C ABI (include/ergodic_amd.h) of the entries that take a device or a layer and no engine: collision, clearance and distance
-// queries, the geodesic field and its paths, the footprint and its planning entries, the range sensor, the census, the evidence grid, the gain and mutual-information fields, and the two layers with their
+// queries, the geodesic field and its paths, the geodesic partition with its goals and paths, the footprint and its planning entries, the range sensor, the census, the evidence grid, the gain and mutual-information fields, and the two layers with their
 // batch entries.  Argument checking (entry_util.hpp) and kernel dispatch; every refusal comes before the device is selected.
 #include "../../include/ergodic_amd.h"
 
@@ -218,6 +218,103 @@ eea_status eea_geodesic_path_batch(int device, const eea_collision_cfg* cfg, con
   if (P == 0u) return EEA_OK;
   EEA_HIP(hipSetDevice(device));
   EEA_HIP(eea::launch_geodesic_path(grid_params(cfg), d_geo, d_pose, P, n_steps, d_path, d_len, static_cast<hipStream_t>(stream)));
+  return EEA_OK;
+}
+
+// ---- geodesic partition: each source's share of free space, its goal and the way there (partition_kernel.hip) ----
+eea_status eea_partition_ws_bytes(const eea_collision_cfg* cfg, size_t* bytes)
+{
+  const eea_status st = geodesic_cfg_refusal(cfg);
+  if (st != EEA_OK) return st;
+  if (bytes == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  *bytes = eea::partition_ws_bytes(cfg->xsize, cfg->ysize);
+  return EEA_OK;
+}
+
+eea_status eea_geodesic_partition(int device, const eea_collision_cfg* cfg, const int8_t* d_grid, const int* d_sq, int clear_sq,
+                                  unsigned flags, const double* d_pose, unsigned P, const int* d_cells, unsigned n_cells,
+                                  unsigned max_rounds, int* d_geo, int* d_owner, void* d_ws, unsigned* d_state, void* stream)
+{
+  // eea_geodesic_field's refusals in its order, then the label plane's
+  const eea_status st = geodesic_cfg_refusal(cfg);
+  if (st != EEA_OK) return st;
+  if (d_grid == nullptr || d_geo == nullptr || d_owner == nullptr || d_ws == nullptr || d_state == nullptr) {
+    return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  }
+  if ((flags & ~static_cast<unsigned>(EEA_GEODESIC_UNKNOWN_BLOCKS | EEA_GEODESIC_CONTINUE)) != 0u) {
+    return fail(EEA_ERR_INVALID_ARGUMENT, "unknown flag bits");
+  }
+  if (clear_sq < 0) return fail(EEA_ERR_INVALID_ARGUMENT, "clear_sq must be >= 0");
+  if (reinterpret_cast<uintptr_t>(d_ws) % 8u != 0u) return fail(EEA_ERR_INVALID_ARGUMENT, "d_ws must be 8-byte aligned");
+  eea::GeodesicArgs a;
+  a.clear_sq = clear_sq;
+  a.unknown_blocks = (flags & EEA_GEODESIC_UNKNOWN_BLOCKS) != 0u;
+  a.keep_field = (flags & EEA_GEODESIC_CONTINUE) != 0u;
+  a.P = d_pose != nullptr ? P : 0u;
+  a.n_cells = d_cells != nullptr ? n_cells : 0u;
+  if (a.P == 0u && a.n_cells == 0u && !a.keep_field) return fail(EEA_ERR_INVALID_ARGUMENT, "the geodesic partition needs a source list");
+  if (static_cast<unsigned long long>(a.P) + a.n_cells > 0x7fffffffull) {
+    return fail(EEA_ERR_UNSUPPORTED, "more than 2^31 - 1 sources: a label is a non-negative int");
+  }
+  const eea::CollisionParams c = grid_params(cfg);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  EEA_HIP(hipSetDevice(device));
+  EEA_HIP(eea::launch_partition_begin(c, a, d_grid, d_sq, d_pose, d_cells, d_geo, d_owner, d_ws, d_state, s));
+  if (max_rounds != 0u) {
+    EEA_HIP(eea::launch_partition_rounds(c, 0u, max_rounds, d_geo, d_owner, d_ws, d_state, s));
+    return EEA_OK;
+  }
+  // the waiting form, as eea_geodesic_field's: a round that is not the last lowers a key, and a key takes finitely many values
+  // (the planes are unpacked behind every batch, so the look that finds the field final finds them written)
+  const unsigned long long cap = static_cast<unsigned long long>(c.xsize) * c.ysize + eea::kGeodesicBatch;
+  for (unsigned long long first = 0; first < cap; first += eea::kGeodesicBatch) {
+    unsigned final_field = 0u;
+    EEA_HIP(eea::launch_partition_rounds(c, static_cast<unsigned>(first), eea::kGeodesicBatch, d_geo, d_owner, d_ws, d_state, s));
+    EEA_HIP(hipMemcpyAsync(&final_field, d_state, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    EEA_HIP(hipStreamSynchronize(s));
+    if (final_field != 0u) return EEA_OK;
+  }
+  return fail(EEA_ERR_HIP, "eea_geodesic_partition: the rounds did not reach a fixed point");
+}
+
+eea_status eea_partition_goals(int device, const eea_collision_cfg* cfg, int kind, const void* d_field, unsigned stride,
+                               const int8_t* d_known, const int* d_geo, const int* d_owner, unsigned n_labels, double w_field,
+                               double w_cost, int* d_goal_cell, double* d_goal_score, unsigned* d_area, void* stream)
+{
+  if (cfg == nullptr || d_field == nullptr || d_known == nullptr || d_geo == nullptr || d_owner == nullptr || d_goal_cell == nullptr ||
+      d_goal_score == nullptr || d_area == nullptr) {
+    return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  }
+  const eea_status st = geodesic_cfg_refusal(cfg);
+  if (st != EEA_OK) return st;
+  if (kind != 0 && kind != 1) return fail(EEA_ERR_INVALID_ARGUMENT, "kind must be 0 (gain field) or 1 (mutual-information field)");
+  if (stride == 0) return fail(EEA_ERR_INVALID_ARGUMENT, "stride must be positive");
+  // (the comparisons are false for a NaN; the cap keeps a score of a finite field finite)
+  if (!(w_field >= 0.0 && w_field <= 1e30) || !(w_cost >= 0.0 && w_cost <= 1e30)) {
+    return fail(EEA_ERR_INVALID_ARGUMENT, "a weight must be finite and within [0, 1e30]");
+  }
+  if (n_labels == 0u) return EEA_OK;
+  EEA_HIP(hipSetDevice(device));
+  EEA_HIP(eea::launch_partition_goals(grid_params(cfg), kind, d_field, stride, d_known, d_geo, d_owner, n_labels, w_field, w_cost,
+                                      d_goal_cell, d_goal_score, d_area, static_cast<hipStream_t>(stream)));
+  return EEA_OK;
+}
+
+eea_status eea_partition_path_batch(int device, const eea_collision_cfg* cfg, const int* d_geo, const int* d_owner,
+                                    const double* d_pose, unsigned P, const int* d_goal_cell, unsigned n_steps, double* d_path,
+                                    int* d_len, void* stream)
+{
+  const eea_status st = geodesic_cfg_refusal(cfg);
+  if (st != EEA_OK) return st;
+  if (d_geo == nullptr || d_owner == nullptr || d_pose == nullptr || d_goal_cell == nullptr || d_path == nullptr) {
+    return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  }
+  if (n_steps == 0u) return fail(EEA_ERR_INVALID_ARGUMENT, "n_steps must be positive");
+  if (P > 0x7fffffffu) return fail(EEA_ERR_UNSUPPORTED, "more than 2^31 - 1 robots: a label is a non-negative int");
+  if (P == 0u) return EEA_OK;
+  EEA_HIP(hipSetDevice(device));
+  EEA_HIP(eea::launch_partition_path(grid_params(cfg), d_geo, d_owner, d_pose, P, d_goal_cell, n_steps, d_path, d_len,
+                                     static_cast<hipStream_t>(stream)));
   return EEA_OK;
 }
 

@@ -1104,6 +1104,77 @@ eea_status eea_geodesic_path_batch(int device, const eea_collision_cfg* cfg, con
 eea_status eea_set_target_reachable(eea_engine* e, const eea_collision_cfg* cfg, int kind, const void* d_field, unsigned stride,
                                     const int8_t* d_known, const int* d_geo, double floor, double lx, double ly, void* stream);
 
+/* ---- geodesic partition: each robot's share of free space, its goal and the way there (additive to ABI 6: detect these
+ * entries by symbol) -------------------------------------------------------------------------------------------------------
+ * No reference counterpart.  eea_geodesic_field says how far a cell is from the nearest source; these say WHICH source that is
+ * (the geodesic Voronoi partition of free space), pick per source the best cell of its own region under a score, and walk from
+ * a robot to its own goal -- from one build, where one field per robot would need B.  Integers and fixed-order fp64 with a
+ * unique answer: bit-reproducible.
+ * eea_geodesic_partition: the grid, the traversable set, the moves, the accepted sources with their waived tests, d_state,
+ *   the two forms of max_rounds, the limits and the refusals are eea_geodesic_field's.  In addition:
+ *   labels        the label of a source is its index in the concatenated list: pose q has label q, cell k has label P + k.
+ *                 Entries that are not accepted keep their index and own nothing.
+ *   key           every cell carries the pair (cost, label) under lexicographic order: an accepted source's cell holds
+ *                 (0, the smallest label accepted there), every other traversable cell the least of (neighbour's cost + move
+ *                 cost, neighbour's label) over the legal moves into it.  Adding a positive cost is monotone for this order, so
+ *                 the fixed point is unique: min over sources s of (d_s(cell), s).
+ *   outputs       d_geo (int32 [ysize][xsize]) is BITWISE what eea_geodesic_field writes for the same arguments; d_owner (int32
+ *                 [ysize][xsize]) is the smallest label among the sources at that cost, -1 exactly where d_geo is -1.  EVERY
+ *                 element of both planes is overwritten.
+ *   The build is eea_geodesic_field's (tiles of EEA_GEODESIC_TILE_X x EEA_GEODESIC_TILE_Y cells, rounds of one launch each,
+ *   nothing waits inside a kernel) on one 64-bit word per cell, cost in the high half and label in the low half, kept in d_ws and
+ *   read and written whole, so that no reader can pair a new cost with an old label; a last launch unpacks it into the planes.
+ *   A budgeted call that is not final leaves, per cell, -1 / -1 or the cost and label of a real move sequence (the cost >= the
+ *   final one and >= that label's single-source cost); no cell that is finally -1 holds anything else.
+ *   EEA_GEODESIC_CONTINUE: the words are rebuilt from d_geo / d_owner as they stand -- valid when both come from a call with
+ *   the same source lists and the same or a smaller traversable set --; the call ends at the bits of a fresh call.
+ *   eea_partition_ws_bytes: host only; the bytes d_ws must hold (positive, monotone in the grid's size).  d_ws is device memory
+ *   aligned to 8 bytes; its contents mean nothing between calls.
+ *   EEA_ERR_INVALID_ARGUMENT besides eea_geodesic_field's: d_owner null; d_ws not 8-byte aligned.  EEA_ERR_UNSUPPORTED besides
+ *   its limits: P + n_cells > 2^31 - 1.
+ * eea_partition_goals: kind 0: d_field is the uint32 field of eea_sense_gain_field; kind 1: the double field of
+ *   eea_sense_mi_field (finite).  Per label r < n_labels:
+ *   d_area[r]        (uint32) the number of cells with owner r.
+ *   candidate        a cell with owner r, both indices multiples of stride, whose cell of d_known does not block, and whose
+ *                    field value is > 0.
+ *   score            w_field * (double)field - w_cost * (double)geo: both products rounded on their own, then subtracted, in
+ *                    fp64 with no contraction.
+ *   d_goal_cell[r]   (int32) the row-major index of the candidate with the greatest score, the lowest index on a tie; -1: r has
+ *                    no candidate.
+ *   d_goal_score[r]  (double) that score; 0.0 when there is no candidate.
+ *   Owners < 0 or >= n_labels are ignored.  Max and min are exact and commutative: the answer does not depend on the schedule.
+ *   No workspace (d_goal_score's own 8 bytes hold an order-preserving integer of the score during the call); asynchronous on
+ *   `stream`: nothing is allocated, waited for or read on the host.  n_labels == 0 is EEA_OK and touches nothing.
+ *   Before the device is selected -- EEA_ERR_INVALID_ARGUMENT: cfg, d_field, d_known, d_geo, d_owner, d_goal_cell, d_goal_score
+ *   or d_area null; kind outside {0, 1}; stride == 0; a weight that is not finite or outside [0, 1e30] (the cap keeps a score
+ *   finite); the configuration errors of the geodesic calls.  EEA_ERR_UNSUPPORTED: their limits.
+ * eea_partition_path_batch: eea_geodesic_path_batch walks towards the NEAREST source; here robot q (pose q of d_pose [P][3],
+ *   label q) gets the path from its own cell to ITS goal g = d_goal_cell[q], in the same layout d_path [P][n_steps][3], d_len
+ *   [P] (may be NULL).  If g < 0, g is off the grid, d_owner[g] != q, d_geo[g] < 0 or the pose is off the grid: len = -1 and all
+ *   rows hold the pose.  Otherwise descend from g: among the eight moves in eea_geodesic_path_batch's order take the first whose
+ *   target n has geo[n] + cost == geo[c] and owner[n] == owner[c] (for a diagonal both passed-between cells must have geo >= 0),
+ *   until geo == 0.  The owner condition is needed: at a tie cell the cost-only rule can step into a neighbour's region and end
+ *   on the wrong robot; in a final field the constrained step always exists and the walk ends on q's own cell.  (A walk that
+ *   finds no step or ends elsewhere -- planes that are not final, or not of these poses -- gives len = -1 and the pose, too.)
+ *   The cells reversed are c_0 (the robot's cell) .. c_m = g: row k < min(m, n_steps) holds the centre of c_{k+1} by
+ *   grid2World's arithmetic with the heading of the FORWARD move c_k -> c_{k+1}, one of the same eight literals (the opposite
+ *   of the descent's move index: 0 <-> 2, 1 <-> 3, 4 <-> 6, 5 <-> 7).  Rows past the end repeat the last way-point -- before
+ *   any way-point: the centre of the robot's own cell with the pose's heading, so m = 0 gives len 0.  len = the number of moves
+ *   written, <= n_steps.  One lane per robot (it walks once to count m, once more to write the rows); asynchronous on `stream`.
+ *   P == 0 is EEA_OK.  Refusals: eea_geodesic_path_batch's, EEA_ERR_INVALID_ARGUMENT for d_owner or d_goal_cell null, and
+ *   EEA_ERR_UNSUPPORTED for P > 2^31 - 1 (a label is a non-negative int).
+ * eea_abi_version() stays 6. */
+eea_status eea_partition_ws_bytes(const eea_collision_cfg* cfg, size_t* bytes);
+eea_status eea_geodesic_partition(int device, const eea_collision_cfg* cfg, const int8_t* d_grid, const int* d_sq, int clear_sq,
+                                  unsigned flags, const double* d_pose, unsigned P, const int* d_cells, unsigned n_cells,
+                                  unsigned max_rounds, int* d_geo, int* d_owner, void* d_ws, unsigned* d_state, void* stream);
+eea_status eea_partition_goals(int device, const eea_collision_cfg* cfg, int kind, const void* d_field, unsigned stride,
+                               const int8_t* d_known, const int* d_geo, const int* d_owner, unsigned n_labels, double w_field,
+                               double w_cost, int* d_goal_cell, double* d_goal_score, unsigned* d_area, void* stream);
+eea_status eea_partition_path_batch(int device, const eea_collision_cfg* cfg, const int* d_geo, const int* d_owner,
+                                    const double* d_pose, unsigned P, const int* d_goal_cell, unsigned n_steps, double* d_path,
+                                    int* d_len, void* stream);
+
 /* ---- footprint collision: a convex polygon base, checked through the distance field ----------------------------------
  * No reference counterpart (the reference README lists "model the robot's base as a polygon for collision detection" and "use
  * a distance field for detecting obstacle cells" under "Future Improvements").  Every other collision call treats the robot
