@@ -11,6 +11,56 @@
 
 using namespace eea;
 
+// ---- what eea_geodesic_field and eea_geodesic_partition share (a template has no C linkage: ahead of the entries) ----
+namespace
+{
+// the refusals of a build in their order, before the device is selected, and what the kernels read of the arguments;
+// any_null: one of the entry's own buffers is missing; misaligned, no_source: the entry's own messages
+eea_status geodesic_build_args(const eea_collision_cfg* cfg, bool any_null, int clear_sq, unsigned flags, const void* d_ws,
+                               unsigned ws_align, const char* misaligned, const double* d_pose, unsigned P, const int* d_cells,
+                               unsigned n_cells, const char* no_source, eea::GeodesicArgs& a)
+{
+  const eea_status st = geodesic_cfg_refusal(cfg);
+  if (st != EEA_OK) return st;
+  if (any_null) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  if ((flags & ~static_cast<unsigned>(EEA_GEODESIC_UNKNOWN_BLOCKS | EEA_GEODESIC_CONTINUE)) != 0u) {
+    return fail(EEA_ERR_INVALID_ARGUMENT, "unknown flag bits");
+  }
+  if (clear_sq < 0) return fail(EEA_ERR_INVALID_ARGUMENT, "clear_sq must be >= 0");
+  if (reinterpret_cast<uintptr_t>(d_ws) % ws_align != 0u) return fail(EEA_ERR_INVALID_ARGUMENT, misaligned);
+  a.clear_sq = clear_sq;
+  a.unknown_blocks = (flags & EEA_GEODESIC_UNKNOWN_BLOCKS) != 0u;
+  a.keep_field = (flags & EEA_GEODESIC_CONTINUE) != 0u;
+  a.P = d_pose != nullptr ? P : 0u;
+  a.n_cells = d_cells != nullptr ? n_cells : 0u;
+  if (a.P == 0u && a.n_cells == 0u && !a.keep_field) return fail(EEA_ERR_INVALID_ARGUMENT, no_source);
+  return EEA_OK;
+}
+
+// the rounds behind a begin; launch_rounds(first, count) enqueues rounds first .. first + count - 1 with what follows them.
+// A budget is enqueued whole.  The waiting form (max_rounds == 0) looks at d_state[0] behind every batch of rounds: a round
+// that is not the last lowers a cell, and a cell takes finitely many values, so the cap below is never met by a build that
+// converges as it must; no_fixed_point: the entry's message if it is
+template <typename LaunchRounds>
+eea_status geodesic_run_rounds(const eea::CollisionParams& c, unsigned max_rounds, const unsigned* d_state, hipStream_t s,
+                               const char* no_fixed_point, LaunchRounds launch_rounds)
+{
+  if (max_rounds != 0u) {
+    EEA_HIP(launch_rounds(0u, max_rounds));
+    return EEA_OK;
+  }
+  const unsigned long long cap = static_cast<unsigned long long>(c.xsize) * c.ysize + eea::kGeodesicBatch;
+  for (unsigned long long first = 0; first < cap; first += eea::kGeodesicBatch) {
+    unsigned final_field = 0u;
+    EEA_HIP(launch_rounds(static_cast<unsigned>(first), eea::kGeodesicBatch));
+    EEA_HIP(hipMemcpyAsync(&final_field, d_state, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    EEA_HIP(hipStreamSynchronize(s));
+    if (final_field != 0u) return EEA_OK;
+  }
+  return fail(EEA_ERR_HIP, no_fixed_point);
+}
+}  // namespace
+
 extern "C" {
 
 // ---- collision lookups ---------------------------------------------------------------------
@@ -172,40 +222,19 @@ eea_status eea_geodesic_field(int device, const eea_collision_cfg* cfg, const in
                               unsigned flags, const double* d_pose, unsigned P, const int* d_cells, unsigned n_cells,
                               unsigned max_rounds, int* d_geo, void* d_ws, unsigned* d_state, void* stream)
 {
-  const eea_status st = geodesic_cfg_refusal(cfg);
-  if (st != EEA_OK) return st;
-  if (d_grid == nullptr || d_geo == nullptr || d_ws == nullptr || d_state == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
-  if ((flags & ~static_cast<unsigned>(EEA_GEODESIC_UNKNOWN_BLOCKS | EEA_GEODESIC_CONTINUE)) != 0u) {
-    return fail(EEA_ERR_INVALID_ARGUMENT, "unknown flag bits");
-  }
-  if (clear_sq < 0) return fail(EEA_ERR_INVALID_ARGUMENT, "clear_sq must be >= 0");
-  if (reinterpret_cast<uintptr_t>(d_ws) % 4u != 0u) return fail(EEA_ERR_INVALID_ARGUMENT, "d_ws must be 4-byte aligned");
   eea::GeodesicArgs a;
-  a.clear_sq = clear_sq;
-  a.unknown_blocks = (flags & EEA_GEODESIC_UNKNOWN_BLOCKS) != 0u;
-  a.keep_field = (flags & EEA_GEODESIC_CONTINUE) != 0u;
-  a.P = d_pose != nullptr ? P : 0u;
-  a.n_cells = d_cells != nullptr ? n_cells : 0u;
-  if (a.P == 0u && a.n_cells == 0u && !a.keep_field) return fail(EEA_ERR_INVALID_ARGUMENT, "the geodesic field needs a source list");
+  const eea_status st = geodesic_build_args(cfg, d_grid == nullptr || d_geo == nullptr || d_ws == nullptr || d_state == nullptr,
+                                            clear_sq, flags, d_ws, 4u, "d_ws must be 4-byte aligned", d_pose, P, d_cells, n_cells,
+                                            "the geodesic field needs a source list", a);
+  if (st != EEA_OK) return st;
   const eea::CollisionParams c = grid_params(cfg);
   hipStream_t s = static_cast<hipStream_t>(stream);
   EEA_HIP(hipSetDevice(device));
   EEA_HIP(eea::launch_geodesic_begin(c, a, d_grid, d_sq, d_pose, d_cells, d_geo, d_ws, d_state, s));
-  if (max_rounds != 0u) {
-    EEA_HIP(eea::launch_geodesic_rounds(c, 0u, max_rounds, d_geo, d_ws, d_state, s));
-    return EEA_OK;
-  }
-  // the waiting form: a look at d_state[0] behind every batch of rounds.  A round that is not the last lowers a cell, and a
-  // cell takes finitely many values: the cap below is never met by a field that converges as it must
-  const unsigned long long cap = static_cast<unsigned long long>(c.xsize) * c.ysize + eea::kGeodesicBatch;
-  for (unsigned long long first = 0; first < cap; first += eea::kGeodesicBatch) {
-    unsigned final_field = 0u;
-    EEA_HIP(eea::launch_geodesic_rounds(c, static_cast<unsigned>(first), eea::kGeodesicBatch, d_geo, d_ws, d_state, s));
-    EEA_HIP(hipMemcpyAsync(&final_field, d_state, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-    EEA_HIP(hipStreamSynchronize(s));
-    if (final_field != 0u) return EEA_OK;
-  }
-  return fail(EEA_ERR_HIP, "eea_geodesic_field: the rounds did not reach a fixed point");
+  return geodesic_run_rounds(c, max_rounds, d_state, s, "eea_geodesic_field: the rounds did not reach a fixed point",
+                             [&](unsigned first, unsigned count) {
+                               return eea::launch_geodesic_rounds(c, first, count, d_geo, d_ws, d_state, s);
+                             });
 }
 
 eea_status eea_geodesic_path_batch(int device, const eea_collision_cfg* cfg, const int* d_geo, const double* d_pose, unsigned P,
@@ -236,23 +265,11 @@ eea_status eea_geodesic_partition(int device, const eea_collision_cfg* cfg, cons
                                   unsigned max_rounds, int* d_geo, int* d_owner, void* d_ws, unsigned* d_state, void* stream)
 {
   // eea_geodesic_field's refusals in its order, then the label plane's
-  const eea_status st = geodesic_cfg_refusal(cfg);
-  if (st != EEA_OK) return st;
-  if (d_grid == nullptr || d_geo == nullptr || d_owner == nullptr || d_ws == nullptr || d_state == nullptr) {
-    return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
-  }
-  if ((flags & ~static_cast<unsigned>(EEA_GEODESIC_UNKNOWN_BLOCKS | EEA_GEODESIC_CONTINUE)) != 0u) {
-    return fail(EEA_ERR_INVALID_ARGUMENT, "unknown flag bits");
-  }
-  if (clear_sq < 0) return fail(EEA_ERR_INVALID_ARGUMENT, "clear_sq must be >= 0");
-  if (reinterpret_cast<uintptr_t>(d_ws) % 8u != 0u) return fail(EEA_ERR_INVALID_ARGUMENT, "d_ws must be 8-byte aligned");
   eea::GeodesicArgs a;
-  a.clear_sq = clear_sq;
-  a.unknown_blocks = (flags & EEA_GEODESIC_UNKNOWN_BLOCKS) != 0u;
-  a.keep_field = (flags & EEA_GEODESIC_CONTINUE) != 0u;
-  a.P = d_pose != nullptr ? P : 0u;
-  a.n_cells = d_cells != nullptr ? n_cells : 0u;
-  if (a.P == 0u && a.n_cells == 0u && !a.keep_field) return fail(EEA_ERR_INVALID_ARGUMENT, "the geodesic partition needs a source list");
+  const eea_status st = geodesic_build_args(
+      cfg, d_grid == nullptr || d_geo == nullptr || d_owner == nullptr || d_ws == nullptr || d_state == nullptr, clear_sq, flags, d_ws, 8u,
+      "d_ws must be 8-byte aligned", d_pose, P, d_cells, n_cells, "the geodesic partition needs a source list", a);
+  if (st != EEA_OK) return st;
   if (static_cast<unsigned long long>(a.P) + a.n_cells > 0x7fffffffull) {
     return fail(EEA_ERR_UNSUPPORTED, "more than 2^31 - 1 sources: a label is a non-negative int");
   }
@@ -260,21 +277,11 @@ eea_status eea_geodesic_partition(int device, const eea_collision_cfg* cfg, cons
   hipStream_t s = static_cast<hipStream_t>(stream);
   EEA_HIP(hipSetDevice(device));
   EEA_HIP(eea::launch_partition_begin(c, a, d_grid, d_sq, d_pose, d_cells, d_geo, d_owner, d_ws, d_state, s));
-  if (max_rounds != 0u) {
-    EEA_HIP(eea::launch_partition_rounds(c, 0u, max_rounds, d_geo, d_owner, d_ws, d_state, s));
-    return EEA_OK;
-  }
-  // the waiting form, as eea_geodesic_field's: a round that is not the last lowers a key, and a key takes finitely many values
   // (the planes are unpacked behind every batch, so the look that finds the field final finds them written)
-  const unsigned long long cap = static_cast<unsigned long long>(c.xsize) * c.ysize + eea::kGeodesicBatch;
-  for (unsigned long long first = 0; first < cap; first += eea::kGeodesicBatch) {
-    unsigned final_field = 0u;
-    EEA_HIP(eea::launch_partition_rounds(c, static_cast<unsigned>(first), eea::kGeodesicBatch, d_geo, d_owner, d_ws, d_state, s));
-    EEA_HIP(hipMemcpyAsync(&final_field, d_state, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-    EEA_HIP(hipStreamSynchronize(s));
-    if (final_field != 0u) return EEA_OK;
-  }
-  return fail(EEA_ERR_HIP, "eea_geodesic_partition: the rounds did not reach a fixed point");
+  return geodesic_run_rounds(c, max_rounds, d_state, s, "eea_geodesic_partition: the rounds did not reach a fixed point",
+                             [&](unsigned first, unsigned count) {
+                               return eea::launch_partition_rounds(c, first, count, d_geo, d_owner, d_ws, d_state, s);
+                             });
 }
 
 eea_status eea_partition_goals(int device, const eea_collision_cfg* cfg, int kind, const void* d_field, unsigned stride,

@@ -6,15 +6,7 @@
 //  - a cell carries ONE 64-bit key, cost << 32 | label, all ones for "none", in a key plane in the workspace.  Keys are ordered
 //    as unsigned integers, which is the lexicographic order of (cost, label); a move adds cost << 32 and keeps the label, which
 //    is monotone, so "no cell can be lowered" has one fixed point: min over sources s of (d_s(cell), s).
-//  - the schedule is geodesic_kernel.hip's, on keys: begin (the traversability plane, the key plane, the tile flags and round
-//    words; then one lane per source, a 64-bit atomicMin of its label into its cell), one launch per round with a workgroup per
-//    tile of 32 x 32 cells relaxed in LDS to its own fixed point, two flag planes, three rotating round words, a closing launch.
-//    Kernel boundaries are the only synchronisation between workgroups; nothing waits.
-//  - the halo is read while the neighbour may be storing.  A reader must never pair a new cost with an old label: that key would
-//    be lower than any real one and, since keys only go down, would stick.  So a key is one aligned 8-byte word, every load of
-//    the plane in a round and every store to it is a relaxed agent-scope 64-bit atomic, and in LDS a key is read and written
-//    whole.  A reader then sees an older or a newer key of the cell, each the cost and label of a real move sequence, and the
-//    neighbour's mark makes the tile run again behind the next kernel boundary.
+//  - the build is geodesic_tile.hpp's rounds on keys (KeyCell); a source takes a 64-bit atomicMin of its label into its cell.
 //  - a last launch unpacks the plane into d_geo / d_owner, after a budget has run out as well.
 //  - goals: an init launch, a pass that adds the areas and takes the 64-bit atomicMax of an order-preserving key of the score
 //    per label (kept in d_goal_score's own 8 bytes), a pass that takes the atomicMin of the cell index over the cells whose key
@@ -29,217 +21,65 @@
 
 #include "../../include/ergodic_amd.h"
 #include "common.hpp"
-#include "grid_cell.hpp"  // world_to_grid (grid.cpp:143-159), occupied
+#include "geodesic_tile.hpp"
 
 namespace eea
 {
 namespace
 {
-using u64 = unsigned long long;
-constexpr u64 kNone = ~0ull;  // no move sequence known
-constexpr int kTX = static_cast<int>(kGeodesicTileX), kTY = static_cast<int>(kGeodesicTileY);
-constexpr int kPitch = kTX + 2;                      // a staged row: the tile and its halo
-constexpr int kPerThread = kTX * kTY / kBlock;       // cells of a tile per thread
-constexpr int kRowStep = kBlock / kTX;               // rows between a thread's cells
-static_assert(kBlock % kTX == 0 && (kTX * kTY) % kBlock == 0, "a thread owns whole cells of one column");
+using u64 = KeyCell::T;
+constexpr u64 kNone = KeyCell::kNone;
 
-// the workspace: the key plane (8-byte aligned), the traversability plane, then two planes of tile flags and the round words
+// the workspace: the key plane (8-byte aligned), then the field's workspace
 struct PartitionWs
 {
-  u64* key;             // [ysize][xsize]
-  unsigned char* trav;  // [ysize][xsize]
-  unsigned* flags;      // [2][tiles]
-  unsigned* pend;       // [3]
-  unsigned* chg;        // [3]
-  unsigned tiles_x, tiles_y;
+  u64* key;  // [ysize][xsize]
+  GeodesicWs tile;
 };
-__host__ __device__ inline size_t trav_bytes(unsigned xsize, unsigned ysize)
-{
-  return (static_cast<size_t>(xsize) * ysize + 255u) / 256u * 256u;
-}
 inline PartitionWs workspace(const CollisionParams& c, void* d_ws)
 {
-  PartitionWs w;
-  w.tiles_x = (c.xsize - 1u) / kGeodesicTileX + 1u;
-  w.tiles_y = (c.ysize - 1u) / kGeodesicTileY + 1u;
-  w.key = static_cast<u64*>(d_ws);
-  w.trav = reinterpret_cast<unsigned char*>(w.key + static_cast<size_t>(c.xsize) * c.ysize);
-  w.flags = reinterpret_cast<unsigned*>(w.trav + trav_bytes(c.xsize, c.ysize));
-  w.pend = w.flags + 2u * static_cast<size_t>(w.tiles_x) * w.tiles_y;
-  w.chg = w.pend + 3;
-  return w;
+  u64* const key = static_cast<u64*>(d_ws);
+  return PartitionWs{ key, tile_workspace(c.xsize, c.ysize, key + static_cast<size_t>(c.xsize) * c.ysize) };
 }
-
-__device__ __forceinline__ u64 load_key(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void store_key(u64* p, u64 v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 __global__ __launch_bounds__(kBlock) void partition_init_kernel(const CollisionParams c, const PartitionWs w, const GeodesicArgs a,
                                                                const int8_t* __restrict__ grid, const int* __restrict__ sq,
                                                                const int* __restrict__ geo, const int* __restrict__ owner,
                                                                unsigned* __restrict__ state)
 {
-  const size_t cells = static_cast<size_t>(c.xsize) * c.ysize, tiles = static_cast<size_t>(w.tiles_x) * w.tiles_y;
+  const size_t cells = static_cast<size_t>(c.xsize) * c.ysize;
   const size_t n = static_cast<size_t>(gridDim.x) * kBlock, t0 = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
   for (size_t g = t0; g < cells; g += n) {
-    const int8_t v = grid[g];
-    bool ok = !occupied(c, v) && !(a.unknown_blocks && v < 0);
-    if (ok && sq != nullptr) {
-      const int d = sq[g];
-      ok = d == -1 || d > a.clear_sq;
-    }
-    w.trav[g] = ok ? 1 : 0;
+    w.tile.trav[g] = traversable(c, a, grid[g], sq, g) ? 1 : 0;
     u64 k = kNone;
     if (a.keep_field) {  // the planes as they stand
       const int d = geo[g];
       if (d >= 0) k = static_cast<u64>(static_cast<unsigned>(d)) << 32 | static_cast<unsigned>(owner[g]);
     }
-    store_key(&w.key[g], k);
+    KeyCell::store(&w.key[g], k);
   }
-  for (size_t t = t0; t < 2 * tiles; t += n) w.flags[t] = t < tiles ? 1u : 0u;
-  if (t0 < 3) {
-    w.pend[t0] = 0u;
-    w.chg[t0] = 0u;
-  }
-  if (t0 < 4) state[t0] = 0u;
+  reset_rounds(w.tile, state, t0, n);
 }
 
-// one lane per source: the poses first, then the cells; its label is its index
+// one lane per source; its label is its index
 __global__ __launch_bounds__(kBlock) void partition_seed_kernel(const CollisionParams c, const PartitionWs w, const GeodesicArgs a,
                                                                const int8_t* __restrict__ grid, const double* __restrict__ pose,
                                                                const int* __restrict__ src, unsigned* __restrict__ state)
 {
   const size_t q = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
-  if (q >= static_cast<size_t>(a.P) + a.n_cells) return;
   size_t at;
-  if (q < a.P) {
-    unsigned j, i;
-    world_to_grid(c, pose[3 * q], pose[3 * q + 1], j, i);
-    if (!((i <= c.ysize - 1u) && (j <= c.xsize - 1u))) return;  // gridBounds (grid.cpp:96-100)
-    at = static_cast<size_t>(i) * c.xsize + j;
-  } else {
-    const int k = src[q - a.P];
-    if (k < 0 || static_cast<size_t>(k) >= static_cast<size_t>(c.xsize) * c.ysize) return;
-    at = static_cast<size_t>(k);
-  }
-  if (occupied(c, grid[at])) return;
+  if (q >= static_cast<size_t>(a.P) + a.n_cells || !source_cell(c, a, grid, pose, src, q, at)) return;
   atomicMin(&w.key[at], static_cast<u64>(q));  // cost 0, this label: the smallest label accepted there stays
   atomicAdd(&state[2], 1u);
-}
-
-// what block 0 does at the start of round r (and the closing launch for the round after the last): the words of round r - 1
-__device__ __forceinline__ void tally(const PartitionWs& w, unsigned* state, unsigned r)
-{
-  if (r == 0u) return;
-  const unsigned prev = (r - 1u) % 3u;
-  state[1] += w.chg[prev];
-  w.chg[prev] = 0u;
-  w.pend[prev] = 0u;
 }
 
 __global__ __launch_bounds__(kBlock) void partition_round_kernel(const PartitionWs w, unsigned xsize, unsigned ysize, unsigned r,
                                                                 unsigned* state)
 {
-  __shared__ __attribute__((aligned(8))) u64 s_key[(kTY + 2) * kPitch];
-  __shared__ unsigned char s_trav[(kTY + 2) * kPitch];
-  __shared__ unsigned s_mark;
-  const int tid = threadIdx.x;
-  const unsigned tile = blockIdx.x, tiles = w.tiles_x * w.tiles_y;
-  if (tile == 0u && tid == 0) tally(w, state, r);
-  unsigned* const mine = w.flags + static_cast<size_t>(r & 1u) * tiles;
-  unsigned* const next = w.flags + static_cast<size_t>((r + 1u) & 1u) * tiles;
-  if (mine[tile] == 0u) return;  // (uniform: every thread reads the same word)
-  __syncthreads();               // every thread has read the flag
-  if (tid == 0) mine[tile] = 0u;
-  if (tid == 0) s_mark = 0u;
-  const int tx = static_cast<int>(tile % w.tiles_x), ty = static_cast<int>(tile / w.tiles_x);
-  const long long x0 = static_cast<long long>(tx) * kTX - 1, y0 = static_cast<long long>(ty) * kTY - 1;
-  for (int k = tid; k < (kTY + 2) * kPitch; k += kBlock) {
-    const long long gy = y0 + k / kPitch, gx = x0 + k % kPitch;
-    u64 v = kNone;
-    unsigned char t = 0;
-    if (gy >= 0 && gy < static_cast<long long>(ysize) && gx >= 0 && gx < static_cast<long long>(xsize)) {
-      const size_t g = static_cast<size_t>(gy) * xsize + static_cast<size_t>(gx);
-      v = load_key(&w.key[g]);  // (the halo's cells may be stored to by their own tile in this launch: one untorn word)
-      t = w.trav[g];
-    }
-    s_key[k] = v;
-    s_trav[k] = t;
-  }
-  __syncthreads();
-  // this thread's cells: column tid % kTX, rows tid / kTX + m kRowStep
-  const int col = tid % kTX, row0 = tid / kTX;
-  u64 before[kPerThread];
-  bool open[kPerThread];  // a move may enter the cell
-#pragma unroll
-  for (int m = 0; m < kPerThread; ++m) {
-    const int at = (row0 + m * kRowStep + 1) * kPitch + col + 1;
-    before[m] = s_key[at];
-    open[m] = s_trav[at] != 0;
-  }
-  bool any = false;
-  for (;;) {
-    int changed = 0;
-#pragma unroll
-    for (int m = 0; m < kPerThread; ++m) {
-      if (!open[m]) continue;
-      const int at = (row0 + m * kRowStep + 1) * kPitch + col + 1;
-      const bool te = s_trav[at + 1] != 0, tn = s_trav[at + kPitch] != 0, tw = s_trav[at - 1] != 0, ts = s_trav[at - kPitch] != 0;
-      const u64 was = s_key[at];
-      u64 best = was;
-      // (a neighbour without a key is skipped, not added to; a cost stays below 2^31, so the sum keeps the label's half)
-      const auto take = [&](u64 v, u64 cost, bool ok) {
-        const u64 cand = v + (cost << 32);
-        best = (ok && v != kNone && cand < best) ? cand : best;
-      };
-      take(s_key[at + 1], 5u, true);
-      take(s_key[at + kPitch], 5u, true);
-      take(s_key[at - 1], 5u, true);
-      take(s_key[at - kPitch], 5u, true);
-      take(s_key[at + kPitch + 1], 7u, te && tn);
-      take(s_key[at + kPitch - 1], 7u, tw && tn);
-      take(s_key[at - kPitch - 1], 7u, tw && ts);
-      take(s_key[at - kPitch + 1], 7u, te && ts);
-      if (best < was) {
-        s_key[at] = best;  // (the cell's only writer; one 8-byte LDS store)
-        changed = 1;
-      }
-    }
-    if (__syncthreads_or(changed) == 0) break;
-    any = true;
-  }
-  if (!any) return;  // (uniform)
-  unsigned mark = 0u;  // bit k: neighbouring tile k of the list below reads a cell of this thread's that went down
-#pragma unroll
-  for (int m = 0; m < kPerThread; ++m) {
-    const int row = row0 + m * kRowStep;
-    const u64 v = s_key[(row + 1) * kPitch + col + 1];
-    if (v == before[m]) continue;
-    const long long gy = y0 + 1 + row, gx = x0 + 1 + col;  // (on the grid: an off-grid cell is not open)
-    store_key(&w.key[static_cast<size_t>(gy) * xsize + static_cast<size_t>(gx)], v);
-    const unsigned up = row == 0 ? 1u : 0u, down = row == kTY - 1 ? 1u : 0u, left = col == 0 ? 1u : 0u, right = col == kTX - 1 ? 1u : 0u;
-    mark |= up | down << 1 | left << 2 | right << 3 | (up & left) << 4 | (up & right) << 5 | (down & left) << 6 | (down & right) << 7;
-  }
-  if (mark != 0u) atomicOr(&s_mark, mark);
-  __syncthreads();
-  if (tid < 8 && ((s_mark >> tid) & 1u) != 0u) {
-    const int dy[8] = { -1, 1, 0, 0, -1, -1, 1, 1 }, dx[8] = { 0, 0, -1, 1, -1, 1, -1, 1 };
-    const int ny = ty + dy[tid], nx = tx + dx[tid];
-    if (ny >= 0 && ny < static_cast<int>(w.tiles_y) && nx >= 0 && nx < static_cast<int>(w.tiles_x)) {
-      next[static_cast<size_t>(ny) * w.tiles_x + nx] = 1u;
-      atomicOr(&w.pend[(r + 1u) % 3u], 1u);
-    }
-  }
-  if (tid == 8) atomicOr(&w.chg[r % 3u], 1u);
+  tile_round<KeyCell>(w.tile, w.key, xsize, ysize, r, state);
 }
 
-// behind round `last`: its words into d_state; final when nothing is pending for the round after it
-__global__ void partition_close_kernel(const PartitionWs w, unsigned last, unsigned* state)
-{
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  tally(w, state, last + 1u);
-  state[0] = w.pend[(last + 1u) % 3u] == 0u ? 1u : 0u;
-  state[3] = 0u;
-}
+__global__ void partition_close_kernel(const PartitionWs w, unsigned last, unsigned* state) { close_rounds(w.tile, last, state); }
 
 // the key plane into the two output planes: every element of both is written
 __global__ __launch_bounds__(kBlock) void partition_unpack_kernel(const u64* __restrict__ key, size_t cells, int* __restrict__ geo,
@@ -401,22 +241,6 @@ __global__ __launch_bounds__(kBlock) void goals_finish_kernel(unsigned n_labels,
 }
 
 // ---- the path ---------------------------------------------------------------------------------------------------------------
-// headings of the eight moves in the header's order, (di, dj) = (0,+1) (+1,0) (0,-1) (-1,0) (+1,+1) (+1,-1) (-1,-1) (-1,+1):
-// geodesic_kernel.hip's literals
-__device__ __forceinline__ double move_heading(int k)
-{
-  switch (k) {
-    case 0: return 0.0;
-    case 1: return 1.5707963267948966;
-    case 2: return -3.141592653589793;
-    case 3: return -1.5707963267948966;
-    case 4: return 0.7853981633974483;
-    case 5: return 2.356194490192345;
-    case 6: return -2.356194490192345;
-    default: return -0.7853981633974483;
-  }
-}
-
 __global__ __launch_bounds__(kBlock) void partition_path_kernel(const CollisionParams c, const int* __restrict__ geo,
                                                                const int* __restrict__ owner, const double* __restrict__ pose,
                                                                unsigned P, const int* __restrict__ goal_cell, unsigned n_steps,
@@ -426,56 +250,34 @@ __global__ __launch_bounds__(kBlock) void partition_path_kernel(const CollisionP
   if (q >= P) return;
   double wx = pose[3 * q], wy = pose[3 * q + 1], wth = pose[3 * q + 2];
   double* const out = path + q * n_steps * 3;
-  const int xs = static_cast<int>(c.xsize), ys = static_cast<int>(c.ysize);
+  const int xs = static_cast<int>(c.xsize);
   const size_t cells = static_cast<size_t>(c.xsize) * c.ysize;
   unsigned j, i;
   world_to_grid(c, wx, wy, j, i);
   const bool in_grid = (i <= c.ysize - 1u) && (j <= c.xsize - 1u);  // gridBounds (grid.cpp:96-100)
   const int goal = goal_cell[q];
   const int label = static_cast<int>(q);
-  const auto geo_at = [&](int ii, int jj) {
-    return (ii >= 0 && ii < ys && jj >= 0 && jj < xs) ? geo[static_cast<size_t>(ii) * c.xsize + static_cast<size_t>(jj)] : -1;
-  };
-  // one step of the descent from (ci, cj) inside the region: the move index, or 8 when there is none
-  const auto step = [&](int& ci, int& cj, int& here) {
-    for (int k = 0; k < 8; ++k) {
-      const int di = k < 4 ? (k == 1 ? 1 : k == 3 ? -1 : 0) : (k < 6 ? 1 : -1);
-      const int dj = k < 4 ? (k == 0 ? 1 : k == 2 ? -1 : 0) : ((k == 4 || k == 7) ? 1 : -1);
-      const int g = geo_at(ci + di, cj + dj);
-      if (g < 0 || g + (k < 4 ? 5 : 7) != here) continue;
-      if (owner[static_cast<size_t>(ci + di) * c.xsize + static_cast<size_t>(cj + dj)] != label) continue;
-      if (k >= 4 && (geo_at(ci + di, cj) < 0 || geo_at(ci, cj + dj) < 0)) continue;
-      ci += di;
-      cj += dj;
-      here = g;
-      return k;
-    }
-    return 8;
-  };
   int moves = -1;  // m: the moves from the robot's cell to the goal
   const bool walk = in_grid && goal >= 0 && static_cast<size_t>(goal) < cells && owner[goal] == label && geo[goal] >= 0;
   if (walk) {
     int ci = goal / xs, cj = goal % xs, here = geo[goal];
     moves = 0;
     while (here > 0) {
-      if (step(ci, cj, here) == 8) break;
+      if (descend<true>(c, geo, owner, label, ci, cj, here) == 8) break;  // (a step inside the region)
       ++moves;
     }
     // (in a final field the walk ends on the robot's own cell; one that does not is refused like a goal of another region)
     if (here != 0 || ci != static_cast<int>(i) || cj != static_cast<int>(j)) moves = -1;
   }
   if (moves >= 0) {
-    // grid2World's arithmetic (grid.cpp:161-175): the centre of the cell
-    const auto centre_x = [&](unsigned jj) { return static_cast<double>(jj * c.resolution) + c.resolution / 2.0 + c.xmin; };
-    const auto centre_y = [&](unsigned ii) { return static_cast<double>(ii * c.resolution) + c.resolution / 2.0 + c.ymin; };
     // before any way-point the rows hold the centre of the robot's own cell with the pose's heading
-    wx = centre_x(j);
-    wy = centre_y(i);
+    wx = centre_x(c, j);
+    wy = centre_y(c, i);
     int ci = goal / xs, cj = goal % xs, here = geo[goal];
     for (int t = 0; t < moves; ++t) {
       // the descent's move t leaves c_{m - t}: way-point m - t - 1 is that cell's centre with the heading of the move INTO it
-      const double px = centre_x(static_cast<unsigned>(cj)), py = centre_y(static_cast<unsigned>(ci));
-      const int k = step(ci, cj, here);
+      const double px = centre_x(c, static_cast<unsigned>(cj)), py = centre_y(c, static_cast<unsigned>(ci));
+      const int k = descend<true>(c, geo, owner, label, ci, cj, here);
       const double pth = move_heading((k & 4) | ((k + 2) & 3));  // the opposite move: 0 <-> 2, 1 <-> 3, 4 <-> 6, 5 <-> 7
       const unsigned row = static_cast<unsigned>(moves - t - 1);
       if (t == 0) {  // the goal: the last way-point, and what the rows past the end repeat
@@ -501,8 +303,7 @@ __global__ __launch_bounds__(kBlock) void partition_path_kernel(const CollisionP
 
 size_t partition_ws_bytes(unsigned xsize, unsigned ysize)
 {
-  const size_t tiles = static_cast<size_t>((xsize - 1u) / kGeodesicTileX + 1u) * ((ysize - 1u) / kGeodesicTileY + 1u);
-  return sizeof(u64) * static_cast<size_t>(xsize) * ysize + trav_bytes(xsize, ysize) + sizeof(unsigned) * (2 * tiles + 6);
+  return sizeof(u64) * static_cast<size_t>(xsize) * ysize + tile_workspace_bytes(xsize, ysize);
 }
 
 hipError_t launch_partition_begin(const CollisionParams& c, const GeodesicArgs& a, const int8_t* d_grid, const int* d_sq,
@@ -510,8 +311,7 @@ hipError_t launch_partition_begin(const CollisionParams& c, const GeodesicArgs& 
                                   unsigned* d_state, hipStream_t s)
 {
   const PartitionWs w = workspace(c, d_ws);
-  const size_t cells = static_cast<size_t>(c.xsize) * c.ysize;
-  const unsigned blocks = static_cast<unsigned>(cells / (4 * kBlock) < 1 ? 1 : (cells / (4 * kBlock) > 4096 ? 4096 : cells / (4 * kBlock)));
+  const unsigned blocks = cell_pass_blocks(static_cast<size_t>(c.xsize) * c.ysize);
   hipLaunchKernelGGL(partition_init_kernel, dim3(blocks), dim3(kBlock), 0, s, c, w, a, d_grid, d_sq, d_geo, d_owner, d_state);
   const size_t n_src = static_cast<size_t>(a.P) + a.n_cells;
   if (n_src != 0) {
@@ -526,12 +326,12 @@ hipError_t launch_partition_rounds(const CollisionParams& c, unsigned first, uns
 {
   const PartitionWs w = workspace(c, d_ws);
   for (unsigned r = first; r < first + count; ++r) {
-    hipLaunchKernelGGL(partition_round_kernel, dim3(w.tiles_x * w.tiles_y), dim3(kBlock), 0, s, w, c.xsize, c.ysize, r, d_state);
+    hipLaunchKernelGGL(partition_round_kernel, dim3(w.tile.tiles_x * w.tile.tiles_y), dim3(kBlock), 0, s, w, c.xsize, c.ysize, r,
+                       d_state);
   }
   hipLaunchKernelGGL(partition_close_kernel, dim3(1), dim3(64), 0, s, w, first + count - 1u, d_state);
   const size_t cells = static_cast<size_t>(c.xsize) * c.ysize;
-  const unsigned blocks = static_cast<unsigned>(cells / (4 * kBlock) < 1 ? 1 : (cells / (4 * kBlock) > 4096 ? 4096 : cells / (4 * kBlock)));
-  hipLaunchKernelGGL(partition_unpack_kernel, dim3(blocks), dim3(kBlock), 0, s, w.key, cells, d_geo, d_owner);
+  hipLaunchKernelGGL(partition_unpack_kernel, dim3(cell_pass_blocks(cells)), dim3(kBlock), 0, s, w.key, cells, d_geo, d_owner);
   return hipGetLastError();
 }
 
