@@ -1,8 +1,10 @@
 // The evidence grid of a simulated fleet (include/ergodic_amd.h, eea_sense_observe_batch / eea_evidence_publish /
 // eea_evidence_table): every robot's NOISY scan is fused into a grid of integer log-odds units, and a publication step turns
 // the evidence into the int8 occupancy probabilities 1 .. 99 the tick, the census, the gain count and the mutual information
-// read.  The sensor is the reveal's (sense_kernel.hip: the rays, the disc and grid tests, blocks(), the robot's cell, the mask,
-// all from sense_rays.hpp / grid_cell.hpp); what a ray meets is not the truth but what the robot's scan SEES of it.  This is NOT
+// read.  The sensor is the reveal's (sense_kernel.hip): the rays, the disc and grid tests, the launch block (ScanParams), the
+// robot of a workgroup's turn with the mask and the off-grid rule (robot_cell) and the march on the staged window
+// (march_window) are sense_rays.hpp's, one definition for both; what a ray meets is not the truth but what the robot's scan
+// SEES of it: this file keeps the staging (the noise) and the write-out (the atomic adds).  This is NOT
 // the reference's OccupancyMapper (mapping.cpp), whose per-update int8 round trip makes the result depend on the order of
 // every beam: it borrows its sensor-model constants and logOdds2Prob (mapping.cpp:51-54, 66-74) and nothing else.
 //
@@ -14,13 +16,13 @@
 //  - observe: the reveal's shape -- one workgroup of 256 threads per robot, the clipped (2R + 1)^2 window in LDS as one byte
 //    per cell, rows read coalesced (a lane per group of four columns; a wavefront takes a row of 64 groups, or several shorter
 //    rows at once: with a wavefront per row a window of 21 columns kept 6 lanes of 64 busy with Philox and the scan cost 1.6
-//    times the reveal).  The noise is applied AT STAGING: bit 0 of a window byte is "appears blocking".  The rays march in LDS through march() as it is and set bit 1 of the cells
-//    they touch (every writer of a byte writes the same value); the write-out walks the window's rows and issues one atomic add
-//    per touched cell.  Global memory sees each window row once on the way in and at most one atomic per cell on the way out.
-//    Only this LDS form is built: R <= 127;
-//  - publish: a streaming kernel of the census' form -- 16-byte loads of the evidence, a byte store per cell, the table of
-//    2 e_clip + 1 bytes carried in the kernel arguments and staged in LDS, the three counts by wavefront reduction and one
-//    integer atomic per workgroup and count.
+//    times the reveal).  The noise is applied AT STAGING: bit 0 of a window byte is "appears blocking".  The rays
+//    march in LDS through the reveal's march_window and set bit 1 of the cells they touch (every writer of a byte writes the
+//    same value); the write-out walks the window's rows and issues one atomic add per touched cell.  Global memory sees each
+//    window row once on the way in and at most one atomic per cell on the way out.  Only this LDS form is built: R <= 127;
+//  - publish: a streaming kernel of the census' form, from the census' pieces (grid_census.hpp: stream_split, count_value,
+//    census_commit) -- 16-byte loads of the evidence, a byte store per cell, the table of 2 e_clip + 1 bytes carried in the
+//    kernel arguments and staged in LDS, the three counts by wavefront reduction and one integer atomic per workgroup and count.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -28,55 +30,29 @@
 #include <cstring>
 
 #include "common.hpp"
-#include "grid_cell.hpp"
+#include "grid_census.hpp"  // Census, count_value, census_commit, stream_split: shared with sense_kernel.hip
 #include "philox.hpp"
-#include "sense_rays.hpp"  // Clip, clip_of, cell_index, march: the reveal's, unchanged
+#include "sense_rays.hpp"  // the rays, and with sense_kernel.hip ScanParams, scan_launch, robot_cell, march_window
 
 namespace eea
 {
 namespace
 {
-constexpr int kEvidenceBlock = 256;
-constexpr unsigned kEvidenceMaxBlocks = 1u << 16;  // workgroups per launch; they stride over the robots past that
-
-struct ObserveParams
+struct ObserveParams : ScanParams<int32_t>  // out: the evidence
 {
-  CollisionParams c;  // the geometry (the radii are not read)
-  int R;
-  int cutoff;  // a truth cell blocks iff cell >= cutoff (128: no cell does)
   int w_occ, w_free;
   uint32_t thr_miss, thr_false, seed_lo, seed_hi;
   unsigned scan, robot0;
-  const int8_t* truth;
-  int32_t* evid;
-  const double* pose;  // [P][3]
-  const int* mask;     // [P] or null
-  int* ranges;         // [P][8R] or null
-  unsigned P;
 };
 
-// the robot of this workgroup's turn, as the reveal takes it: false when the mask leaves it out or its cell is off the grid
-// (its row of ranges is then -1)
-__device__ __forceinline__ bool observer_cell(const ObserveParams& p, unsigned b, unsigned& i0, unsigned& j0)
-{
-  if (p.mask != nullptr && p.mask[b] == 0) return false;
-  world_to_grid(p.c, p.pose[3 * static_cast<size_t>(b)], p.pose[3 * static_cast<size_t>(b) + 1], j0, i0);
-  if ((i0 <= p.c.ysize - 1u) && (j0 <= p.c.xsize - 1u)) return true;
-  if (p.ranges != nullptr) {
-    int* const row = p.ranges + static_cast<size_t>(b) * 8u * p.R;
-    for (int q = threadIdx.x; q < 8 * p.R; q += kEvidenceBlock) row[q] = -1;
-  }
-  return false;
-}
-
-__global__ __launch_bounds__(kEvidenceBlock) void evidence_observe_kernel(const ObserveParams p)
+__global__ __launch_bounds__(kBlock) void evidence_observe_kernel(const ObserveParams p)
 {
   extern __shared__ __attribute__((aligned(16))) unsigned char s_cell[];  // [2R + 1][2R + 1]: bit 0 appears blocking, bit 1 touched
   const int R = p.R, W = 2 * R + 1, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (unsigned b = blockIdx.x; b < p.P; b += gridDim.x) {
     __syncthreads();  // the robot before has read the window
     unsigned i0, j0;
-    if (!observer_cell(p, b, i0, j0)) continue;  // (uniform over the workgroup)
+    if (!robot_cell(p, b, i0, j0)) continue;  // (uniform over the workgroup)
     const Clip w = clip_of(p.c, i0, j0, R);
     // columns jlo .. jhi of the grid, in groups of four that share a Philox call: group = column >> 2
     const unsigned jlo = j0 + static_cast<unsigned>(w.xlo), jhi = j0 + static_cast<unsigned>(w.xhi);
@@ -85,7 +61,7 @@ __global__ __launch_bounds__(kEvidenceBlock) void evidence_observe_kernel(const 
     // row (a wavefront covers a row of 64 groups, or several shorter rows), and a thread's next group lies 256 further on
     const unsigned per_row = (jhi >> 2) - glo + 1u;  // <= 65: a row of 2R + 1 <= 255 cells
     const unsigned rows = static_cast<unsigned>(w.yhi - w.ylo) + 1u;
-    const unsigned skip_rows = kEvidenceBlock / per_row, skip_grps = kEvidenceBlock % per_row;
+    const unsigned skip_rows = kBlock / per_row, skip_grps = kBlock % per_row;
     unsigned row = static_cast<unsigned>(tid) / per_row, at = static_cast<unsigned>(tid) % per_row;
     while (row < rows) {
       const int dy = w.ylo + static_cast<int>(row);
@@ -110,18 +86,10 @@ __global__ __launch_bounds__(kEvidenceBlock) void evidence_observe_kernel(const 
     }
     __syncthreads();
     if (tid == 0) s_cell[R * W + R] = 2;  // the robot's own cell: touched, never appears blocking (no ray visits offset (0, 0))
-    for (int q = tid; q < 8 * R; q += kEvidenceBlock) {
-      const int range = march(q, R, w, [&](int dx, int dy) {
-        unsigned char* const cell = s_cell + (dy + R) * W + (dx + R);
-        const unsigned char v = *cell;
-        if (v < 2) *cell = v | 2;
-        return (v & 1) != 0;
-      });
-      if (p.ranges != nullptr) p.ranges[static_cast<size_t>(b) * 8u * R + q] = range;
-    }
+    march_window(p, b, w, s_cell);
     __syncthreads();
-    for (int dy = w.ylo + wave; dy <= w.yhi; dy += kEvidenceBlock / 64) {
-      int32_t* const erow = p.evid + cell_index(p.c, i0, j0, 0, dy);
+    for (int dy = w.ylo + wave; dy <= w.yhi; dy += kBlock / 64) {
+      int32_t* const erow = p.out + cell_index(p.c, i0, j0, 0, dy);
       const unsigned char* const srow = s_cell + (dy + R) * W + R;
       for (int dx = w.xlo + lane; dx <= w.xhi; dx += 64) {
         const unsigned char v = srow[dx];
@@ -145,66 +113,40 @@ struct PublishParams
 };
 static_assert(sizeof(PublishParams) <= 4096, "the publish launch carries its table in the kernel arguments");
 
-struct Census
-{
-  unsigned unknown, below, blocking;
-};
-
 // one cell: its byte is stored and counted
 __device__ __forceinline__ void publish_cell(const PublishParams& p, const int8_t* s_table, size_t at, int e, Census& n)
 {
   const int c = e < -p.e_clip ? -p.e_clip : e > p.e_clip ? p.e_clip : e;
   const int v = e == 0 ? -1 : s_table[c + p.e_clip];
   p.known[at] = static_cast<int8_t>(v);
-  n.unknown += v < 0 ? 1u : 0u;
-  n.below += (v >= 0 && v < p.cutoff) ? 1u : 0u;
-  n.blocking += v >= p.cutoff ? 1u : 0u;
+  count_value(n, v, p.cutoff);
 }
 
 // 16 bytes (four cells) per load from the evidence's first 16-byte boundary on; the cells in front of it and behind the last
 // whole load one by one (at most 3 each: the first threads of the launch take them).  `known` is written in bytes: it may
 // start anywhere
-__global__ __launch_bounds__(kEvidenceBlock) void evidence_publish_kernel(const PublishParams p)
+__global__ __launch_bounds__(kBlock) void evidence_publish_kernel(const PublishParams p)
 {
   __shared__ uint32_t s_words[kTableWords];
-  __shared__ unsigned s_part[kEvidenceBlock / 64][3];
-  for (int k = threadIdx.x; k < kTableWords; k += kEvidenceBlock) s_words[k] = p.table[k];
+  for (int k = threadIdx.x; k < kTableWords; k += kBlock) s_words[k] = p.table[k];
   __syncthreads();
   const int8_t* const s_table = reinterpret_cast<const int8_t*>(s_words);
-  size_t head = ((16u - (reinterpret_cast<uintptr_t>(p.evid) & 15u)) & 15u) / 4u;
-  if (head > p.n) head = p.n;
-  const size_t chunks = (p.n - head) / 4u, tail0 = head + chunks * 4u;
-  const size_t t = static_cast<size_t>(blockIdx.x) * kEvidenceBlock + threadIdx.x, stride = static_cast<size_t>(gridDim.x) * kEvidenceBlock;
+  const StreamSplit sp = stream_split<4>(reinterpret_cast<uintptr_t>(p.evid), p.n);
+  const size_t t = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x, stride = static_cast<size_t>(gridDim.x) * kBlock;
   Census cnt{ 0u, 0u, 0u };
-  const int4* const body = reinterpret_cast<const int4*>(p.evid + head);
-  for (size_t ch = t; ch < chunks; ch += stride) {
+  const int4* const body = reinterpret_cast<const int4*>(p.evid + sp.head);
+  for (size_t ch = t; ch < sp.chunks; ch += stride) {
     const int4 v = body[ch];
-    const size_t at = head + 4u * ch;
+    const size_t at = sp.head + 4u * ch;
     publish_cell(p, s_table, at, v.x, cnt);
     publish_cell(p, s_table, at + 1, v.y, cnt);
     publish_cell(p, s_table, at + 2, v.z, cnt);
     publish_cell(p, s_table, at + 3, v.w, cnt);
   }
-  if (t < head) publish_cell(p, s_table, t, p.evid[t], cnt);
-  if (t < p.n - tail0) publish_cell(p, s_table, tail0 + t, p.evid[tail0 + t], cnt);
+  if (t < sp.head) publish_cell(p, s_table, t, p.evid[t], cnt);
+  if (t < p.n - sp.tail0) publish_cell(p, s_table, sp.tail0 + t, p.evid[sp.tail0 + t], cnt);
   if (p.counts == nullptr) return;  // (uniform over the launch)
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    cnt.unknown += __shfl_down(cnt.unknown, d, 64);
-    cnt.below += __shfl_down(cnt.below, d, 64);
-    cnt.blocking += __shfl_down(cnt.blocking, d, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    s_part[threadIdx.x >> 6][0] = cnt.unknown;
-    s_part[threadIdx.x >> 6][1] = cnt.below;
-    s_part[threadIdx.x >> 6][2] = cnt.blocking;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    unsigned long long sum = 0;
-    for (int wv = 0; wv < kEvidenceBlock / 64; ++wv) sum += s_part[wv][threadIdx.x];
-    if (sum != 0) atomicAdd(p.counts + threadIdx.x, sum);  // integers: any order of the workgroups gives the same sums
-  }
+  census_commit(cnt, p.counts);
 }
 }  // namespace
 
@@ -225,9 +167,8 @@ hipError_t launch_evidence_observe(const CollisionParams& c, const EvidenceParam
   if (P == 0) return hipSuccess;
   if (range_cells == 0 || range_cells > kEvidenceMaxR) return hipErrorInvalidValue;  // (the entry has refused it: the window is LDS)
   ObserveParams p;
-  p.c = c;
-  p.R = static_cast<int>(range_cells);
-  p.cutoff = blocking_cutoff(c.occupied_threshold);
+  size_t window = 0;
+  const unsigned blocks = scan_launch(c, range_cells, d_truth, d_evid, d_pose, d_mask, d_ranges, P, p, &window);
   p.w_occ = ev.w_occ;
   p.w_free = ev.w_free;
   p.thr_miss = ev.thr_miss;
@@ -236,15 +177,7 @@ hipError_t launch_evidence_observe(const CollisionParams& c, const EvidenceParam
   p.seed_hi = ev.seed_hi;
   p.scan = scan;
   p.robot0 = robot0;
-  p.truth = d_truth;
-  p.evid = d_evid;
-  p.pose = d_pose;
-  p.mask = d_mask;
-  p.ranges = d_ranges;
-  p.P = P;
-  const unsigned blocks = P < kEvidenceMaxBlocks ? P : kEvidenceMaxBlocks;
-  const size_t W = 2 * static_cast<size_t>(range_cells) + 1;
-  hipLaunchKernelGGL(evidence_observe_kernel, dim3(blocks), dim3(kEvidenceBlock), W * W, s, p);
+  hipLaunchKernelGGL(evidence_observe_kernel, dim3(blocks), dim3(kBlock), window, s, p);
   return hipGetLastError();
 }
 
@@ -281,11 +214,11 @@ hipError_t launch_evidence_publish(const CollisionParams& c, const EvidenceParam
     const hipError_t e = hipMemsetAsync(d_counts, 0, 3 * sizeof(unsigned long long), s);
     if (e != hipSuccess) return e;
   }
-  const size_t want = (p.n / 4u + kEvidenceBlock - 1) / kEvidenceBlock + 1;  // (+ 1: the head and tail cells when there is no whole load)
+  const size_t want = (p.n / 4u + kBlock - 1) / kBlock + 1;  // (+ 1: the head and tail cells when there is no whole load)
   // every workgroup of a counting launch ends in three atomics on the same three counters: fewer, longer workgroups then
   const size_t most = d_counts != nullptr ? 256u : 2048u;
   const unsigned blocks = static_cast<unsigned>(want < most ? want : most);
-  hipLaunchKernelGGL(evidence_publish_kernel, dim3(blocks), dim3(kEvidenceBlock), 0, s, p);
+  hipLaunchKernelGGL(evidence_publish_kernel, dim3(blocks), dim3(kBlock), 0, s, p);
   return hipGetLastError();
 }
 }  // namespace eea

@@ -8,7 +8,8 @@
 //    own base plus a uniform offset, adds `alive & unknown` and clears `alive` on a cell that ends the ray.  A ray ends for the
 //    wavefront where it leaves the disc or no lane is alive.  No cross-lane reduction.
 //  - LDS form: the union of the tile's windows, (31 stride + 1 + 2R) x (7 stride + 1 + 2R) cells, is staged as one byte per
-//    cell -- bit 0 blocks, bit 1 unknown, bit 2 off the grid -- with coalesced row reads; the R cells of padding on every side
+//    cell -- bit 0 blocks, bit 1 unknown, bit 2 off the grid -- with coalesced row reads (gain_tile.hpp: stage_window, under
+//    this field's encoder); the R cells of padding on every side
 //    are off-grid bytes, so the march has no bounds test and no LDS write.  Taken when the window fits the 64 KB a launch may
 //    ask for without opting in (stride 1: R <= 118; 2: R <= 109; 4: R <= 91; 8: R <= 60).
 //  - global form (everything else, up to R = 1024 and any stride): the same tile, every lane marches its own rays through
@@ -35,28 +36,13 @@ struct GainParams : CandidateGrid
 __global__ __launch_bounds__(kGainBlock) void gain_field_lds_kernel(const GainParams p)
 {
   extern __shared__ __attribute__((aligned(16))) unsigned char s_win[];  // [H][W]: bit 0 blocks, bit 1 unknown, bit 2 off-grid
-  const int R = p.R, W = p.W, H = p.H, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int R = p.R, W = p.W, tid = threadIdx.x;
   const int st = static_cast<int>(p.stride);  // (small: the window fits 64 KB)
   const int base = ((tid / kGainTX) * st + R) * W + (tid % kGainTX) * st + R;
   for (unsigned long long t = blockIdx.x; t < p.tiles; t += gridDim.x) {
     __syncthreads();  // the tile before has read the window
     const Tile k = tile_of(p, t);
-    const long long wx0 = static_cast<long long>(k.cx0 * p.stride) - R, wy0 = static_cast<long long>(k.cy0 * p.stride) - R;
-    for (int wy = wave; wy < H; wy += kGainBlock / 64) {
-      const long long gy = wy0 + wy;
-      const bool row_in = gy >= 0 && gy < static_cast<long long>(p.c.ysize);
-      const int8_t* const krow = p.known + (row_in ? static_cast<size_t>(gy) * p.c.xsize : 0);
-      unsigned char* const srow = s_win + wy * W;
-      for (int wx = lane; wx < W; wx += 64) {
-        const long long gx = wx0 + wx;
-        unsigned char b = 4;
-        if (row_in && gx >= 0 && gx < static_cast<long long>(p.c.xsize)) {
-          const int v = krow[gx];
-          b = (v >= p.cutoff ? 1 : 0) | (v < 0 ? 2 : 0);
-        }
-        srow[wx] = b;
-      }
-    }
+    stage_window(p, k, s_win, 4, [&](int v) { return (v >= p.cutoff ? 1 : 0) | (v < 0 ? 2 : 0); });
     zero_off_lattice(p, k, p.gain);
     __syncthreads();
     const unsigned own = s_win[base];  // (inside the window for every lane, candidate or not)
@@ -118,19 +104,13 @@ __global__ __launch_bounds__(kGainBlock) void gain_field_global_kernel(const Gai
 }
 
 // the value grid of eea_set_target_gain: (real)((double)gain + floor) on the candidates whose cell does not block, 0 elsewhere
+// (gain_tile.hpp: candidate_values)
 template <typename R>
 __global__ __launch_bounds__(kGainBlock) void gain_values_kernel(const int8_t* __restrict__ known, const unsigned* __restrict__ gain,
                                                                  unsigned xsize, unsigned ysize, unsigned stride, int cutoff,
                                                                  double floor, R* __restrict__ out)
 {
-  const unsigned long long x = static_cast<unsigned long long>(blockIdx.x) * kGainBlock + threadIdx.x;
-  if (x >= xsize) return;
-  const bool lattice_col = static_cast<unsigned>(x) % stride == 0u;
-  for (unsigned y = blockIdx.y; y < ysize; y += gridDim.y) {
-    const size_t g = static_cast<size_t>(y) * xsize + x;
-    const bool cand = lattice_col && y % stride == 0u && known[g] < cutoff;
-    out[g] = cand ? static_cast<R>(static_cast<double>(gain[g]) + floor) : R(0);
-  }
+  candidate_values<R, unsigned, false>(known, gain, nullptr, xsize, ysize, stride, cutoff, floor, out);
 }
 
 }  // namespace
@@ -154,8 +134,7 @@ template <typename R>
 hipError_t launch_gain_values(const CollisionParams& c, unsigned stride, const int8_t* d_known, const unsigned* d_gain, double floor,
                               R* d_values, hipStream_t s)
 {
-  const unsigned bx = (c.xsize - 1u) / kGainBlock + 1u, by = c.ysize < 65535u ? c.ysize : 65535u;
-  hipLaunchKernelGGL(gain_values_kernel<R>, dim3(bx, by), dim3(kGainBlock), 0, s, d_known, d_gain, c.xsize, c.ysize, stride,
+  hipLaunchKernelGGL(gain_values_kernel<R>, values_grid(c), dim3(kGainBlock), 0, s, d_known, d_gain, c.xsize, c.ysize, stride,
                      blocking_cutoff(c.occupied_threshold), floor, d_values);
   return hipGetLastError();
 }

@@ -3,6 +3,9 @@
 // CANDIDATE, and the union of the tile's sensor windows -- (31 stride + 1 + 2R) x (7 stride + 1 + 2R) cells -- is what the LDS
 // forms stage.  The cells of a tile's footprint that are off the lattice are zeroed by the tile, the lattice cells are stored
 // by the lanes that own them: no cell has two writers.
+// With the tiling: the staging of that window under a per-cell encoder (stage_window: the two fields differ in the byte they
+// write per cell and nothing else), and the value grid of a target over a candidate field (candidate_values, values_grid): the
+// one body of gain_values_kernel, mi_values_kernel and geodesic_kernel.hip's reachable_values_kernel.
 #pragma once
 
 #include <cstdint>
@@ -57,6 +60,12 @@ inline unsigned candidate_grid(const CollisionParams& c, unsigned range_cells, u
   return p.tiles < kGainMaxBlocks ? static_cast<unsigned>(p.tiles) : kGainMaxBlocks;
 }
 
+// the workgroups of a value-grid launch (candidate_values below): a thread per column, the rows dealt to gridDim.y
+inline dim3 values_grid(const CollisionParams& c)
+{
+  return dim3((c.xsize - 1u) / kGainBlock + 1u, c.ysize < 65535u ? c.ysize : 65535u);
+}
+
 #if defined(__HIPCC__)
 struct Tile
 {
@@ -92,6 +101,44 @@ __device__ __forceinline__ void zero_off_lattice(const CandidateGrid& p, const T
     for (unsigned long long rx = lane; rx < w; rx += 64) {
       if (!(lattice_row && static_cast<unsigned>(rx) % p.stride == 0u)) row[rx] = T(0);
     }
+  }
+}
+
+// stages the union of the tile's sensor windows, s_win [H][W] from R cells in front of the tile's first candidate on, as one byte
+// per cell: encode(value) for a cell of the grid, off_grid for the padding.  A wavefront per row, the row read coalesced
+template <typename Encode>
+__device__ __forceinline__ void stage_window(const CandidateGrid& p, const Tile& k, unsigned char* s_win, int off_grid, Encode encode)
+{
+  const int R = p.R, W = p.W, H = p.H, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long wx0 = static_cast<long long>(k.cx0 * p.stride) - R, wy0 = static_cast<long long>(k.cy0 * p.stride) - R;
+  for (int wy = wave; wy < H; wy += kGainBlock / 64) {
+    const long long gy = wy0 + wy;
+    const bool row_in = gy >= 0 && gy < static_cast<long long>(p.c.ysize);
+    const int8_t* const krow = p.known + (row_in ? static_cast<size_t>(gy) * p.c.xsize : 0);
+    unsigned char* const srow = s_win + wy * W;
+    for (int wx = lane; wx < W; wx += 64) {
+      const long long gx = wx0 + wx;
+      int b = off_grid;
+      if (row_in && gx >= 0 && gx < static_cast<long long>(p.c.xsize)) b = encode(static_cast<int>(krow[gx]));
+      srow[wx] = static_cast<unsigned char>(b);
+    }
+  }
+}
+
+// the value grid of a target over a candidate field (eea_set_target_gain / _mi / _reachable): (real)((double)field + floor) on
+// the candidates whose cell does not block -- with GEO: and has geo >= 0 --, 0 elsewhere.  The body of the three value kernels
+template <typename R, typename Cell, bool GEO>
+__device__ __forceinline__ void candidate_values(const int8_t* __restrict__ known, const Cell* __restrict__ field,
+                                                 const int* __restrict__ geo, unsigned xsize, unsigned ysize, unsigned stride,
+                                                 int cutoff, double floor, R* __restrict__ out)
+{
+  const unsigned long long x = static_cast<unsigned long long>(blockIdx.x) * kGainBlock + threadIdx.x;
+  if (x >= xsize) return;
+  const bool lattice_col = static_cast<unsigned>(x) % stride == 0u;
+  for (unsigned y = blockIdx.y; y < ysize; y += gridDim.y) {
+    const size_t g = static_cast<size_t>(y) * xsize + x;
+    const bool cand = lattice_col && y % stride == 0u && known[g] < cutoff && (!GEO || geo[g] >= 0);
+    out[g] = cand ? static_cast<R>(static_cast<double>(field[g]) + floor) : R(0);
   }
 }
 #endif

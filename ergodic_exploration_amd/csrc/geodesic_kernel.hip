@@ -9,6 +9,7 @@
 
 #include "../../include/ergodic_amd.h"
 #include "common.hpp"
+#include "gain_tile.hpp"  // candidate_values, values_grid: the value grid's body and launch shape, shared with the candidate fields
 #include "geodesic_tile.hpp"
 
 namespace eea
@@ -91,20 +92,13 @@ __global__ __launch_bounds__(kBlock) void geodesic_path_kernel(const CollisionPa
   if (len != nullptr) len[q] = moves;
 }
 
-// the value grid of eea_set_target_reachable: gain_values_kernel's / mi_values_kernel's with "and geo >= 0"
+// the value grid of eea_set_target_reachable: candidate_values (gain_tile.hpp) with "and geo >= 0"
 template <typename R, typename Cell>
 __global__ __launch_bounds__(kBlock) void reachable_values_kernel(const int8_t* __restrict__ known, const Cell* __restrict__ field,
                                                                  const int* __restrict__ geo, unsigned xsize, unsigned ysize,
                                                                  unsigned stride, int cutoff, double floor, R* __restrict__ out)
 {
-  const unsigned long long x = static_cast<unsigned long long>(blockIdx.x) * kBlock + threadIdx.x;
-  if (x >= xsize) return;
-  const bool lattice_col = static_cast<unsigned>(x) % stride == 0u;
-  for (unsigned y = blockIdx.y; y < ysize; y += gridDim.y) {
-    const size_t g = static_cast<size_t>(y) * xsize + x;
-    const bool cand = lattice_col && y % stride == 0u && known[g] < cutoff && geo[g] >= 0;
-    out[g] = cand ? static_cast<R>(static_cast<double>(field[g]) + floor) : R(0);
-  }
+  candidate_values<R, Cell, true>(known, field, geo, xsize, ysize, stride, cutoff, floor, out);
 }
 }  // namespace
 
@@ -148,13 +142,12 @@ template <typename R>
 hipError_t launch_reachable_values(const CollisionParams& c, int kind, const void* d_field, unsigned stride, const int8_t* d_known,
                                    const int* d_geo, double floor, R* d_values, hipStream_t s)
 {
-  const unsigned bx = (c.xsize - 1u) / kBlock + 1u, by = c.ysize < 65535u ? c.ysize : 65535u;
   const int cutoff = blocking_cutoff(c.occupied_threshold);
   if (kind == 0) {
-    hipLaunchKernelGGL((reachable_values_kernel<R, unsigned>), dim3(bx, by), dim3(kBlock), 0, s, d_known,
+    hipLaunchKernelGGL((reachable_values_kernel<R, unsigned>), values_grid(c), dim3(kBlock), 0, s, d_known,
                        static_cast<const unsigned*>(d_field), d_geo, c.xsize, c.ysize, stride, cutoff, floor, d_values);
   } else {
-    hipLaunchKernelGGL((reachable_values_kernel<R, double>), dim3(bx, by), dim3(kBlock), 0, s, d_known,
+    hipLaunchKernelGGL((reachable_values_kernel<R, double>), values_grid(c), dim3(kBlock), 0, s, d_known,
                        static_cast<const double*>(d_field), d_geo, c.xsize, c.ysize, stride, cutoff, floor, d_values);
   }
   return hipGetLastError();

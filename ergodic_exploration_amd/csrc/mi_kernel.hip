@@ -10,8 +10,8 @@
 //
 //  - the tiling is the gain field's (gain_tile.hpp): a workgroup of 256 owns 32 x 8 candidates, A LANE IS A CANDIDATE, the ray
 //    geometry is wavefront-uniform and stays in scalar registers.
-//  - LDS form: the table, then the union of the tile's windows as one class byte per cell, the R cells of padding on every side
-//    and whatever else is off the grid being class 102.  A step is a byte read, a 16-byte pair read (ds_read_b128) and
+//  - LDS form: the table, then the union of the tile's windows as one class byte per cell (gain_tile.hpp: stage_window, the
+//    encoder being class_of), the R cells of padding on every side and whatever else is off the grid being class 102.  A step is a byte read, a 16-byte pair read (ds_read_b128) and
 //    beam += reach * h; reach *= pass: no bounds test, no blocking test, no alive flag.  kGainChunk steps are read before the
 //    first is used.  A ray ends for the wavefront where it leaves the disc or no lane has reach > 0.  Taken when
 //    W H + 1648 <= 64 KB (stride 1: R <= 116; 2: R <= 107; 4: R <= 90; 8: R <= 58) and the classes say all the table has to
@@ -68,26 +68,14 @@ __global__ __launch_bounds__(kGainBlock) void mi_field_lds_kernel(const MiParams
   extern __shared__ __attribute__((aligned(16))) unsigned char s_mem[];  // the table, then [H][W] class bytes
   double2* const s_tab = reinterpret_cast<double2*>(s_mem);
   unsigned char* const s_win = s_mem + kMiTableBytes;
-  const int R = p.R, W = p.W, H = p.H, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int R = p.R, W = p.W, tid = threadIdx.x;
   const int st = static_cast<int>(p.stride);  // (small: the window fits 64 KB)
   const int base = ((tid / kGainTX) * st + R) * W + (tid % kGainTX) * st + R;
   stage_table(p, reinterpret_cast<double*>(s_mem));
   for (unsigned long long t = blockIdx.x; t < p.tiles; t += gridDim.x) {
     __syncthreads();  // the tile before has read the window
     const Tile k = tile_of(p, t);
-    const long long wx0 = static_cast<long long>(k.cx0 * p.stride) - R, wy0 = static_cast<long long>(k.cy0 * p.stride) - R;
-    for (int wy = wave; wy < H; wy += kGainBlock / 64) {
-      const long long gy = wy0 + wy;
-      const bool row_in = gy >= 0 && gy < static_cast<long long>(p.c.ysize);
-      const int8_t* const krow = p.known + (row_in ? static_cast<size_t>(gy) * p.c.xsize : 0);
-      unsigned char* const srow = s_win + wy * W;
-      for (int wx = lane; wx < W; wx += 64) {
-        const long long gx = wx0 + wx;
-        int b = kMiOffGrid;
-        if (row_in && gx >= 0 && gx < static_cast<long long>(p.c.xsize)) b = class_of(krow[gx]);
-        srow[wx] = static_cast<unsigned char>(b);
-      }
-    }
+    stage_window(p, k, s_win, kMiOffGrid, [](int v) { return class_of(v); });
     zero_off_lattice(p, k, p.mi);
     __syncthreads();
     const size_t g0 = static_cast<size_t>(k.i0) * p.c.xsize + k.j0;  // (cell (0, 0) for a lane without a candidate)
@@ -163,19 +151,13 @@ __global__ __launch_bounds__(kGainBlock) void mi_field_global_kernel(const MiPar
 }
 
 // the value grid of eea_set_target_mi: (real)(mi + floor) on the candidates whose cell does not block, 0 elsewhere
+// (gain_tile.hpp: candidate_values; the cell is a double already)
 template <typename R>
 __global__ __launch_bounds__(kGainBlock) void mi_values_kernel(const int8_t* __restrict__ known, const double* __restrict__ mi,
                                                                unsigned xsize, unsigned ysize, unsigned stride, int cutoff, double floor,
                                                                R* __restrict__ out)
 {
-  const unsigned long long x = static_cast<unsigned long long>(blockIdx.x) * kGainBlock + threadIdx.x;
-  if (x >= xsize) return;
-  const bool lattice_col = static_cast<unsigned>(x) % stride == 0u;
-  for (unsigned y = blockIdx.y; y < ysize; y += gridDim.y) {
-    const size_t g = static_cast<size_t>(y) * xsize + x;
-    const bool cand = lattice_col && y % stride == 0u && known[g] < cutoff;
-    out[g] = cand ? static_cast<R>(mi[g] + floor) : R(0);
-  }
+  candidate_values<R, double, false>(known, mi, nullptr, xsize, ysize, stride, cutoff, floor, out);
 }
 }  // namespace
 
@@ -209,8 +191,7 @@ template <typename R>
 hipError_t launch_mi_values(const CollisionParams& c, unsigned stride, const int8_t* d_known, const double* d_mi, double floor,
                             R* d_values, hipStream_t s)
 {
-  const unsigned bx = (c.xsize - 1u) / kGainBlock + 1u, by = c.ysize < 65535u ? c.ysize : 65535u;
-  hipLaunchKernelGGL(mi_values_kernel<R>, dim3(bx, by), dim3(kGainBlock), 0, s, d_known, d_mi, c.xsize, c.ysize, stride,
+  hipLaunchKernelGGL(mi_values_kernel<R>, values_grid(c), dim3(kGainBlock), 0, s, d_known, d_mi, c.xsize, c.ysize, stride,
                      blocking_cutoff(c.occupied_threshold), floor, d_values);
   return hipGetLastError();
 }

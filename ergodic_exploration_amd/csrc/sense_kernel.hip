@@ -19,50 +19,28 @@
 //    rows are 2R + 1 bytes, an odd count: the cells of a column sit in different banks.
 //    R > 127 (the window passes 64 KB): the rays march in global memory, a dependent byte load and a byte store per step.
 //    Both compute the contract bit for bit (tests/test_gpu_sense.py holds each to tests/sense_restatement.py).
+//  What a scan is around its staging and write-out -- the launch block, the robot of a workgroup's turn, the march on the staged
+//  window -- lives in sense_rays.hpp, for this file and evidence_kernel.hip; the census' classes, reduction and 16-byte split
+//  live in grid_census.hpp, for grid_census_kernel and the evidence grid's publish kernel.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "common.hpp"
-#include "grid_cell.hpp"
-#include "sense_rays.hpp"  // Clip, clip_of, march: shared with gain_kernel.hip
+#include "grid_census.hpp"  // Census, count_value, census_commit, stream_split: shared with evidence_kernel.hip
+#include "sense_rays.hpp"   // the rays (shared with the candidate fields) and the scan's prologue and march (with evidence_kernel.hip)
 
 namespace eea
 {
 namespace
 {
-constexpr int kSenseBlock = 256;
-constexpr unsigned kSenseMaxBlocks = 1u << 16;  // workgroups per launch; they stride over the robots past that
-constexpr unsigned kSenseLdsMaxR = 127;         // (2R + 1)^2 bytes <= 64 KB
+constexpr unsigned kSenseLdsMaxR = 127;  // (2R + 1)^2 bytes <= 64 KB
 
-struct SenseParams
+struct SenseParams : ScanParams<int8_t>  // out: `known`
 {
-  CollisionParams c;  // the geometry (the radii are not read)
-  int R;
-  int cutoff;  // a cell blocks a ray iff cell >= cutoff (128: no cell does)
-  const int8_t* truth;
-  int8_t* known;
-  const double* pose;  // [P][3]
-  const int* mask;     // [P] or null
-  int* ranges;         // [P][8R] or null
-  unsigned P;
 };
 
-// the robot of this workgroup's turn: false when the mask leaves it out or its cell is off the grid (mapping.cpp:81-86's
-// rule; its row of ranges is then -1)
-__device__ __forceinline__ bool robot_cell(const SenseParams& p, unsigned b, unsigned& i0, unsigned& j0)
-{
-  if (p.mask != nullptr && p.mask[b] == 0) return false;
-  world_to_grid(p.c, p.pose[3 * static_cast<size_t>(b)], p.pose[3 * static_cast<size_t>(b) + 1], j0, i0);
-  if ((i0 <= p.c.ysize - 1u) && (j0 <= p.c.xsize - 1u)) return true;
-  if (p.ranges != nullptr) {
-    int* const row = p.ranges + static_cast<size_t>(b) * 8u * p.R;
-    for (int q = threadIdx.x; q < 8 * p.R; q += kSenseBlock) row[q] = -1;
-  }
-  return false;
-}
-
-__global__ __launch_bounds__(kSenseBlock) void sense_reveal_lds_kernel(const SenseParams p)
+__global__ __launch_bounds__(kBlock) void sense_reveal_lds_kernel(const SenseParams p)
 {
   extern __shared__ __attribute__((aligned(16))) unsigned char s_cell[];  // [2R + 1][2R + 1]: bit 0 blocks, bit 1 revealed
   const int R = p.R, W = 2 * R + 1, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -71,34 +49,26 @@ __global__ __launch_bounds__(kSenseBlock) void sense_reveal_lds_kernel(const Sen
     unsigned i0, j0;
     if (!robot_cell(p, b, i0, j0)) continue;  // (uniform over the workgroup)
     const Clip w = clip_of(p.c, i0, j0, R);
-    for (int dy = w.ylo + wave; dy <= w.yhi; dy += kSenseBlock / 64) {
+    for (int dy = w.ylo + wave; dy <= w.yhi; dy += kBlock / 64) {
       const int8_t* const trow = p.truth + cell_index(p.c, i0, j0, 0, dy);
       unsigned char* const srow = s_cell + (dy + R) * W + R;
       for (int dx = w.xlo + lane; dx <= w.xhi; dx += 64) srow[dx] = trow[dx] >= p.cutoff ? 1 : 0;
     }
     __syncthreads();
     if (tid == 0) s_cell[R * W + R] |= 2;  // the robot's own cell (no ray visits offset (0, 0))
-    for (int q = tid; q < 8 * R; q += kSenseBlock) {
-      const int range = march(q, R, w, [&](int dx, int dy) {
-        unsigned char* const cell = s_cell + (dy + R) * W + (dx + R);
-        const unsigned char v = *cell;
-        if (v < 2) *cell = v | 2;
-        return (v & 1) != 0;
-      });
-      if (p.ranges != nullptr) p.ranges[static_cast<size_t>(b) * 8u * R + q] = range;
-    }
+    march_window(p, b, w, s_cell);
     __syncthreads();
-    for (int dy = w.ylo + wave; dy <= w.yhi; dy += kSenseBlock / 64) {
+    for (int dy = w.ylo + wave; dy <= w.yhi; dy += kBlock / 64) {
       const size_t g0 = cell_index(p.c, i0, j0, 0, dy);
       const unsigned char* const srow = s_cell + (dy + R) * W + R;
       for (int dx = w.xlo + lane; dx <= w.xhi; dx += 64) {
-        if (srow[dx] & 2) p.known[g0 + dx] = p.truth[g0 + dx];
+        if (srow[dx] & 2) p.out[g0 + dx] = p.truth[g0 + dx];
       }
     }
   }
 }
 
-__global__ __launch_bounds__(kSenseBlock) void sense_reveal_global_kernel(const SenseParams p)
+__global__ __launch_bounds__(kBlock) void sense_reveal_global_kernel(const SenseParams p)
 {
   const int R = p.R, tid = threadIdx.x;
   for (unsigned b = blockIdx.x; b < p.P; b += gridDim.x) {
@@ -107,13 +77,13 @@ __global__ __launch_bounds__(kSenseBlock) void sense_reveal_global_kernel(const 
     const Clip w = clip_of(p.c, i0, j0, R);
     if (tid == 0) {
       const size_t g = cell_index(p.c, i0, j0, 0, 0);
-      p.known[g] = p.truth[g];
+      p.out[g] = p.truth[g];
     }
-    for (int q = tid; q < 8 * R; q += kSenseBlock) {
+    for (int q = tid; q < 8 * R; q += kBlock) {
       const int range = march(q, R, w, [&](int dx, int dy) {
         const size_t g = cell_index(p.c, i0, j0, dx, dy);
         const int8_t t = p.truth[g];
-        p.known[g] = t;
+        p.out[g] = t;
         return t >= p.cutoff;
       });
       if (p.ranges != nullptr) p.ranges[static_cast<size_t>(b) * 8u * R + q] = range;
@@ -121,57 +91,27 @@ __global__ __launch_bounds__(kSenseBlock) void sense_reveal_global_kernel(const 
   }
 }
 
-// ---- census ----------------------------------------------------------------------------------
-struct Census
-{
-  unsigned unknown, below, blocking;
-};
-__device__ __forceinline__ void count_cell(Census& n, int cell, int cutoff)
-{
-  n.unknown += cell < 0 ? 1u : 0u;
-  n.below += (cell >= 0 && cell < cutoff) ? 1u : 0u;
-  n.blocking += cell >= cutoff ? 1u : 0u;
-}
-
+// ---- census (grid_census.hpp) ------------------------------------------------------------------
 // 16 bytes per load from the grid's first 16-byte boundary on; the bytes in front of it and behind the last whole load one
 // by one (at most 15 each: the first threads of the launch take them).  d_counts was zeroed on the stream.
-__global__ __launch_bounds__(kSenseBlock) void grid_census_kernel(const int8_t* __restrict__ grid, size_t n, int cutoff,
-                                                                  unsigned long long* __restrict__ counts)
+__global__ __launch_bounds__(kBlock) void grid_census_kernel(const int8_t* __restrict__ grid, size_t n, int cutoff,
+                                                             unsigned long long* __restrict__ counts)
 {
-  __shared__ unsigned s_part[kSenseBlock / 64][3];
-  size_t head = (16u - (reinterpret_cast<uintptr_t>(grid) & 15u)) & 15u;
-  if (head > n) head = n;
-  const size_t chunks = (n - head) / 16u, tail0 = head + chunks * 16u;
-  const size_t t = static_cast<size_t>(blockIdx.x) * kSenseBlock + threadIdx.x, stride = static_cast<size_t>(gridDim.x) * kSenseBlock;
+  const StreamSplit sp = stream_split<1>(reinterpret_cast<uintptr_t>(grid), n);
+  const size_t t = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x, stride = static_cast<size_t>(gridDim.x) * kBlock;
   Census cnt{ 0u, 0u, 0u };
-  const uint4* const body = reinterpret_cast<const uint4*>(grid + head);
-  for (size_t ch = t; ch < chunks; ch += stride) {
+  const uint4* const body = reinterpret_cast<const uint4*>(grid + sp.head);
+  for (size_t ch = t; ch < sp.chunks; ch += stride) {
     const uint4 v = body[ch];
     const unsigned word[4] = { v.x, v.y, v.z, v.w };
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
-      for (int k = 0; k < 4; ++k) count_cell(cnt, static_cast<int8_t>((word[a] >> (8 * k)) & 0xffu), cutoff);
+      for (int k = 0; k < 4; ++k) count_value(cnt, static_cast<int8_t>((word[a] >> (8 * k)) & 0xffu), cutoff);
   }
-  if (t < head) count_cell(cnt, grid[t], cutoff);
-  if (t < n - tail0) count_cell(cnt, grid[tail0 + t], cutoff);
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    cnt.unknown += __shfl_down(cnt.unknown, d, 64);
-    cnt.below += __shfl_down(cnt.below, d, 64);
-    cnt.blocking += __shfl_down(cnt.blocking, d, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    s_part[threadIdx.x >> 6][0] = cnt.unknown;
-    s_part[threadIdx.x >> 6][1] = cnt.below;
-    s_part[threadIdx.x >> 6][2] = cnt.blocking;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    unsigned long long sum = 0;
-    for (int wv = 0; wv < kSenseBlock / 64; ++wv) sum += s_part[wv][threadIdx.x];
-    if (sum != 0) atomicAdd(counts + threadIdx.x, sum);  // integers: any order of the workgroups gives the same sums
-  }
+  if (t < sp.head) count_value(cnt, grid[t], cutoff);
+  if (t < n - sp.tail0) count_value(cnt, grid[sp.tail0 + t], cutoff);
+  census_commit(cnt, counts);
 }
 }  // namespace
 
@@ -180,21 +120,12 @@ hipError_t launch_sense_reveal(const CollisionParams& c, unsigned range_cells, c
 {
   if (P == 0) return hipSuccess;
   SenseParams p;
-  p.c = c;
-  p.R = static_cast<int>(range_cells);
-  p.cutoff = blocking_cutoff(c.occupied_threshold);
-  p.truth = d_truth;
-  p.known = d_known;
-  p.pose = d_pose;
-  p.mask = d_mask;
-  p.ranges = d_ranges;
-  p.P = P;
-  const unsigned blocks = P < kSenseMaxBlocks ? P : kSenseMaxBlocks;
+  size_t window = 0;
+  const unsigned blocks = scan_launch(c, range_cells, d_truth, d_known, d_pose, d_mask, d_ranges, P, p, &window);
   if (range_cells <= kSenseLdsMaxR) {
-    const size_t W = 2 * static_cast<size_t>(range_cells) + 1;
-    hipLaunchKernelGGL(sense_reveal_lds_kernel, dim3(blocks), dim3(kSenseBlock), W * W, s, p);
+    hipLaunchKernelGGL(sense_reveal_lds_kernel, dim3(blocks), dim3(kBlock), window, s, p);
   } else {
-    hipLaunchKernelGGL(sense_reveal_global_kernel, dim3(blocks), dim3(kSenseBlock), 0, s, p);
+    hipLaunchKernelGGL(sense_reveal_global_kernel, dim3(blocks), dim3(kBlock), 0, s, p);
   }
   return hipGetLastError();
 }
@@ -204,9 +135,9 @@ hipError_t launch_grid_census(const CollisionParams& c, const int8_t* d_grid, un
   const size_t n = static_cast<size_t>(c.xsize) * c.ysize;
   hipError_t e = hipMemsetAsync(d_counts, 0, 3 * sizeof(unsigned long long), s);
   if (e != hipSuccess) return e;
-  const size_t want = (n / 16u + kSenseBlock - 1) / kSenseBlock + 1;  // (+ 1: the head and tail bytes when there is no whole load)
+  const size_t want = (n / 16u + kBlock - 1) / kBlock + 1;  // (+ 1: the head and tail bytes when there is no whole load)
   const unsigned blocks = want < 2048u ? static_cast<unsigned>(want) : 2048u;
-  hipLaunchKernelGGL(grid_census_kernel, dim3(blocks), dim3(kSenseBlock), 0, s, d_grid, n, blocking_cutoff(c.occupied_threshold),
+  hipLaunchKernelGGL(grid_census_kernel, dim3(blocks), dim3(kBlock), 0, s, d_grid, n, blocking_cutoff(c.occupied_threshold),
                      d_counts);
   return hipGetLastError();
 }

@@ -168,6 +168,25 @@ def test_clipped_windows_at_the_lds_limit(xs, ys):
     assert (dev.evid > 0).any() and (dev.evid < 0).any()
 
 
+def test_masked_off_grid_and_corner_robot_in_one_call():
+    """the robot of a workgroup's turn is the reveal's (csrc/sense_rays.hpp: robot_cell), here in a scan: 23 x 19, R = 3, three
+    robots in one call -- masked out (its row of ranges is not written, no evidence), off the grid (a row of -1, no evidence), in
+    a corner (the clipped scan) -- ranges and evidence equal to the restatement bit for bit, noisy sensor"""
+    g = tgs._geom(23, 19)
+    truth = np.random.default_rng(23).choice(np.array([0] * 6 + [100, -1], dtype=np.int8), size=(19, 23))
+    truth[16, 0] = truth[17, 2] = truth[18, 2] = 100      # a wall around the corner robot
+    poses =[tgs._centre(g, 9, 11), [tgs.XMIN - 0.3, 0.0, 0.0], tgs._centre(g, 18, 0)]
+    dev = _Device(g, truth, NOISY)
+    got, want = dev.observe(3, 0, poses, mask=[0, 1, 1])
+    _same(got, want, "ranges")
+    dev.check_evid()
+    rows = got[GUARD:-GUARD].reshape(3, 24)
+    assert (rows[0] == S_RANGES).all() and (rows[1] == -1).all() and (rows[2] != S_RANGES).all() and (rows[2] > 0).any()
+    only_corner = np.zeros((19, 23), dtype=np.int32)
+    er.observe(g, NOISY, 3, 0, 2, truth, only_corner, [poses[2]])
+    assert np.array_equal(dev.evid, only_corner) and (only_corner != 0).sum() >= 9 and (only_corner > 0).any()
+
+
 @functools.lru_cache(maxsize=None)
 def _strided_fleet():
     """65536 + 3 robots on an 8 x 8 grid (a few off it), noisy sensor at R = 1: the restatement's evidence and ranges"""
