@@ -82,6 +82,15 @@ DISTANCE_MAX_SIDE = 8192     # EEA_DISTANCE_MAX_SIDE
 GEODESIC_TILE_X, GEODESIC_TILE_Y = 32, 32           # EEA_GEODESIC_TILE_X / _Y: the tile of the geodesic field's rounds
 GEODESIC_UNKNOWN_BLOCKS, GEODESIC_CONTINUE = 1, 2   # EEA_GEODESIC_*: flags of geodesic_field
 FOOTPRINT_MAX_VERTICES = 16  # EEA_FOOTPRINT_MAX_VERTICES
+FRONTIER_OF_GRID, FRONTIER_OF_MASK = 0, 1           # EEA_FRONTIER_OF_*: kind of frontier_regions
+
+
+class FrontierRegion(C.Structure):
+    """eea_frontier_region (56 bytes): sums of the members' rows / columns, the entry (cell, cost: one 8-byte word), root, size,
+    the bounding box, the entry's owner, 0"""
+    _fields_ = [("sum_i", C.c_uint64), ("sum_j", C.c_uint64), ("entry_cell", C.c_int32), ("entry_cost", C.c_int32),
+                ("root", C.c_int32), ("size", C.c_uint32), ("i_min", C.c_int32), ("i_max", C.c_int32), ("j_min", C.c_int32),
+                ("j_max", C.c_int32), ("entry_owner", C.c_int32), ("reserved", C.c_int32)]
 
 
 class Footprint(C.Structure):
@@ -263,6 +272,12 @@ def lib():
                                               C.c_void_p]
             L.eea_partition_path_batch.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint,
                                                    C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "eea_frontier_regions"):    # additive to ABI 6 as well
+            L.eea_frontier_ws_bytes.argtypes = [C.POINTER(CollisionCfg), C.POINTER(C.c_size_t)]
+            L.eea_frontier_regions.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.eea_frontier_goals.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_double, C.c_double,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         if hasattr(L, "eea_footprint_check_batch"):   # additive to ABI 6 as well
             L.eea_footprint_radii.argtypes = [C.POINTER(Footprint), C.POINTER(C.c_double), C.POINTER(C.c_double)]
             L.eea_footprint_check_batch.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.POINTER(Footprint), C.c_void_p, C.c_void_p,
@@ -848,6 +863,34 @@ def partition_path_batch(cfg, geo, owner, pose, goal_cell, path, length=None, de
     [P] (moves written, -1: no such way) or None.  Device tensors; asynchronous"""
     check(lib().eea_partition_path_batch(device, C.byref(cfg), _ptr(geo), _ptr(owner), _ptr(pose), int(pose.shape[0]),
                                          _ptr(goal_cell), int(path.shape[1]), _ptr(path), _ptr(length), C.c_void_p(stream or 0)))
+
+
+def frontier_ws_bytes(cfg):
+    """eea_frontier_ws_bytes: the bytes of workspace frontier_regions needs for the grid of cfg; host only"""
+    n = C.c_size_t()
+    check(lib().eea_frontier_ws_bytes(C.byref(cfg), C.byref(n)))
+    return n.value
+
+
+def frontier_regions(cfg, kind, grid, root, region, ws, state, regions=None, max_regions=0, geo=None, owner=None, device=0,
+                     stream=None):
+    """eea_frontier_regions: the members of the int8 device grid (FRONTIER_OF_GRID: free cells with an unknown axis neighbour;
+    FRONTIER_OF_MASK: non-zero cells; with geo also geo >= 0) in 8-connected regions.  root / region int32 [ysize][xsize] = the
+    least index / the rank of the cell's region, -1 for a non-member; regions: max_regions records of sizeof(FrontierRegion)
+    bytes (any dtype) or None with max_regions 0; state uint32 [4] (regions, records written, members, 0); ws:
+    frontier_ws_bytes(cfg) bytes, 8-byte aligned.  Device tensors; asynchronous"""
+    check(lib().eea_frontier_regions(device, C.byref(cfg), int(kind), _ptr(grid), _ptr(geo), _ptr(owner), int(max_regions), _ptr(root),
+                                     _ptr(region), _ptr(regions), _ptr(ws), _ptr(state), C.c_void_p(stream or 0)))
+
+
+def frontier_goals(regions, state, max_regions, goal_cell, goal_region, goal_score, min_size=1, w_size=1.0, w_cost=0.0, device=0,
+                   stream=None):
+    """eea_frontier_goals: per robot q < len(goal_cell) the record r < state[1] with entry_owner q, an entry and size >= min_size
+    of the greatest w_size * size - w_cost * entry_cost, the lowest r on a tie: goal_cell int32 = its entry_cell or -1,
+    goal_region int32 = r or -1, goal_score float64 = the score or 0.0.  Device tensors; asynchronous"""
+    check(lib().eea_frontier_goals(device, _ptr(regions), _ptr(state), int(max_regions), int(goal_cell.shape[0]), int(min_size),
+                                   float(w_size), float(w_cost), _ptr(goal_cell), _ptr(goal_region), _ptr(goal_score),
+                                   C.c_void_p(stream or 0)))
 
 
 def footprint_radii(fp):

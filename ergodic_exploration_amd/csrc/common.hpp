@@ -7,6 +7,8 @@
 #include <cstddef>
 #include <cstdint>
 
+struct eea_frontier_region;  // include/ergodic_amd.h: the record frontier_kernel.hip fills
+
 namespace eea
 {
 constexpr int kBlock = 256;    // threads per workgroup: 4 wavefronts of 64 lanes
@@ -561,6 +563,20 @@ hipError_t launch_partition_goals(const CollisionParams& c, int kind, const void
 // d_path [P][n_steps][3], d_len [P] (may be null): robot q's way from its own cell to d_goal_cell[q] inside its region
 hipError_t launch_partition_path(const CollisionParams& c, const int* d_geo, const int* d_owner, const double* d_pose, unsigned P,
                                  const int* d_goal_cell, unsigned n_steps, double* d_path, int* d_len, hipStream_t s);
+
+// ---- frontier regions: the 8-connected components of a grid's frontier cells or of a mask (frontier_kernel.hip) ----
+// the workspace holds two counts per 1024 cells; d_ws is 8-byte aligned
+size_t frontier_ws_bytes(unsigned xsize, unsigned ysize);
+// d_root / d_region [ysize][xsize], d_regions [min(n, max_regions)], d_state = {n, min(n, max_regions), members, 0}; kind:
+// EEA_FRONTIER_OF_GRID / EEA_FRONTIER_OF_MASK; d_geo, d_owner, d_regions (max_regions == 0) may be null.  A fixed number of launches
+hipError_t launch_frontier_regions(const CollisionParams& c, int kind, const int8_t* d_grid, const int* d_geo, const int* d_owner,
+                                   unsigned max_regions, int* d_root, int* d_region, eea_frontier_region* d_regions, void* d_ws,
+                                   unsigned* d_state, hipStream_t s);
+// per robot q < P the record r < d_state[1] with entry_owner q, an entry and size >= min_size of the greatest score w_size * size
+// - w_cost * entry_cost (lowest r on a tie) into d_goal_cell / d_goal_region / d_goal_score
+hipError_t launch_frontier_goals(const eea_frontier_region* d_regions, const unsigned* d_state, unsigned max_regions, unsigned P,
+                                 unsigned min_size, double w_size, double w_cost, int* d_goal_cell, int* d_goal_region,
+                                 double* d_goal_score, hipStream_t s);
 
 // ======================================================================================
 // device helpers

@@ -1,5 +1,5 @@
 // C ABI (include/ergodic_amd.h) of the entries that take a device or a layer and no engine: collision, clearance and distance
-// queries, the geodesic field and its paths, the geodesic partition with its goals and paths, the footprint and its planning entries, the range sensor, the census, the evidence grid, the gain and mutual-information fields, and the two layers with their
+// queries, the geodesic field and its paths, the geodesic partition with its goals and paths, the frontier regions and their goals, the footprint and its planning entries, the range sensor, the census, the evidence grid, the gain and mutual-information fields, and the two layers with their
 // batch entries.  Argument checking (entry_util.hpp) and kernel dispatch; every refusal comes before the device is selected.
 #include "../../include/ergodic_amd.h"
 
@@ -322,6 +322,56 @@ eea_status eea_partition_path_batch(int device, const eea_collision_cfg* cfg, co
   EEA_HIP(hipSetDevice(device));
   EEA_HIP(eea::launch_partition_path(grid_params(cfg), d_geo, d_owner, d_pose, P, d_goal_cell, n_steps, d_path, d_len,
                                      static_cast<hipStream_t>(stream)));
+  return EEA_OK;
+}
+
+// ---- frontier regions: connected frontiers, their records and a goal per robot (frontier_kernel.hip) ----
+eea_status eea_frontier_ws_bytes(const eea_collision_cfg* cfg, size_t* bytes)
+{
+  const eea_status st = geodesic_cfg_refusal(cfg);
+  if (st != EEA_OK) return st;
+  if (bytes == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  *bytes = eea::frontier_ws_bytes(cfg->xsize, cfg->ysize);
+  return EEA_OK;
+}
+
+eea_status eea_frontier_regions(int device, const eea_collision_cfg* cfg, int kind, const int8_t* d_grid, const int* d_geo,
+                                const int* d_owner, unsigned max_regions, int* d_root, int* d_region,
+                                eea_frontier_region* d_regions, void* d_ws, unsigned* d_state, void* stream)
+{
+  const eea_status st = geodesic_cfg_refusal(cfg);
+  if (st != EEA_OK) return st;
+  if (d_grid == nullptr || d_root == nullptr || d_region == nullptr || d_ws == nullptr || d_state == nullptr) {
+    return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  }
+  if (d_regions == nullptr && max_regions != 0u) return fail(EEA_ERR_INVALID_ARGUMENT, "d_regions is null with max_regions > 0");
+  if (d_owner != nullptr && d_geo == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "d_owner needs d_geo");
+  if (kind != EEA_FRONTIER_OF_GRID && kind != EEA_FRONTIER_OF_MASK) {
+    return fail(EEA_ERR_INVALID_ARGUMENT, "kind must be 0 (frontier of a grid) or 1 (a mask)");
+  }
+  if (reinterpret_cast<uintptr_t>(d_ws) % 8u != 0u) return fail(EEA_ERR_INVALID_ARGUMENT, "d_ws must be 8-byte aligned");
+  EEA_HIP(hipSetDevice(device));
+  EEA_HIP(eea::launch_frontier_regions(grid_params(cfg), kind, d_grid, d_geo, d_owner, max_regions, d_root, d_region, d_regions, d_ws,
+                                       d_state, static_cast<hipStream_t>(stream)));
+  return EEA_OK;
+}
+
+eea_status eea_frontier_goals(int device, const eea_frontier_region* d_regions, const unsigned* d_state, unsigned max_regions,
+                              unsigned P, unsigned min_size, double w_size, double w_cost, int* d_goal_cell, int* d_goal_region,
+                              double* d_goal_score, void* stream)
+{
+  if (d_regions == nullptr || d_state == nullptr || d_goal_cell == nullptr || d_goal_region == nullptr || d_goal_score == nullptr) {
+    return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  }
+  // (the comparisons are false for a NaN; the cap keeps a score finite)
+  if (!(w_size >= 0.0 && w_size <= 1e30) || !(w_cost >= 0.0 && w_cost <= 1e30)) {
+    return fail(EEA_ERR_INVALID_ARGUMENT, "a weight must be finite and within [0, 1e30]");
+  }
+  if (P > 0x7fffffffu) return fail(EEA_ERR_UNSUPPORTED, "more than 2^31 - 1 robots: a label is a non-negative int");
+  if (P == 0u) return EEA_OK;
+  EEA_HIP(hipSetDevice(device));
+  EEA_HIP(eea::launch_frontier_goals(d_regions, d_state, max_regions, P, min_size, w_size, w_cost, d_goal_cell, d_goal_region,
+                                     d_goal_score, static_cast<hipStream_t>(stream)));
   return EEA_OK;
 }
 

@@ -1,0 +1,168 @@
+// FrontierRegions: the frontier cells of a GridMap -- free cells with an unknown axis neighbour -- grouped into their
+// 8-connected regions, each with a label, a rank, a size, a centroid, a bounding box and, given a GeodesicPartition of the same
+// map, the member that is cheapest to reach with the robot that owns it; and per robot the region it should go for
+// (eea_frontier_regions / eea_frontier_goals).  No reference class.  Constructed from Collision's parameters, like
+// GeodesicPartition.  The object owns the two device planes, the records, the workspace, the state words and the goals of its
+// last goals() call.
+#pragma once
+
+#include <stdexcept>
+#include <vector>
+
+#include <ergodic_exploration/collision.hpp>
+#include <ergodic_exploration/device.hpp>
+#include <ergodic_exploration/geodesic_partition.hpp>
+#include <ergodic_exploration/grid.hpp>
+
+namespace ergodic_exploration
+{
+class FrontierRegions
+{
+public:
+  // max_regions: the records kept (regions are ranked by their least cell index; those past max_regions keep their rank in
+  // regionAt and have no record)
+  FrontierRegions(double boundary_radius, double search_radius, double obstacle_threshold, double occupied_threshold,
+                  unsigned max_regions = 4096)
+    : collision_(boundary_radius, search_radius, obstacle_threshold, occupied_threshold), max_regions_(max_regions)
+  {
+  }
+  FrontierRegions(const FrontierRegions&) = delete;
+  FrontierRegions& operator=(const FrontierRegions&) = delete;
+  ~FrontierRegions() { release(); }
+
+  // labels the frontier of this map; with a partition (built from the same map, it must outlive the goals() calls that
+  // follow) only reachable cells are members and every record gets its entry.  Waits
+  void update(const GridMap& grid, const GeodesicPartition* partition = nullptr)
+  {
+    const eea_collision_cfg cfg = collision_.deviceConfig(grid);
+    const size_t cells = static_cast<size_t>(cfg.xsize) * cfg.ysize;
+    size_t ws_bytes = 0;
+    throw_on_error(eea_frontier_ws_bytes(&cfg, &ws_bytes));
+    const int8_t* const d_grid = device_cells(grid);
+    built_ = false;
+    hip_check(hipSetDevice(device_ordinal()));
+    if (cells > capacity_ || ws_bytes > ws_capacity_) {
+      release_planes();
+      hip_check(hipMalloc(reinterpret_cast<void**>(&d_root_), cells * sizeof(int)));
+      hip_check(hipMalloc(reinterpret_cast<void**>(&d_region_), cells * sizeof(int)));
+      hip_check(hipMalloc(&d_ws_, ws_bytes));  // (an allocation's start: 8-byte aligned)
+      hip_check(hipMalloc(reinterpret_cast<void**>(&d_state_), 4 * sizeof(unsigned)));
+      if (max_regions_ != 0) hip_check(hipMalloc(reinterpret_cast<void**>(&d_regions_), sizeof(eea_frontier_region) * max_regions_));
+      capacity_ = cells;
+      ws_capacity_ = ws_bytes;
+    }
+    throw_on_error(eea_frontier_regions(device_ordinal(), &cfg, EEA_FRONTIER_OF_GRID, d_grid, partition ? partition->costs() : nullptr,
+                                        partition ? partition->owners() : nullptr, max_regions_, d_root_, d_region_, d_regions_, d_ws_,
+                                        d_state_, nullptr));
+    hip_check(hipMemcpy(state_, d_state_, sizeof(state_), hipMemcpyDeviceToHost));
+    records_.resize(state_[1]);
+    if (state_[1] != 0) {
+      hip_check(hipMemcpy(records_.data(), d_regions_, sizeof(eea_frontier_region) * state_[1], hipMemcpyDeviceToHost));
+    }
+    xsize_ = cfg.xsize;
+    cells_ = cells;
+    robots_ = partition ? partition->robots() : 0;
+    built_ = true;
+  }
+
+  // of the last update: the regions found, the member cells, and the records of the first min(count, max_regions) regions
+  unsigned count() const { return state_[0]; }
+  unsigned members() const { return state_[2]; }
+  const std::vector<eea_frontier_region>& regions() const { return records_; }
+
+  // the planes of the last update, [ysize][xsize] row-major device memory: the least cell index of the cell's region and the
+  // region's rank, -1 for a cell that is no member
+  const int* roots() const { return d_root_; }
+  const int* ranks() const { return d_region_; }
+  // one cell of them (row i, column j); each call copies one int from the device
+  int rootAt(unsigned i, unsigned j) const { return cell_of(d_root_, i, j); }
+  int regionAt(unsigned i, unsigned j) const { return cell_of(d_region_, i, j); }
+
+  struct Goals
+  {
+    std::vector<int> cell;      // [P] row-major index of the robot's goal (its region's entry cell), -1: none
+    std::vector<int> region;    // [P] the rank of the region it goes for, -1: none
+    std::vector<double> score;  // [P] its score, 0.0 without a goal
+  };
+  // per robot of the partition of the last update the region whose entry it owns, of at least min_size cells, with the
+  // greatest w_size * size - w_cost * entry cost, the lowest rank on a tie.  Waits
+  Goals goals(unsigned min_size, double w_size, double w_cost)
+  {
+    if (!built_) throw std::logic_error("FrontierRegions: update() has not labelled a map");
+    Goals out;
+    const unsigned P = robots_;
+    if (P == 0) return out;
+    if (max_regions_ == 0) throw std::logic_error("FrontierRegions: goals() needs records (max_regions > 0)");
+    if (P > robots_capacity_) {
+      release_robots();
+      hip_check(hipSetDevice(device_ordinal()));
+      hip_check(hipMalloc(reinterpret_cast<void**>(&d_goal_score_), sizeof(double) * P));
+      hip_check(hipMalloc(reinterpret_cast<void**>(&d_goal_cell_), sizeof(int) * P));
+      hip_check(hipMalloc(reinterpret_cast<void**>(&d_goal_region_), sizeof(int) * P));
+      robots_capacity_ = P;
+    }
+    throw_on_error(eea_frontier_goals(device_ordinal(), d_regions_, d_state_, max_regions_, P, min_size, w_size, w_cost, d_goal_cell_,
+                                      d_goal_region_, d_goal_score_, nullptr));
+    out.cell.resize(P);
+    out.region.resize(P);
+    out.score.resize(P);
+    hip_check(hipMemcpy(out.cell.data(), d_goal_cell_, sizeof(int) * P, hipMemcpyDeviceToHost));
+    hip_check(hipMemcpy(out.region.data(), d_goal_region_, sizeof(int) * P, hipMemcpyDeviceToHost));
+    hip_check(hipMemcpy(out.score.data(), d_goal_score_, sizeof(double) * P, hipMemcpyDeviceToHost));
+    return out;
+  }
+  // the goal cells of the last goals() call on the device, [robots]: what eea_partition_path_batch takes as d_goal_cell
+  const int* goalCells() const { return d_goal_cell_; }
+
+private:
+  int cell_of(const int* plane, unsigned i, unsigned j) const
+  {
+    if (!built_) throw std::logic_error("FrontierRegions: update() has not labelled a map");
+    const size_t at = static_cast<size_t>(i) * xsize_ + j;
+    if (j >= xsize_ || at >= cells_) throw std::out_of_range("FrontierRegions: cell outside the grid");
+    int v = -1;
+    hip_check(hipMemcpy(&v, plane + at, sizeof(int), hipMemcpyDeviceToHost));
+    return v;
+  }
+  void release_planes()
+  {
+    if (d_root_) (void)hipFree(d_root_);
+    if (d_region_) (void)hipFree(d_region_);
+    if (d_ws_) (void)hipFree(d_ws_);
+    if (d_state_) (void)hipFree(d_state_);
+    if (d_regions_) (void)hipFree(d_regions_);
+    d_root_ = d_region_ = nullptr;
+    d_ws_ = nullptr;
+    d_state_ = nullptr;
+    d_regions_ = nullptr;
+    capacity_ = ws_capacity_ = 0;
+  }
+  void release_robots()
+  {
+    if (d_goal_score_) (void)hipFree(d_goal_score_);
+    if (d_goal_cell_) (void)hipFree(d_goal_cell_);
+    if (d_goal_region_) (void)hipFree(d_goal_region_);
+    d_goal_score_ = nullptr;
+    d_goal_cell_ = d_goal_region_ = nullptr;
+    robots_capacity_ = 0;
+  }
+  void release()
+  {
+    release_planes();
+    release_robots();
+    built_ = false;
+  }
+  Collision collision_;
+  unsigned max_regions_;
+  int *d_root_ = nullptr, *d_region_ = nullptr, *d_goal_cell_ = nullptr, *d_goal_region_ = nullptr;
+  eea_frontier_region* d_regions_ = nullptr;
+  void* d_ws_ = nullptr;
+  unsigned* d_state_ = nullptr;
+  double* d_goal_score_ = nullptr;
+  unsigned state_[4] = { 0, 0, 0, 0 };
+  std::vector<eea_frontier_region> records_;
+  unsigned xsize_ = 0, robots_ = 0;
+  size_t cells_ = 0, capacity_ = 0, ws_capacity_ = 0, robots_capacity_ = 0;
+  bool built_ = false;
+};
+}  // namespace ergodic_exploration

@@ -1175,6 +1175,80 @@ eea_status eea_partition_path_batch(int device, const eea_collision_cfg* cfg, co
                                     const double* d_pose, unsigned P, const int* d_goal_cell, unsigned n_steps, double* d_path,
                                     int* d_len, void* stream);
 
+/* ---- frontier regions: connected frontiers, their statistics and a goal per robot (additive to ABI 6: detect these entries
+ * by symbol) ---------------------------------------------------------------------------------------------------------------
+ * No reference counterpart.  eea_partition_goals scores single cells: a one-cell hole in explored space scores like the edge
+ * of an unexplored room, and a goal has no identity.  These group the member cells of a grid into connected regions, each
+ * with a label, a rank, a size, a centroid (as two sums), a bounding box and an entry cell, and pick per robot the region to go
+ * for.  Integers with a unique answer (and one fp64 score of fixed arithmetic): bit-reproducible.
+ * eea_frontier_regions:
+ *   members       kind EEA_FRONTIER_OF_GRID: a cell (i, j) of value v = d_grid[i][j] with v >= 0, !blocks(v) -- the literal
+ *                 !(v / 100.0 < occupied_threshold) --, and at least one of its four axis neighbours INSIDE the grid of value
+ *                 < 0.  Off-grid neighbours are not unknown; a cell with only a diagonal unknown neighbour is no frontier.
+ *                 kind EEA_FRONTIER_OF_MASK: a cell with d_grid[i][j] != 0 (any class a caller has).
+ *                 With d_geo != NULL both kinds also require d_geo[i][j] >= 0: the reachable cells of eea_geodesic_field's or
+ *                 eea_geodesic_partition's plane.  d_owner (eea_geodesic_partition's) is only read with d_geo.
+ *   regions       the connected components of the members under 8-connectivity (no passed-between condition).  The label of a
+ *                 region is its root: the least row-major index of a member.  Regions are ranked 0 .. n - 1 by ascending root.
+ *   d_root        (int32 [ysize][xsize]) the root of the cell's region, -1 for a non-member.
+ *   d_region      (int32 [ysize][xsize]) the rank of the cell's region, -1 for a non-member; ranks >= max_regions are written
+ *                 as they are.  EVERY element of both planes is overwritten.
+ *   d_regions     [max_regions] records; record r < min(n, max_regions) is written, the others are not touched:
+ *                 size, sum_i / sum_j (sums of the members' rows / columns: the centroid is sum / size), i_min .. j_max (the
+ *                 bounding box), root; entry_cell = the member with the least (d_geo, row-major index), entry_cost = its
+ *                 d_geo, entry_owner = d_owner[entry_cell]; each of the three is -1 without the plane it needs; reserved = 0.
+ *                 entry_cost and entry_cell share one aligned 8-byte word, cost << 32 | cell, so that the entry is one 64-bit
+ *                 atomic minimum.
+ *   d_state       (uint32 [4], device) [0] n; [1] min(n, max_regions); [2] the number of member cells; [3] 0.
+ *   max_regions == 0 is allowed (d_regions may then be NULL): only the planes and the state are written.
+ *   The build is label-equivalence union-find on tiles of EEA_GEODESIC_TILE_X x EEA_GEODESIC_TILE_Y cells in a fixed number
+ *   of launches, whatever the map: every tile labels its own components in LDS and stores, per member, the index of its local
+ *   root into d_root; one lane per pair of member neighbours across a tile border unites their sets with a lock-free union
+ *   (find both roots, hang the larger under the smaller with an atomic minimum, go on with the link that was displaced; the
+ *   larger index of the pair falls in every turn, so every loop is bounded and none waits for another workgroup); then every
+ *   member takes the root of its set, roots are counted per 1024 consecutive cells and ranked by one scan, and the members add
+ *   into their records with integer atomics, combined per wavefront first.  Nothing waits inside a kernel; asynchronous on
+ *   `stream`: nothing is allocated, waited for or read on the host.
+ *   eea_frontier_ws_bytes: host only; the bytes d_ws must hold (positive, monotone in the grid's size).  d_ws is device memory
+ *   aligned to 8 bytes; its contents mean nothing between calls.
+ *   Before the device is selected, with no output touched -- EEA_ERR_INVALID_ARGUMENT: cfg, d_grid, d_root, d_region, d_ws or
+ *   d_state null; d_regions null with max_regions > 0; d_owner without d_geo; kind outside {0, 1}; d_ws not 8-byte aligned; the
+ *   configuration errors of the geodesic calls.  EEA_ERR_UNSUPPORTED: their limits (xsize * ysize <= 2^26, sides of at most
+ *   EEA_DISTANCE_MAX_SIDE).
+ * eea_frontier_goals: each robot q < P picks among the records r < d_state[1] (read on the device; d_state and max_regions are
+ *   those of the eea_frontier_regions call that wrote d_regions) with entry_owner == q, entry_cell >= 0 and size >= min_size
+ *   the one of the greatest score, the lowest r on a tie.
+ *   score            w_size * (double)size - w_cost * (double)entry_cost: both products rounded on their own, then subtracted,
+ *                    in fp64 with no contraction (eea_partition_goals' arithmetic).
+ *   d_goal_cell[q]   (int32) that record's entry_cell, or -1.
+ *   d_goal_region[q] (int32) r, or -1.
+ *   d_goal_score[q]  (double) the score, or 0.0.  EVERY element of the three is overwritten.
+ *   The goal cell g has d_owner[g] == q and d_geo[g] >= 0 by construction, so d_goal_cell goes straight into
+ *   eea_partition_path_batch and every robot with a goal gets len >= 0.  A robot whose region holds no entry gets -1.
+ *   No workspace (d_goal_score's own 8 bytes hold an order-preserving integer of the score during the call); asynchronous on
+ *   `stream`.  P == 0 is EEA_OK and touches nothing.  Before the device is selected -- EEA_ERR_INVALID_ARGUMENT: d_regions,
+ *   d_state, d_goal_cell, d_goal_region or d_goal_score null; a weight that is not finite or outside [0, 1e30].
+ *   EEA_ERR_UNSUPPORTED: P > 2^31 - 1.
+ * eea_abi_version() stays 6. */
+typedef struct eea_frontier_region { /* 56 bytes, 8-byte aligned */
+  uint64_t sum_i, sum_j; /* sums of the members' rows / columns: centroid = sum / size */
+  int32_t entry_cell;    /* member with the least (geo, row-major index); -1 without d_geo */
+  int32_t entry_cost;    /* its geo; -1 without d_geo */
+  int32_t root;          /* the region's label: least row-major index of a member */
+  uint32_t size;         /* members */
+  int32_t i_min, i_max, j_min, j_max;
+  int32_t entry_owner;   /* d_owner[entry_cell]; -1 without d_owner */
+  int32_t reserved;      /* 0 */
+} eea_frontier_region;
+enum { EEA_FRONTIER_OF_GRID = 0, EEA_FRONTIER_OF_MASK = 1 };
+eea_status eea_frontier_ws_bytes(const eea_collision_cfg* cfg, size_t* bytes);
+eea_status eea_frontier_regions(int device, const eea_collision_cfg* cfg, int kind, const int8_t* d_grid, const int* d_geo,
+                                const int* d_owner, unsigned max_regions, int* d_root, int* d_region,
+                                eea_frontier_region* d_regions, void* d_ws, unsigned* d_state, void* stream);
+eea_status eea_frontier_goals(int device, const eea_frontier_region* d_regions, const unsigned* d_state, unsigned max_regions,
+                              unsigned P, unsigned min_size, double w_size, double w_cost, int* d_goal_cell, int* d_goal_region,
+                              double* d_goal_score, void* stream);
+
 /* ---- footprint collision: a convex polygon base, checked through the distance field ----------------------------------
  * No reference counterpart (the reference README lists "model the robot's base as a polygon for collision detection" and "use
  * a distance field for detecting obstacle cells" under "Future Improvements").  Every other collision call treats the robot
