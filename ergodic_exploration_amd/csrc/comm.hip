@@ -526,12 +526,25 @@ struct eea_consensus_plan
   void* d_ws = nullptr;       // [slots] record-sum workspaces
   void* d_tickets = nullptr;  // [slots]
   size_t ws_bytes = 0, ticket_bytes = 0;
+  bool clear_slots = false;   // a group has d_skip: the graph empties a slot's records before the pass that writes them
+  double dom[4] = { 0.0, 0.0, 0.0, 0.0 };  // lx, ly, map_x, map_y the captured kernel nodes hold BY VALUE (fill_params)
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
 };
 
 namespace
 {
+// the domain scalars fill_params copies into a launch (T and K are fixed per engine)
+void plan_domain(const eea_engine* e, double dom[4])
+{
+  eea::EngineView v;
+  eea::engine_view(e, &v);
+  dom[0] = v.lx;
+  dom[1] = v.ly;
+  dom[2] = v.map_x;
+  dom[3] = v.map_y;
+}
+
 void plan_release(eea_consensus_plan* p)
 {
   if (p == nullptr) return;
@@ -612,6 +625,17 @@ eea_status plan_enqueue(eea_consensus_plan* p)
     if (st != EEA_OK) return st;
     st = eea_comm_allreduce_sum(p->e, p->c, s_slot, p->rec_len, p->xs);  // (nothing without an RCCL communicator)
     if (st != EEA_OK) return st;
+    if (p->clear_slots) {
+      // A skipped agent (a wavefront whose agents are all skipped) writes no record, so the records of pass i + lag start
+      // empty: what an agent that has been skipped since left there must not count again.  Here, in front of ev_x[slot]:
+      // the slot of pass i + lag was last read by the exchange of pass i + lag - slots = i - 2, earlier on this stream,
+      // and the groups of pass i + lag wait for ev_x[slot] anyway -- no new event, no new wait.  The first `lag` passes of a
+      // launch find the slots the last `lag` exchanges of the launch before cleared (passes % slots == 0; the device
+      // serialises the launches), those of the first launch the hipMemset of plan_create.
+      const unsigned ahead = (i + p->lag) % p->slots;
+      EEA_HIP(hipMemsetAsync(arec + static_cast<size_t>(ahead) * p->B * rec_bytes, 0, static_cast<size_t>(p->n_rec) * rec_bytes,
+                             p->xs));
+    }
     EEA_HIP(hipEventRecord(p->ev_x[slot], p->xs));
   }
   // join: the origin ends behind every group stream (its own last node is the last exchange, which follows the last launches)
@@ -661,6 +685,7 @@ eea_status eea_consensus_plan_create(eea_engine* e, eea_comm* c, const eea_conse
     mine.rec_seq = 0;
     mine.d_ck_flag = nullptr;
     mine.ck_flag_seq = 0;
+    p->clear_slots = p->clear_slots || io.d_skip != nullptr;
     p->io.push_back(mine);
   }
   EEA_HIP(hipSetDevice(p->device));
@@ -671,6 +696,7 @@ eea_status eea_consensus_plan_create(eea_engine* e, eea_comm* c, const eea_conse
     const eea_status st = eea_get_phik(e, phik.data());
     if (st != EEA_OK) return st;
   }
+  plan_domain(e, p->dom);
   eea_status st = eea_ck_records_sum_ws_bytes(e, p->B, &p->ws_bytes, &p->ticket_bytes);
   if (st != EEA_OK) return st;
   p->ws_bytes = (p->ws_bytes + 255) / 256 * 256;
@@ -726,6 +752,14 @@ eea_status eea_consensus_plan_create(eea_engine* e, eea_comm* c, const eea_conse
 eea_status eea_consensus_plan_launch(eea_consensus_plan* p, void* stream)
 {
   if (p == nullptr || p->exec == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null plan");
+  // the kernel nodes hold the domain by value: replayed on another domain they would run the old scalars against the new
+  // phi_k.  Values, not a generation count: a new target on the same domain is read through the phi_k pointer and is fine.
+  double dom[4];
+  plan_domain(p->e, dom);
+  if (dom[0] != p->dom[0] || dom[1] != p->dom[1] || dom[2] != p->dom[2] || dom[3] != p->dom[3]) {
+    return fail(EEA_ERR_UNSUPPORTED, "the domain changed since the plan was created (lx, ly and the map origin are captured by "
+                                     "value): the plan must be re-created (eea_consensus_plan_destroy, eea_consensus_plan_create)");
+  }
   EEA_HIP(hipSetDevice(p->device));
   EEA_HIP(hipGraphLaunch(p->exec, static_cast<hipStream_t>(stream)));
   return EEA_OK;

@@ -216,7 +216,9 @@ typedef struct {
                                         agent rejected with EEA_ERR_INVALID_TWIST gets an all-zero
                                         record.  eea_ck_records_sum adds the B records in ONE small
                                         launch (fixed order); the result -- sums and agent count --
-                                        is what d_ck_shared takes with ck_shared_parts > 0        */
+                                        is what d_ck_shared takes with ck_shared_parts > 0.  An agent
+                                        left out by d_skip writes NO record (below): the buffer keeps
+                                        what it held                                              */
   unsigned ck_shared_parts;/* ABI 3: 0 = d_ck_shared holds K^2 consensus values (ABI 2 form).
                                         n >= 1 = d_ck_shared holds n consecutive sum records
                                         (eea_ck_records_sum of earlier calls -- e.g. one per agent
@@ -230,7 +232,13 @@ typedef struct {
   unsigned* d_rec_ready;  /* [B] out (with d_ck_rec): rec_ready[b] = rec_seq once agent b's record is visible
                                         device-wide -- written behind the drained, write-through record, about half
                                         way through the agent's wavefront; eea_ck_records_sum_bound polls these marks
-                                        instead of waiting for the kernel to finish                              */
+                                        instead of waiting for the kernel to finish.  A record whose agents are ALL
+                                        left out by d_skip gets no mark: the device-bound sum polls for it until its
+                                        bound (about a second) runs out, then adds whatever the record holds and makes
+                                        the agent count of the sum negative (consumers keep their own c_k and report
+                                        EEA_ERR_TIMEOUT) -- with a skip set that can leave a record without agents, use
+                                        the stream-ordered sum (eea_ck_records_sum, eea_comm_records_exchange_async,
+                                        eea_consensus_plan) or set the marks of those records to rec_seq yourself */
   unsigned rec_seq;       /* sequence number of this pass (any value that grows from pass to pass, mod 2^32)     */
   const unsigned* d_ck_flag;/* in (with d_ck_shared): the kernel waits until *d_ck_flag has reached ck_flag_seq
                                         ((int)(*d_ck_flag - ck_flag_seq) >= 0) right before the first use of the shared
@@ -243,7 +251,12 @@ typedef struct {
   const int* d_skip;      /* [B] in, optional (ABI 5): agents with a non-zero entry are LEFT OUT of the call -- nothing of
                                         theirs is read or written, their warm start does not advance (a robot that
                                         follows a dynamic-window twist does not call control(), exploration.hpp:230-236;
-                                        eea_tick_batch fills it)                                                 */
+                                        eea_tick_batch fills it).  That includes its record in d_ck_rec and its mark in
+                                        d_rec_ready (with rec_per_wavefront: those of a wavefront whose agents are all
+                                        left out): they keep what they held.  A caller who REUSES a record buffer across
+                                        passes while the skip set changes must clear it before each pass, or an agent
+                                        that is skipped now counts again with its old c_k (eea_consensus_plan clears
+                                        its own slots)                                                           */
   int rec_per_wavefront;  /* ABI 6, with d_ck_rec: non-zero = where several agents share a wavefront (short horizons,
                                         eea_batch_agent_lanes < 64) the launch writes ONE record per wavefront -- [sum of
                                         the c_k of its accepted agents, their number, pad], the agents added in agent
@@ -429,6 +442,14 @@ eea_status eea_stream_wait_flag(const unsigned* d_flag, unsigned seq, unsigned* 
  * d_n_mem / mem_stride, d_status, d_skip per group: the exchange fields of group_io are ignored) and may rewrite the CONTENTS of
  * those buffers between launches (new poses), not the pointers.  Across launches the protocol continues: pass 0 of a launch
  * consumes the record of the last passes of the launch before (the first `lag` passes ever consume an empty record: own c_k).
+ * d_skip: its contents may change between launches like any other buffer's.  A skipped agent writes no record, so a plan with
+ * d_skip in any group EMPTIES a slot's records inside the graph before the pass that writes them: only the agents a pass runs
+ * count in its sum record, and a pass that skips everybody leaves an empty one (count 0: its consumers use their own c_k).
+ * The TARGET may change between launches as long as the domain stays: phi_k is read at replay time.  The DOMAIN -- lx, ly and
+ * the map origin, which eea_config_domain and every target entry that takes (lx, ly) can change -- is captured BY VALUE: while
+ * any of the four differs from its value at eea_consensus_plan_create, eea_consensus_plan_launch enqueues nothing and returns
+ * EEA_ERR_UNSUPPORTED (eea_last_error: the domain changed since the plan was created, the plan must be re-created); destroy the
+ * plan and create a new one, or restore the old values.
  * With several ranks every rank creates and launches its plan the same number of times (the all-reduces pair up in order).
  * A plan refers to its engine and communicator: destroy it before either.
  * EEA_ERR_UNSUPPORTED: the collective library cannot be captured -- use the per-call form.  No reference counterpart
