@@ -115,6 +115,48 @@ def regions(kind, grid, occupied_threshold, geo=None, owner=None, max_regions=No
     return root, region, rec, state
 
 
+def regions_fast(kind, grid, occupied_threshold, geo=None, owner=None, max_regions=None):
+    """regions() for grids where a pass per region is too slow: the same four values, byte for byte (tests/test_frontier.py holds
+    it to regions(), which stays the definition).  Labels from the raster union-find -- regions() takes the flood fill's --, ranks
+    by ascending root, and every record field by one array operation over the members"""
+    m = members(kind, grid, occupied_threshold, geo)
+    ys, xs = m.shape
+    root = roots_by_raster_union_find(m)
+    flat = root.reshape(-1)
+    idx = np.flatnonzero(flat >= 0).astype(np.int64)                         # the members, row-major
+    labels, rank = np.unique(flat[idx], return_inverse=True)                 # ascending roots; a member's rank
+    rank = rank.reshape(-1).astype(np.int64)
+    region = np.full(ys * xs, -1, dtype=np.int32)
+    region[idx] = rank
+    n = len(labels)
+    kept = n if max_regions is None else min(n, max_regions)
+    rec = np.zeros(kept, dtype=RECORD)
+    rec["root"] = labels[:kept]
+    rec["entry_cell"] = rec["entry_cost"] = rec["entry_owner"] = -1
+    has = rank < kept
+    idx, rank = idx[has], rank[has]
+    ii, jj = idx // xs, idx % xs
+    rec["size"] = np.bincount(rank, minlength=kept)
+    for name, v in (("sum_i", ii), ("sum_j", jj)):
+        total = np.zeros(kept, dtype=np.int64)
+        np.add.at(total, rank, v)
+        rec[name] = total
+    for name, v, op, start in (("i_min", ii, np.minimum, ys), ("i_max", ii, np.maximum, -1), ("j_min", jj, np.minimum, xs),
+                               ("j_max", jj, np.maximum, -1)):
+        edge = np.full(kept, start, dtype=np.int64)
+        op.at(edge, rank, v)
+        rec[name] = edge
+    if geo is not None and kept:
+        cost = np.asarray(geo).reshape(-1)[idx].astype(np.int64)
+        order = np.lexsort((idx, cost, rank))                                # by rank, then the least (geo, index) first
+        first = order[np.searchsorted(rank[order], np.arange(kept))]         # (every kept rank has a member)
+        rec["entry_cell"], rec["entry_cost"] = idx[first], cost[first]
+        if owner is not None:
+            rec["entry_owner"] = np.asarray(owner).reshape(-1)[idx[first]]
+    state = np.array([n, kept, int(m.sum()), 0], dtype=np.uint32)
+    return root, region.reshape(ys, xs), rec, state
+
+
 def goals(rec, P, min_size, w_size, w_cost):
     """(goal_cell int32 [P], goal_region int32 [P], goal_score float64 [P]): brute force over the records in ascending order"""
     cell = np.full(P, -1, dtype=np.int32)

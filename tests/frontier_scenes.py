@@ -80,6 +80,108 @@ MASKS = {
 }
 
 
+# ---- scenes past the sizes at which the kernels take another path -------------------------------------------------------------
+# frontier_rank_kernel sums share = (chunks - 1) / 256 + 1 consecutive chunks of 1024 cells per thread: only past 256 * 1024
+# cells is share >= 2 (here 2), do the trailing threads clamp lo / hi, and does a scatter workgroup read an offset its rank
+# thread wrote on the second turn of its loop.  Built on first use, like the others
+RANK_SINGLE_SHARE_CELLS = 256 * 1024
+LARGE_YS, LARGE_XS = 506, 520      # 257 chunks (thread 128 of the rank scan owns one trailing chunk), 16 x 17 tiles, ragged both ways
+
+
+def _large(f):
+    def build():
+        m = np.asarray(f())
+        assert m.size > RANK_SINGLE_SHARE_CELLS, "the rank kernel's share must be >= 2: more than 256 chunks of 1024 cells"
+        return m
+    return _frozen(build)
+
+
+def _large_every_third():
+    m = np.zeros((LARGE_YS, LARGE_XS), dtype=np.int8)
+    m[0::3, 0::3] = 1
+    return m
+
+
+def _large_rows():
+    """33 rows of 8192 columns (the widest grid the entry takes): 256 x 2 tiles, the second tile row one cell high, 264 chunks.
+    Row 0 is one region, united only westwards across 256 tiles; row 2 holds 4096 regions of one cell; row 32 holds runs of 63
+    members and one gap: a run that starts on a tile's first column crosses the next tile border in its middle"""
+    m = np.zeros((T + 1, capi.DISTANCE_MAX_SIDE), dtype=np.int8)
+    m[0, :] = 1
+    m[2, 0::2] = 1
+    m[T, :] = np.arange(m.shape[1]) % 64 != 63
+    return m
+
+
+def _large_random(density, seed):
+    return lambda: (np.random.default_rng(seed).random((LARGE_YS, LARGE_XS)) < density).astype(np.int8) * np.int8(-5)
+
+
+LARGE_MASKS = {
+    "large_every_third": _large(_large_every_third),                       # 29 406 regions of one cell: ranks through every offset
+    "large_serpentine": _large(lambda: fr.serpentine_mask(LARGE_YS, LARGE_XS)),  # one region through all 272 tiles: deep trees
+    "large_rows": _large(_large_rows),
+    "large_random_05": _large(_large_random(0.05, 41)),
+    "large_random_45": _large(_large_random(0.45, 42)),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def large_mask_regions(name, max_regions=None):
+    """fr.regions_fast of a large mask, computed once per (scene, max_regions); read-only"""
+    out = fr.regions_fast(fr.OF_MASK, LARGE_MASKS[name](), THR, max_regions=max_regions)
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+LargeRevealed = collections.namedtuple("LargeRevealed", "g truth known poses R sq clear_sq geo owner n_src")
+
+
+@functools.lru_cache(maxsize=None)
+def large_revealed():
+    """506 x 520: border walls, four long walls with gaps and 1 % clutter; 300 robots on free cells with a sensor of 10 cells.
+    300 sources are two workgroups of the seed and goal launches (a lane per source or label, 256 per workgroup), and the map
+    spans 16 x 17 tiles of the round machinery.  Robots 298 and 299 stand in the cells of robots 0 and 1: labels that own no
+    cell.  The clearance plane is the true walls', as in revealed_scene"""
+    from tests import distance_restatement as dr
+    ys, xs, R, P = LARGE_YS, LARGE_XS, 10, 300
+    assert ys * xs > RANK_SINGLE_SHARE_CELLS, "the rank kernel's share must be >= 2: more than 256 chunks of 1024 cells"
+    g = gs.geom(xs, ys)
+    rng = np.random.default_rng(506520)
+    truth = np.zeros((ys, xs), dtype=np.int8)
+    truth[rng.random((ys, xs)) < 0.01] = 100
+    truth[0, :] = truth[-1, :] = truth[:, 0] = truth[:, -1] = 100
+    truth[120, 30:400] = truth[300, 100:500] = 100
+    truth[40:380, 170] = truth[150:480, 350] = 100
+    truth[120, 90:96] = truth[120, 250:256] = truth[300, 200:206] = truth[300, 420:426] = 0
+    truth[200:206, 170] = truth[330:336, 170] = truth[220:226, 350] = truth[400:406, 350] = 0
+    free = np.argwhere(truth == 0)
+    at = free[np.sort(rng.choice(len(free), size=P - 2, replace=False))]
+    at = np.concatenate([at, at[:2]])
+    poses = np.array([gs.centre(g, int(i), int(j)) for i, j in at])
+    poses[:, 2] = rng.uniform(-3, 3, P)
+    known = np.full_like(truth, -1)
+    sr.reveal(g, R, truth, known, poses)
+    sq = dr.separable(truth, g.occupied_threshold)[0]
+    clear_sq = 2
+    cost, owner, n_src = part.partition(g, known, poses=poses, sq=sq, clear_sq=clear_sq, flags=geo.UNKNOWN_BLOCKS)
+    assert n_src == P and not (owner == P - 1).any() and not (owner == P - 2).any() and (owner == P - 3).any()
+    for a in (truth, known, sq, cost, owner, poses):
+        a.setflags(write=False)
+    return LargeRevealed(g, truth, known, poses, R, sq, clear_sq, cost, owner, n_src)
+
+
+@functools.lru_cache(maxsize=None)
+def large_revealed_regions():
+    """fr.regions_fast of large_revealed() with the partition's planes, computed once; read-only"""
+    sc = large_revealed()
+    out = fr.regions_fast(fr.OF_GRID, sc.known, sc.g.occupied_threshold, geo=sc.geo, owner=sc.owner)
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
 @functools.lru_cache(maxsize=None)
 def known_grid():
     """(grid int8 [7][8], members bool) at occupied_threshold 0.7: 69 is free and 70 blocks; the unknown cell (0, 7) sits at

@@ -104,6 +104,90 @@ def test_two_statements_agree_on_random_grids(seed):
                 assert m[i, j] == (v >= 0 and v / 100.0 < 0.8 and near)
 
 
+# ---- regions_fast, the reference of the large scenes, against regions, the definition ----------------------------------------
+def _identical(fast, slow):
+    for a, b, what in zip(fast, slow, ("root", "region", "records", "state")):
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), what
+
+
+@pytest.mark.parametrize("name", sorted(fs.MASKS))
+def test_regions_fast_is_regions_on_the_mask_scenes(name):
+    mask = fs.MASKS[name]()
+    n = int(fr.regions(fr.OF_MASK, mask, fs.THR)[3][0])
+    for max_regions in (None, 0, 1, 5, n, n + 1):
+        _identical(fr.regions_fast(fr.OF_MASK, mask, fs.THR, max_regions=max_regions),
+                   fr.regions(fr.OF_MASK, mask, fs.THR, max_regions=max_regions))
+
+
+def test_regions_fast_is_regions_on_the_grids():
+    """the hand-built grid; the revealed scene without the partition's planes, with d_geo alone and with both (entries with
+    ties in geo), each with room for every record, for some, for one and for none"""
+    grid, _ = fs.known_grid()
+    for max_regions in (None, 0, 3):
+        _identical(fr.regions_fast(fr.OF_GRID, grid, 0.7, max_regions=max_regions), fr.regions(fr.OF_GRID, grid, 0.7, max_regions=max_regions))
+    sc = fs.revealed_scene()
+    for planes in ({}, dict(geo=sc.geo), dict(geo=sc.geo, owner=sc.owner)):
+        for kind in (fr.OF_MASK, fr.OF_GRID):
+            for max_regions in (None, 0, 1, 2):
+                fast = fr.regions_fast(kind, sc.known, sc.g.occupied_threshold, max_regions=max_regions, **planes)
+                _identical(fast, fr.regions(kind, sc.known, sc.g.occupied_threshold, max_regions=max_regions, **planes))
+    assert fast[3][0] > 2 and (fast[2]["entry_owner"] >= 0).all()
+
+
+@pytest.mark.parametrize("seed", range(24))
+def test_regions_fast_is_regions_on_random_grids(seed):
+    """the grids of test_two_statements_agree_on_random_grids: both kinds, a third of them with geo (-1 among its values) and an
+    owner plane"""
+    rng = np.random.default_rng(500 + seed)
+    ys, xs = int(rng.integers(1, 40)), int(rng.integers(1, 40))
+    if seed % 2:
+        grid = (rng.random((ys, xs)) < rng.choice([0.3, 0.45, 0.6])).astype(np.int8) * np.int8(rng.choice([1, -3, 100]))
+        kind = fr.OF_MASK
+    else:
+        grid = rng.choice(np.array([0, 0, 0, -1, -1, 100, 79, 80], dtype=np.int8), size=(ys, xs))
+        kind = fr.OF_GRID
+    geo = rng.integers(-1, 4, size=(ys, xs)).astype(np.int32) if seed % 3 == 0 else None
+    owner = None if geo is None else rng.integers(0, 3, size=(ys, xs)).astype(np.int32)
+    for max_regions in (None, 2):
+        _identical(fr.regions_fast(kind, grid, 0.8, geo=geo, owner=owner, max_regions=max_regions),
+                   fr.regions(kind, grid, 0.8, geo=geo, owner=owner, max_regions=max_regions))
+
+
+@pytest.mark.parametrize("name", sorted(fs.LARGE_MASKS))
+def test_the_large_masks_are_what_their_names_say(name):
+    """more than 256 chunks of 1024 cells each; the labels of regions_fast (a raster union-find) are the flood fill's; the
+    counts the scenes were drawn for"""
+    mask = fs.LARGE_MASKS[name]()
+    root, region, rec, state = fs.large_mask_regions(name)
+    assert (mask.size - 1) // 1024 + 1 > 256 and not mask.flags.writeable
+    assert np.array_equal(root, fr.roots_by_flood_fill(fr.members(fr.OF_MASK, mask, fs.THR)))
+    assert state[0] == state[1] == len(rec) and rec["size"].sum() == state[2] == np.count_nonzero(mask)
+    assert np.array_equal(region.reshape(-1)[rec["root"]], np.arange(len(rec))) and (np.diff(rec["root"]) > 0).all()
+    if name == "large_every_third":
+        assert mask.shape == (506, 520) and state[0] == 29406 and (rec["size"] == 1).all()
+    if name == "large_serpentine":
+        assert state.tolist() == [1, 1, 131813, 0] and (rec[0]["i_max"], rec[0]["j_max"]) == (505, 519)
+    if name == "large_rows":
+        assert mask.shape == (33, 8192) and state[0] == 1 + 4096 + 128 and rec[0]["size"] == 8192 and (rec[1:4097]["size"] == 1).all()
+        assert (rec[4097:]["size"] == 63).all()
+    if name.startswith("large_random"):
+        assert state[0] > 1000
+    cut = fs.large_mask_regions(name, 300) if name == "large_every_third" else None
+    if cut is not None:
+        assert cut[3].tolist() == [29406, 300, 29406, 0] and cut[2].tobytes() == rec[:300].tobytes() and np.array_equal(cut[1], region)
+
+
+def test_the_large_revealed_scene():
+    """300 accepted sources, the last two without a cell of their own; frontier regions owned by most robots"""
+    sc = fs.large_revealed()
+    root, region, rec, state = fs.large_revealed_regions()
+    assert sc.known.shape == (506, 520) and sc.n_src == 300 and len(sc.poses) == 300
+    assert set(np.unique(sc.owner)) == set(range(-1, 298))
+    assert state[0] > 300 and len(set(rec["entry_owner"].tolist())) > 200 and (rec["entry_cell"] >= 0).all()
+    cell, reg, score = fr.goals(rec, 300, 2, 1.0, 0.125)
+    assert (cell >= 0).sum() > 200 and cell[298] == cell[299] == -1
+
+
 @pytest.mark.parametrize("seed", range(12))
 def test_goals_are_the_argmax_with_ties_to_the_lowest_record(seed):
     rng = np.random.default_rng(seed)

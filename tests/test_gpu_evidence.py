@@ -276,6 +276,44 @@ def test_publish_is_the_table_lookup(shift):
     assert np.array_equal(ebuf.cpu().numpy()[GUARD + shift:GUARD + shift + 210], evid.reshape(-1))   # read only
 
 
+@pytest.mark.parametrize("shift", [0, 3])
+def test_publish_past_both_launch_caps(shift):
+    """2048 x 1025 cells: 524 800 loads of four cells.  A counting launch is capped at 256 workgroups (its threads take nine
+    steps of the body loop), one without counts at 2048 (the first threads take a second step); every smaller grid in this file
+    gives each thread at most one load.  known = the table lookup, whole and between guard bytes; d_counts = eea_grid_census of
+    the published grid, between guard words"""
+    xs, ys = 2048, 1025
+    n = xs * ys
+    assert n // 4 - 1 > 2048 * 256
+    g, ev = tgs._geom(xs, ys), IDEAL
+    rng = np.random.default_rng(100 + shift)
+    evid = rng.integers(-1100, 1101, size=(ys, xs)).astype(np.int32)
+    evid[rng.random((ys, xs)) < 0.2] = 0
+    evid[0, :8], evid[-1, -8:] = -2 ** 31, 2 ** 31 - 1
+    ebuf = torch.as_tensor(np.concatenate([np.full(GUARD + shift, G_EVID, np.int32), evid.reshape(-1),
+                                           np.full(GUARD, G_EVID, np.int32)])).cuda()
+    d_evid = ebuf[GUARD + shift:GUARD + shift + n]
+    want = er.publish(ev, evid, capi.evidence_table(_ecfg(ev)))
+    image = np.concatenate([np.full(GUARD + shift, G_KNOWN, np.int8), want.reshape(-1), np.full(GUARD, G_KNOWN, np.int8)])
+    for with_counts in (True, False):
+        kbuf = torch.full((2 * GUARD + shift + n,), G_KNOWN, dtype=torch.int8, device="cuda")
+        d_known = kbuf[GUARD + shift:GUARD + shift + n]
+        counts = torch.full((5,), 123456789, dtype=torch.int64, device="cuda")
+        census = torch.zeros(3, dtype=torch.int64, device="cuda")
+        capi.evidence_publish(tgs._cfg(g), _ecfg(ev), d_evid, d_known, counts[1:4] if with_counts else None)
+        capi.grid_census(tgs._cfg(g), d_known, census)
+        torch.cuda.synchronize()
+        _same(kbuf.cpu().numpy(), image, "known")
+        c = counts.cpu().numpy()
+        assert c[0] == c[4] == 123456789
+        assert tuple(int(v) for v in census.cpu().numpy()) == sr.census(g, want)
+        if with_counts:
+            assert tuple(int(v) for v in c[1:4]) == sr.census(g, want) and (c[1:4] > 100000).all()
+        else:
+            assert (c[1:4] == 123456789).all()
+    assert np.array_equal(ebuf.cpu().numpy()[GUARD + shift:GUARD + shift + n], evid.reshape(-1))   # read only
+
+
 def test_join_feeds_the_mutual_information():
     """a 48 x 40 grid with walls, 6 robots, 8 noisy scans, then the publication: evidence and published grid equal the
     restatement, and eea_sense_mi_field on the published grid (R = 6, stride 1) equals tests/mi_restatement.py bit for bit"""

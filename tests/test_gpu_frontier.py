@@ -99,12 +99,13 @@ def _sentinel(n):
     return np.full(n * WORDS, S_RECORD, np.int64).view(fr.RECORD)
 
 
-def _run(dev, kind, geo_plane=None, owner=None, max_regions=None, spare=3, **kw):
+def _run(dev, kind, geo_plane=None, owner=None, max_regions=None, spare=3, want=None, **kw):
     """one call against the restatement: both planes and the state as whole buffers, the records written by their bytes, the
     records past min(n, max_regions) (the buffer holds `spare` more than max_regions) still the sentinel.  max_regions None: room
-    for every region.  Returns the planes, the records written and the state"""
-    want_root, want_region, want_rec, want_state = fr.regions(kind, dev.grid, dev.g.occupied_threshold, geo=geo_plane, owner=owner,
-                                                              max_regions=max_regions)
+    for every region.  want: the restatement's answer to these arguments where the caller holds it already (the large scenes,
+    whose reference is fr.regions_fast, computed once).  Returns the planes, the records written and the state"""
+    want_root, want_region, want_rec, want_state = want if want is not None else fr.regions(
+        kind, dev.grid, dev.g.occupied_threshold, geo=geo_plane, owner=owner, max_regions=max_regions)
     cap = int(want_state[0]) + 2 if max_regions is None else max_regions
     root, region, rec, state = dev.regions(kind, geo_plane, owner, max_regions=cap, n_records=cap + spare if cap else 0, **kw)
     _same(root, want_root, "root")
@@ -308,6 +309,88 @@ def test_reveal_partition_frontier_goals_paths_on_the_device():
     for q in going:
         cx, cy = geo.cell_centre(g, int(cell[q]) // g.xsize, int(cell[q]) % g.xsize)
         assert np.array_equal(_bits(path[q, -1, :2]), _bits(np.array([cx, cy]))), q
+
+
+# ---- past 256 chunks: the paths only large inputs reach ----------------------------------------------------------------------
+# More than 256 * 1024 cells (tests/frontier_scenes.py asserts it): every thread of frontier_rank_kernel sums share = 2 chunks,
+# so its two chunk loops take a second turn, the threads past chunks / 2 clamp lo and hi, and half the scatter workgroups read an
+# offset written on that second turn; the stats launch has 129 and more workgroups, merge and flatten see sets that span
+# hundreds of tiles.  The reference is fr.regions_fast, held to fr.regions byte for byte by tests/test_frontier.py
+@pytest.mark.parametrize("name", sorted(fs.LARGE_MASKS))
+def test_large_masks_are_the_restatement(name):
+    """506 x 520 (257 chunks, 16 x 17 tiles, ragged both ways): 29 406 regions of one cell, whose ranks run through every chunk
+    offset; one serpentine of 131 813 members through all 272 tiles, whose record takes atomics from every stats workgroup;
+    random masks at 5 % and 45 %.  33 x 8192 (264 chunks, 256 x 2 tiles): a row united only westwards across 256 tiles, 4096
+    regions of one cell, runs of 63.  Planes, state and every record with room for all of them"""
+    mask = fs.LARGE_MASKS[name]()
+    want = fs.large_mask_regions(name)
+    dev = _Device(_geom(mask.shape[1], mask.shape[0]), mask)
+    assert dev.n_fws == 2 * 4 * ((mask.size - 1) // 1024 + 1) > 2 * 4 * 256
+    root, region, rec, state = _run(dev, capi.FRONTIER_OF_MASK, want=want)
+    assert len(rec) == int(want[3][0]) == state[0] and state[2] == np.count_nonzero(mask)
+    if name == "large_serpentine":
+        assert state[0] == 1 and (root[mask != 0] == 0).all() and rec[0]["size"] == np.count_nonzero(mask)
+    if name == "large_rows":
+        assert (root[0] == 0).all() and rec[0]["size"] == mask.shape[1] and np.array_equal(region[2, 0::2], np.arange(1, 4097))
+
+
+@pytest.mark.parametrize("max_regions", [300, 0])
+def test_large_every_third_with_fewer_records_than_regions(max_regions):
+    """29 406 regions and room for 300 records, or none (d_regions NULL): d_region holds the true ranks past the cut in every
+    one of the 257 chunks, the records from the 301st on keep the sentinel"""
+    mask = fs.LARGE_MASKS["large_every_third"]()
+    dev = _Device(_geom(mask.shape[1], mask.shape[0]), mask)
+    root, region, rec, state = _run(dev, capi.FRONTIER_OF_MASK, max_regions=max_regions,
+                                    want=fs.large_mask_regions("large_every_third", max_regions))
+    n = np.count_nonzero(mask)
+    assert state.tolist() == [n, max_regions, n, 0] and len(rec) == max_regions and n == 29406
+    assert np.array_equal(region[mask != 0], np.arange(n))
+
+
+def test_a_large_revealed_map_its_goals_and_their_paths():
+    """506 x 520 revealed by 300 robots, with the partition's planes (300 labels): regions and records, then eea_frontier_goals
+    for P = 300 (two workgroups of robots) on the device's own records, then eea_partition_path_batch on the goal cells: every
+    robot with a goal has len >= 0, way-points and lengths are the restatement's"""
+    sc = fs.large_revealed()
+    g, P = sc.g, len(sc.poses)
+    dev = _Device(g, sc.known)
+    root, region, rec, state = _run(dev, capi.FRONTIER_OF_GRID, geo_plane=sc.geo, owner=sc.owner, want=fs.large_revealed_regions())
+    assert state[0] > P and (rec["entry_cell"] >= 0).all() and len(set(rec["entry_owner"].tolist())) > 200
+    cell, reg, score = dev.goals_of(dev.d_rec, dev.d_state, len(rec), P, 2, 1.0, 0.125)
+    want = fr.goals(rec, P, 2, 1.0, 0.125)
+    assert np.array_equal(cell, want[0]) and np.array_equal(reg, want[1]) and np.array_equal(_bits(score), _bits(want[2]))
+    going = np.flatnonzero(cell >= 0)
+    assert len(going) > 200 and (going >= 256).any() and cell[P - 1] == -1
+    assert (sc.owner.reshape(-1)[cell[going]] == going).all() and (sc.geo.reshape(-1)[cell[going]] >= 0).all()
+    n_steps = int(rec["entry_cost"][reg[going]].max()) // 5 + 3
+    d_pose = dev.upload(sc.poses, np.float64).view(-1, 3)
+    _, pbuf, d_path = _guarded(np.full(P * n_steps * 3, S_PATH), 2.5, np.float64)
+    _, lbuf, d_len = _guarded(np.full(P, S_GEO, np.int32), G_OUT, np.int32)
+    torch.cuda.synchronize()
+    capi.partition_path_batch(dev.cfg, dev.d_geo, dev.d_owner, d_pose, dev.d_goal_cell, d_path.view(P, n_steps, 3), d_len)
+    torch.cuda.synchronize()
+    path, length = dev.check(pbuf, 2.5).reshape(P, n_steps, 3), dev.check(lbuf)
+    want_path, want_len = part.paths(g, sc.geo, sc.owner, sc.poses, cell, n_steps)
+    assert np.array_equal(length, want_len) and np.array_equal(_bits(path), _bits(want_path))
+    assert np.array_equal(length >= 0, cell >= 0) and (length > 0).any() and length.max() < n_steps
+
+
+def test_a_large_call_again_on_another_stream_gives_the_same_bits():
+    """the 45 % mask (thousands of unions in flight, records that take atomics from many workgroups) and the revealed map with
+    its planes: the second call, on another stream, gives the bits of the first"""
+    st = torch.cuda.Stream()
+    mask = fs.LARGE_MASKS["large_random_45"]()
+    dev = _Device(_geom(mask.shape[1], mask.shape[0]), mask)
+    want = fs.large_mask_regions("large_random_45")
+    first = _run(dev, capi.FRONTIER_OF_MASK, want=want)
+    other = _run(dev, capi.FRONTIER_OF_MASK, want=want, stream=st.cuda_stream)
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(first, other))
+    sc = fs.large_revealed()
+    dev = _Device(sc.g, sc.known)
+    want = fs.large_revealed_regions()
+    first = _run(dev, capi.FRONTIER_OF_GRID, geo_plane=sc.geo, owner=sc.owner, want=want)
+    other = _run(dev, capi.FRONTIER_OF_GRID, geo_plane=sc.geo, owner=sc.owner, want=want, stream=st.cuda_stream)
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(first, other))
 
 
 # ---- the host mirror -------------------------------------------------------------------------------------------------------

@@ -17,6 +17,7 @@ torch = pytest.importorskip("torch")
 
 from oracle import pyoracle as po
 from ergodic_exploration_amd import capi
+from tests import frontier_scenes as fs
 from tests import gain_scenes as gs
 from tests import geodesic_restatement as geo
 from tests import sense_restatement as sr
@@ -308,6 +309,35 @@ def test_a_generous_budget_is_the_waiting_call():
     got, state = dev.field(cells=a, max_rounds=budget, stream=st.cuda_stream)
     _same(got, waited)
     assert state[0] == 1 and 0 < state[1] < budget and state[2] == 1 and state[3] == 0, state
+
+
+# ---- more sources than a workgroup has lanes, more tiles than a wavefront -------------------------------------------------
+def test_300_sources_on_272_tiles_and_one_round_at_a_time():
+    """tests/frontier_scenes.py's large_revealed(): 506 x 520 cells (16 x 17 tiles) revealed by 300 robots -- a second workgroup
+    of geodesic_seed_kernel --, unknown cells block, the clearance of the true walls.  The field is the cost plane of the
+    partition's restatement (computed once, with the scene); a budget of one round and EEA_GEODESIC_CONTINUE calls of one round
+    each end at the same bits"""
+    sc = fs.large_revealed()
+    dev = _Device(sc.g, sc.known)
+    dev.use_sq(sc.sq)
+    args = dict(poses=sc.poses, clear_sq=sc.clear_sq)
+    flags = capi.GEODESIC_UNKNOWN_BLOCKS
+    got, waited = dev.field(flags=flags, **args)
+    _same(got, sc.geo)
+    assert waited[0] == 1 and waited[2] == sc.n_src == 300 and waited[3] == 0, waited
+    limit = 4 * int(waited[1]) + 64
+    got, state = dev.field(flags=flags, max_rounds=1, **args)
+    assert state[0] == 0 and state[1] == 1 and state[2] == 300 and state[3] == 0, state
+    assert ((got == -1) | (got >= sc.geo)).all() and (got[sc.geo == -1] == -1).all()
+    calls = 1
+    while state[0] == 0:
+        assert calls < limit, "no end after %d calls of one round" % calls
+        got, state = dev.field(flags=flags | capi.GEODESIC_CONTINUE, max_rounds=1, start=got, **args)
+        calls += 1
+        assert state[1] <= 1 and state[2] == 300 and state[3] == 0, state
+    _same(got, sc.geo)
+    assert calls > 2
+    print("large revealed map: final after %d calls of one round (the waiting call: %d rounds changed something)" % (calls, waited[1]))
 
 
 # ---- paths ---------------------------------------------------------------------------------------------------------------

@@ -18,6 +18,7 @@ torch = pytest.importorskip("torch")
 
 from oracle import pyoracle as po
 from ergodic_exploration_amd import capi
+from tests import frontier_scenes as fs
 from tests import gain_scenes as gs
 from tests import geodesic_restatement as geo
 from tests import partition_restatement as part
@@ -333,6 +334,70 @@ def test_a_different_label_in_every_lane():
     for kind in (0, 1):
         _check_goals(dev, kind, _field_of(kind, xs * ys, 3), 1, cost, owner, 64, weights=_WEIGHTS[1:3])
     _check_goals(dev, 0, _field_of(0, xs * ys, 3), 1, cost, np.full(xs * ys, 64, dtype=np.int32), 64, weights=_WEIGHTS[:1])
+
+
+# ---- more sources and labels than a workgroup has lanes, more tiles than a wavefront ----------------------------------------------
+# tests/frontier_scenes.py's large_revealed(): 506 x 520 cells (16 x 17 tiles) revealed by 300 robots, unknown cells block, the
+# clearance of the true walls.  300 sources are a second workgroup of partition_seed_kernel / geodesic_seed_kernel, 257 and 300
+# labels a second workgroup of goals_init_kernel and goals_finish_kernel, and the rounds run over 272 tiles.  The planes of the
+# restatement are computed once, with the scene
+def _large():
+    sc = fs.large_revealed()
+    dev = _Device(sc.g, sc.known)
+    dev.use_sq(sc.sq)
+    return sc, dev, dict(poses=sc.poses, clear_sq=sc.clear_sq, flags=capi.GEODESIC_UNKNOWN_BLOCKS)
+
+
+def test_300_sources_on_272_tiles():
+    """both planes whole against the restatement, d_state[2] the 300 accepted sources (robots 298 and 299 stand in the cells of
+    robots 0 and 1 and own nothing), and d_geo the bits of eea_geodesic_field on the same arguments"""
+    sc, dev, args = _large()
+    cost, owner, state = dev.partition(**args)
+    _same(cost, sc.geo)
+    _same(owner, sc.owner, "owner")
+    assert state[0] == 1 and state[2] == sc.n_src == 300 and state[3] == 0, state
+    assert (owner == 297).any() and (owner < 298).all() and len(np.unique(owner)) == 299
+    plain, plain_state = dev.field(**args)
+    assert np.array_equal(plain, cost) and plain_state[0] == 1 and plain_state[2] == 300 and plain_state[3] == 0, plain_state
+    print("large revealed map: %d rounds of the partition changed something, %d of the field" % (state[1], plain_state[1]))
+
+
+def test_one_round_at_a_time_on_272_tiles():
+    """a budget of one round, then EEA_GEODESIC_CONTINUE calls of one round each from the planes of the call before: unfinished
+    until d_state[0] = 1, then the planes of the waiting call"""
+    sc, dev, args = _large()
+    _, _, waited = dev.partition(**args)
+    limit = 4 * int(waited[1]) + 64
+    cost, owner, state = dev.partition(max_rounds=1, **args)
+    assert state[0] == 0 and state[1] == 1 and state[2] == 300 and state[3] == 0, state
+    assert np.array_equal(cost == -1, owner == -1) and ((cost == -1) | (cost >= sc.geo)).all() and (cost[sc.geo == -1] == -1).all()
+    calls = 1
+    while state[0] == 0:
+        assert calls < limit, "no end after %d calls of one round" % calls
+        cost, owner, state = dev.partition(max_rounds=1, start=(cost, owner), **dict(args, flags=args["flags"] | capi.GEODESIC_CONTINUE))
+        calls += 1
+        assert state[1] <= 1 and state[2] == 300 and state[3] == 0, state
+    _same(cost, sc.geo)
+    _same(owner, sc.owner, "owner")
+    assert calls > 2
+    print("large revealed map: final after %d calls of one round (the waiting call: %d rounds changed something)" % (calls, waited[1]))
+
+
+@pytest.mark.parametrize("stride", [1, 3])
+@pytest.mark.parametrize("kind", [0, 1])
+@pytest.mark.parametrize("n_labels", [256, 257, 300])
+def test_goals_of_more_labels_than_a_workgroup(n_labels, kind, stride):
+    """256 labels are one workgroup of the init and finish launches, 257 one lane of a second, 300 the fleet: areas, goal cells
+    and the bits of the scores against the restatement; owners >= n_labels are ignored; labels 298 and 299 own no cell and get
+    -1 / 0.0 / area 0"""
+    sc = fs.large_revealed()
+    dev = _Device(sc.g, sc.known)
+    fieldv = _field_of(kind, sc.known.size, 5 + kind)
+    (cell, score, area), _ = _check_goals(dev, kind, fieldv, stride, sc.geo, sc.owner, n_labels, weights=_WEIGHTS[1:3])
+    assert area.sum() == ((sc.owner >= 0) & (sc.owner < n_labels)).sum() and (cell[200:] >= 0).sum() > 20
+    if n_labels == 300:
+        assert area[298:].tolist() == [0, 0] and cell[298:].tolist() == [-1, -1] and score[298:].tolist() == [0.0, 0.0]
+        assert (area[:298] > 0).all()
 
 
 # ---- paths -----------------------------------------------------------------------------------------------------------------

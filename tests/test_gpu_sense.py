@@ -177,6 +177,75 @@ def test_mask_and_no_ranges():
     assert (idle.known == S_KNOWN).all()
 
 
+STRIDED = 65536 + 3              # robots: a launch has at most 65536 workgroups, which stride over the robots past that
+
+
+@functools.lru_cache(maxsize=None)
+def _strided_fleet(second_turn_live):
+    """65536 + 3 robots on an 8 x 8 grid.  Robots 0 .. 2 and 65536 .. 65538 are the two turns of workgroups 0 .. 2: three stand
+    in columns 5 and 6 and work, of the three others the first and the last are masked out -- in cells (5, 6) and (7, 7), which
+    the working three do not reach (at R = 1 a robot reveals its cell and the four beside it) -- and the middle one is off the
+    grid (a row of -1).  Everybody else stands in columns 0 .. 2
+    (a few off the grid, one in eight live), so columns 5 .. 7 are revealed by the working three alone: a turn that is skipped or
+    whose stores are lost shows in `known`, not only in the ranges"""
+    rng = np.random.default_rng(STRIDED)
+    g = _geom(8, 8)
+    truth = rng.choice(np.array([0, 0, 0, 100, 50, -1], dtype=np.int8), size=(8, 8))
+    cells = np.stack([rng.integers(0, 8, STRIDED), rng.integers(0, 3, STRIDED)], 1)
+    poses = np.array([[XMIN + (j + 0.5) * RES, YMIN + (i + 0.5) * RES, 0.0] for i, j in cells.tolist()])
+    poses[rng.integers(3, 65536, 40), 0] = XMIN - 0.3                      # off the grid, in the crowd
+    mask = (rng.integers(0, 8, STRIDED) == 0).astype(np.int32)
+    working, idle = ((65536, 65537, 65538), (0, 1, 2)) if second_turn_live else ((0, 1, 2), (65536, 65537, 65538))
+    for b, (i, j) in zip(working, ((0, 6), (3, 6), (7, 5))):
+        poses[b], mask[b] = _centre(g, i, j), 1
+    poses[idle[0]], mask[idle[0]] = _centre(g, 5, 6), 0
+    poses[idle[1]], mask[idle[1]] = [XMIN + 8 * RES + 0.3, 0.0, 0.0], 1
+    poses[idle[2]], mask[idle[2]] = _centre(g, 7, 7), 0
+    for a in (truth, poses, mask):
+        a.setflags(write=False)
+    return g, truth, poses, mask, working, idle
+
+
+@pytest.mark.parametrize("want_ranges", [True, False], ids=["ranges", "no_ranges"])
+@pytest.mark.parametrize("second_turn_live", [True, False], ids=["second_turn_works", "first_turn_works"])
+def test_workgroups_stride_over_the_robots(second_turn_live, want_ranges):
+    """more robots than workgroups in a launch, R = 1 (the LDS kernel, whose loop over a workgroup's robots has a barrier at its
+    top and a `continue` for a robot that is masked out or off the grid): workgroups 0 .. 2 skip their first robot and work on
+    their second, and the other way round; ranges (or, with d_ranges NULL, their sentinel) and `known` whole against the
+    restatement"""
+    g, truth, poses, mask, working, idle = _strided_fleet(second_turn_live)
+    dev = _Device(g, truth)
+    got, want = dev.reveal(1, poses.copy(), mask=mask.copy(), want_ranges=want_ranges)    # (the scene's arrays are read-only)
+    _check_ranges(got, want)
+    dev.check_known()
+    rows = want[GUARD:-GUARD].reshape(STRIDED, 8)
+    if want_ranges:
+        assert (rows[list(working)] != S_RANGES).all() and (rows[[idle[0], idle[2]]] == S_RANGES).all() and (rows[idle[1]] == -1).all()
+    # columns 5 .. 7 are the working three's alone, and the masked robots' own cells stay untouched
+    assert (dev.known[:, 5:] != S_KNOWN).sum() == 12 and dev.known[5, 6] == S_KNOWN and dev.known[7, 7] == S_KNOWN
+    assert (dev.known[:, :4] != S_KNOWN).all()
+    alone = np.full_like(dev.known, S_KNOWN)
+    sr.reveal(g, 1, truth, alone, poses[list(working)])
+    assert np.array_equal(alone[:, 5:], dev.known[:, 5:])
+
+
+def test_workgroups_stride_over_the_robots_in_global_memory():
+    """the same fleet at R = 128, where the rays march in global memory and the kernel has a loop of its own: d_ranges NULL
+    (65539 rows of 1024 ranges are not worth their bytes), `known` whole, second turn working and first turn working"""
+    for second_turn_live in (True, False):
+        g, truth, poses, mask, working, idle = _strided_fleet(second_turn_live)
+        few = np.array(mask)
+        few[3:65536] = 0                                                   # the crowd stays out: 1024 rays per robot in the restatement
+        dev = _Device(g, truth)
+        d_pose, d_mask = torch.as_tensor(poses.copy()).cuda(), torch.as_tensor(few).cuda()
+        torch.cuda.synchronize()
+        capi.sense_reveal_batch(dev.cfg, 128, dev.d_truth, dev.d_known, d_pose, None, d_mask)
+        torch.cuda.synchronize()
+        sr.reveal(g, 128, truth, dev.known, poses, few)
+        dev.check_known()
+        assert (dev.known != S_KNOWN).sum() > 12
+
+
 @pytest.mark.parametrize("R", [32, 33, 65, 127, 128])
 def test_each_side_of_every_switch(R):
     """the workgroup has 256 threads, a thread per ray: R = 32 is exactly one round of rays, 33 one round and a tail, 65 two
@@ -236,6 +305,31 @@ def test_census_against_count_nonzero(xs, ys, shift):
     want = (np.count_nonzero(cells < 0), np.count_nonzero((cells >= 0) & below), np.count_nonzero(~below))
     assert tuple(int(v) for v in got[1:4]) == want == sr.census(g, grid)
     assert got[0] == got[4] == 123456789 and want[0] + want[1] + want[2] == grid.size
+
+
+@pytest.mark.parametrize("shift", [0, 5])
+def test_census_past_the_launch_cap(shift):
+    """8192 x 1025 cells: 524 800 loads of 16 bytes for the 2048 x 256 threads a launch is capped at, so the first threads take a
+    second step of the body loop (every smaller grid gives each thread at most one load).  The grid starts 37 and 42 bytes into
+    its allocation; d_counts sits between guard words and is overwritten, not added to"""
+    xs, ys = 8192, 1025
+    assert xs * ys // 16 - 1 > 2048 * 256
+    rng = np.random.default_rng(xs + ys + shift)
+    g = _geom(xs, ys)
+    grid = rng.choice(np.array([-1, -1, 0, 0, 0, 79, 80, 100, -128, 127, 50], dtype=np.int8), size=(ys, xs))
+    grid[-1, -600:] = 100                      # the cells of the second step's last loads and of the tail: unlike the rest
+    grid[0, :300] = -1                         # ... and of the head and the first loads
+    buf = torch.as_tensor(np.concatenate([np.full(GUARD + shift, 100, np.int8), grid.reshape(-1), np.full(GUARD, -1, np.int8)])).cuda()
+    counts = torch.full((5,), 123456789, dtype=torch.int64, device="cuda")
+    for _ in range(2):
+        capi.grid_census(_cfg(g), buf[GUARD + shift:GUARD + shift + grid.size], counts[1:4])
+    torch.cuda.synchronize()
+    got = counts.cpu().numpy()
+    cells = grid.reshape(-1)
+    below = cells.astype(np.float64) / 100.0 < THR
+    want = (np.count_nonzero(cells < 0), np.count_nonzero((cells >= 0) & below), np.count_nonzero(~below))
+    assert tuple(int(v) for v in got[1:4]) == want == sr.census(g, grid)
+    assert got[0] == got[4] == 123456789 and want[0] + want[1] + want[2] == grid.size and min(want) > 1000000
 
 
 def _entropy_target(occ):
