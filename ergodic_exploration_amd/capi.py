@@ -278,6 +278,12 @@ def lib():
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             L.eea_frontier_goals.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_double, C.c_double,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "eea_frontier_auction"):    # additive to ABI 6 as well
+            L.eea_frontier_auction_ws_bytes.argtypes = [C.POINTER(CollisionCfg), C.c_uint, C.c_uint, C.POINTER(C.c_size_t)]
+            L.eea_frontier_auction.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_void_p, C.c_void_p, C.c_int, C.c_uint, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_uint,
+                                               C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]
         if hasattr(L, "eea_footprint_check_batch"):   # additive to ABI 6 as well
             L.eea_footprint_radii.argtypes = [C.POINTER(Footprint), C.POINTER(C.c_double), C.POINTER(C.c_double)]
             L.eea_footprint_check_batch.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.POINTER(Footprint), C.c_void_p, C.c_void_p,
@@ -891,6 +897,32 @@ def frontier_goals(regions, state, max_regions, goal_cell, goal_region, goal_sco
     check(lib().eea_frontier_goals(device, _ptr(regions), _ptr(state), int(max_regions), int(goal_cell.shape[0]), int(min_size),
                                    float(w_size), float(w_cost), _ptr(goal_cell), _ptr(goal_region), _ptr(goal_score),
                                    C.c_void_p(stream or 0)))
+
+
+def frontier_auction_ws_bytes(cfg, P, max_regions):
+    """eea_frontier_auction_ws_bytes: the bytes of workspace frontier_auction needs for the grid of cfg, P robots and
+    max_regions records; host only"""
+    n = C.c_size_t()
+    check(lib().eea_frontier_auction_ws_bytes(C.byref(cfg), int(P), int(max_regions), C.byref(n)))
+    return n.value
+
+
+def frontier_auction(cfg, grid, region, regions, fstate, max_regions, pose, goal_region, goal_cell, goal_cost, ws, state, path=None,
+                     length=None, sq=None, clear_sq=0, flags=0, n_auction=1, min_size=1, cells_per_robot=0, max_rounds=0, device=0,
+                     stream=None):
+    """eea_frontier_auction: per robot of pose [P][3] a region of one frontier_regions call on the same int8 device grid (its
+    rank plane region, its records regions or None with max_regions 0, its state fstate), by n_auction rounds of: the partition
+    sourced at the open regions, a bid of every unassigned robot for its nearest one, and each region taking the nearest
+    bidders it has room for (1, or ceil(size / cells_per_robot)).  goal_region / goal_cell / goal_cost int32 [P] (-1: none); path
+    float64 [P][n_steps][3] (or None: n_steps 0) = the way to goal_cell as geodesic_path_batch's rows; length int32 [P] or None;
+    ws: frontier_auction_ws_bytes(cfg, P, max_regions) bytes, 8-byte aligned; state uint32 [4] (every build final, tile rounds
+    that changed something, robots assigned, rounds that were not idle).  max_rounds == 0 builds every field to the end and
+    waits on the stream; max_rounds > 0 enqueues that many tile rounds per auction round and does not wait.  Device tensors"""
+    check(lib().eea_frontier_auction(device, C.byref(cfg), _ptr(grid), _ptr(sq), int(clear_sq), int(flags), _ptr(region), _ptr(regions),
+                                     _ptr(fstate), int(max_regions), _ptr(pose), 0 if pose is None else int(pose.shape[0]),
+                                     int(n_auction), int(min_size), int(cells_per_robot), int(max_rounds),
+                                     0 if path is None else int(path.shape[1]), _ptr(goal_region), _ptr(goal_cell), _ptr(goal_cost),
+                                     _ptr(path), _ptr(length), _ptr(ws), _ptr(state), C.c_void_p(stream or 0)))
 
 
 def footprint_radii(fp):

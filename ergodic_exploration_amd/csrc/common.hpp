@@ -578,6 +578,38 @@ hipError_t launch_frontier_goals(const eea_frontier_region* d_regions, const uns
                                  unsigned min_size, double w_size, double w_cost, int* d_goal_cell, int* d_goal_region,
                                  double* d_goal_score, hipStream_t s);
 
+// ---- frontier auction: a region for every robot, by distance and capacity (auction_kernel.hip) ----
+// what a call reads of its arguments beside the buffers (g: clear_sq and unknown_blocks)
+struct AuctionArgs
+{
+  GeodesicArgs g;
+  unsigned P, max_regions, min_size, cells_per_robot, n_steps;
+};
+// a key per cell, two unpacked planes, per robot a cell and a bid, per record slot two capacities and a count, eight words,
+// and the geodesic field's planes; d_ws is 8-byte aligned
+size_t auction_ws_bytes(unsigned xsize, unsigned ysize, unsigned P, unsigned max_regions);
+// eight device words of d_ws: the tile rounds' state of the current build ([0]: final), then {unassigned placed robots, open
+// regions} as the even and as the odd auction rounds read them
+const unsigned* auction_words(const CollisionParams& c, const AuctionArgs& a, void* d_ws);
+// d_state = {1, 0, 0, 0} and nothing else: what a call with no robot leaves
+hipError_t launch_auction_state(unsigned* d_state, hipStream_t s);
+// once per call: the traversability plane with the placed robots' cells open, their cells, every output in its "unassigned"
+// state (-1; the pose in every row), the capacities, both counters, d_state = {1, 0, 0, 0}.  a.P > 0
+hipError_t launch_auction_setup(const CollisionParams& c, const AuctionArgs& a, const int8_t* d_grid, const int* d_sq,
+                                const eea_frontier_region* d_regions, const unsigned* d_fstate, const double* d_pose,
+                                int* d_goal_region, int* d_goal_cell, int* d_goal_cost, double* d_path, int* d_len, void* d_ws,
+                                unsigned* d_state, hipStream_t s);
+// auction round `round`: the key plane seeded from the open regions and the state before tile round 0 (idle: no tile pending)
+hipError_t launch_auction_begin(const CollisionParams& c, const AuctionArgs& a, unsigned round, const int8_t* d_grid,
+                                const int* d_region, void* d_ws, hipStream_t s);
+// tile rounds first .. first + count - 1 of the current build, one launch each, then its state words brought up to date
+hipError_t launch_auction_rounds(const CollisionParams& c, const AuctionArgs& a, unsigned first, unsigned count, void* d_ws,
+                                 hipStream_t s);
+// behind the build of auction round `round`: unpack, bid, rank with accept and walk, update; d_state brought up to date
+hipError_t launch_auction_settle(const CollisionParams& c, const AuctionArgs& a, unsigned round, const double* d_pose,
+                                 int* d_goal_region, int* d_goal_cell, int* d_goal_cost, double* d_path, int* d_len, void* d_ws,
+                                 unsigned* d_state, hipStream_t s);
+
 // ======================================================================================
 // device helpers
 // ======================================================================================

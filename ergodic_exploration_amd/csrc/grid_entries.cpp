@@ -1,5 +1,5 @@
 // C ABI (include/ergodic_amd.h) of the entries that take a device or a layer and no engine: collision, clearance and distance
-// queries, the geodesic field and its paths, the geodesic partition with its goals and paths, the frontier regions and their goals, the footprint and its planning entries, the range sensor, the census, the evidence grid, the gain and mutual-information fields, and the two layers with their
+// queries, the geodesic field and its paths, the geodesic partition with its goals and paths, the frontier regions and their goals, the frontier auction, the footprint and its planning entries, the range sensor, the census, the evidence grid, the gain and mutual-information fields, and the two layers with their
 // batch entries.  Argument checking (entry_util.hpp) and kernel dispatch; every refusal comes before the device is selected.
 #include "../../include/ergodic_amd.h"
 
@@ -372,6 +372,69 @@ eea_status eea_frontier_goals(int device, const eea_frontier_region* d_regions, 
   EEA_HIP(hipSetDevice(device));
   EEA_HIP(eea::launch_frontier_goals(d_regions, d_state, max_regions, P, min_size, w_size, w_cost, d_goal_cell, d_goal_region,
                                      d_goal_score, static_cast<hipStream_t>(stream)));
+  return EEA_OK;
+}
+
+// ---- frontier auction: a region for every robot, by distance and capacity (auction_kernel.hip) ----
+eea_status eea_frontier_auction_ws_bytes(const eea_collision_cfg* cfg, unsigned P, unsigned max_regions, size_t* bytes)
+{
+  const eea_status st = geodesic_cfg_refusal(cfg);
+  if (st != EEA_OK) return st;
+  if (bytes == nullptr) return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  *bytes = eea::auction_ws_bytes(cfg->xsize, cfg->ysize, P, max_regions);
+  return EEA_OK;
+}
+
+eea_status eea_frontier_auction(int device, const eea_collision_cfg* cfg, const int8_t* d_grid, const int* d_sq, int clear_sq,
+                                unsigned flags, const int* d_region, const eea_frontier_region* d_regions,
+                                const unsigned* d_fstate, unsigned max_regions, const double* d_pose, unsigned P,
+                                unsigned n_auction, unsigned min_size, unsigned cells_per_robot, unsigned max_rounds,
+                                unsigned n_steps, int* d_goal_region, int* d_goal_cell, int* d_goal_cost, double* d_path,
+                                int* d_len, void* d_ws, unsigned* d_state, void* stream)
+{
+  const eea_status st = geodesic_cfg_refusal(cfg);
+  if (st != EEA_OK) return st;
+  if (d_grid == nullptr || d_region == nullptr || d_fstate == nullptr || (d_pose == nullptr && P != 0u) || d_goal_region == nullptr ||
+      d_goal_cell == nullptr || d_goal_cost == nullptr || d_ws == nullptr || d_state == nullptr) {
+    return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  }
+  if (d_regions == nullptr && max_regions != 0u) return fail(EEA_ERR_INVALID_ARGUMENT, "d_regions is null with max_regions > 0");
+  if (d_path == nullptr && n_steps != 0u) return fail(EEA_ERR_INVALID_ARGUMENT, "d_path is null with n_steps > 0");
+  if ((flags & ~static_cast<unsigned>(EEA_GEODESIC_UNKNOWN_BLOCKS)) != 0u) return fail(EEA_ERR_INVALID_ARGUMENT, "unknown flag bits");
+  if (clear_sq < 0) return fail(EEA_ERR_INVALID_ARGUMENT, "clear_sq must be >= 0");
+  if (n_auction == 0u) return fail(EEA_ERR_INVALID_ARGUMENT, "n_auction must be positive");
+  if (reinterpret_cast<uintptr_t>(d_ws) % 8u != 0u) return fail(EEA_ERR_INVALID_ARGUMENT, "d_ws must be 8-byte aligned");
+  if (P > 65536u) return fail(EEA_ERR_UNSUPPORTED, "more than 65536 robots: a rank is counted against every bid");
+  if (max_regions > 0x7fffffffu) return fail(EEA_ERR_UNSUPPORTED, "more than 2^31 - 1 records: a label is a non-negative int");
+  const eea::CollisionParams c = grid_params(cfg);
+  const eea::AuctionArgs a{ eea::GeodesicArgs{ clear_sq, (flags & EEA_GEODESIC_UNKNOWN_BLOCKS) != 0u, false, P, 0u }, P, max_regions,
+                            min_size, cells_per_robot, n_steps };
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  EEA_HIP(hipSetDevice(device));
+  if (P == 0u) {
+    EEA_HIP(eea::launch_auction_state(d_state, s));
+    return EEA_OK;
+  }
+  EEA_HIP(eea::launch_auction_setup(c, a, d_grid, d_sq, d_regions, d_fstate, d_pose, d_goal_region, d_goal_cell, d_goal_cost, d_path,
+                                    d_len, d_ws, d_state, s));
+  const unsigned* const d_words = eea::auction_words(c, a, d_ws);
+  for (unsigned round = 0; round < n_auction; ++round) {
+    if (max_rounds == 0u) {
+      // the waiting form looks at the round's counters first: an idle round changes nothing, nor does any behind it
+      unsigned counters[2] = { 0u, 0u };
+      EEA_HIP(hipMemcpyAsync(counters, d_words + 4u + 2u * (round & 1u), sizeof(counters), hipMemcpyDeviceToHost, s));
+      EEA_HIP(hipStreamSynchronize(s));
+      if (counters[0] == 0u || counters[1] == 0u) break;
+    }
+    EEA_HIP(eea::launch_auction_begin(c, a, round, d_grid, d_region, d_ws, s));
+    const eea_status built = geodesic_run_rounds(c, max_rounds, d_words, s, "eea_frontier_auction: the rounds did not reach a fixed point",
+                                                 [&](unsigned first, unsigned count) {
+                                                   return eea::launch_auction_rounds(c, a, first, count, d_ws, s);
+                                                 });
+    if (built != EEA_OK) return built;
+    EEA_HIP(eea::launch_auction_settle(c, a, round, d_pose, d_goal_region, d_goal_cell, d_goal_cost, d_path, d_len, d_ws, d_state, s));
+  }
+  if (max_rounds == 0u) EEA_HIP(hipStreamSynchronize(s));
   return EEA_OK;
 }
 

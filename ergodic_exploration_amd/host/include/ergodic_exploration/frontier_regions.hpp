@@ -3,7 +3,8 @@
 // map, the member that is cheapest to reach with the robot that owns it; and per robot the region it should go for
 // (eea_frontier_regions / eea_frontier_goals).  No reference class.  Constructed from Collision's parameters, like
 // GeodesicPartition.  The object owns the two device planes, the records, the workspace, the state words and the goals of its
-// last goals() call.
+// last goals() call.  auction() gives every robot -- of any fleet, not only the partition's -- a region by distance and capacity
+// (eea_frontier_auction) and owns one more block: its workspace, poses and outputs.
 #pragma once
 
 #include <stdexcept>
@@ -114,6 +115,68 @@ public:
   // the goal cells of the last goals() call on the device, [robots]: what eea_partition_path_batch takes as d_goal_cell
   const int* goalCells() const { return d_goal_cell_; }
 
+  struct Assignment
+  {
+    std::vector<int> region;  // [P] the rank of the region the robot goes for, -1: none
+    std::vector<int> cell;    // [P] row-major index of its goal, the member of that region its walk ends on, -1: none
+    std::vector<int> cost;    // [P] the cost of the way there, -1: none
+    std::vector<int> len;     // [P] the moves written into path, -1: none
+    mat path;                 // 3 x (P * n_steps): robot q's way-points in columns q * n_steps ..; its pose without a goal
+    bool final = false;       // every field of the call was built to the end
+    unsigned assigned = 0, rounds = 0;  // robots with a goal; auction rounds that were not idle
+  };
+  // a region of the last update for every robot of poses (3 x P; any robots, not only a partition's), by distance and capacity
+  // (eea_frontier_auction): n_auction rounds in which every robot without a region bids for the nearest region with room left
+  // and a region takes the nearest bidders -- 1, or ceil(size / cells_per_robot) of them over the whole call.  grid is the map
+  // of the last update; distance, clear_sq, flags: as GeodesicField::update.  Waits
+  Assignment auction(const GridMap& grid, const mat& poses, unsigned n_auction, unsigned min_size, unsigned cells_per_robot,
+                     unsigned n_steps, unsigned flags = 0, const DistanceField* distance = nullptr, int clear_sq = 0)
+  {
+    if (!built_) throw std::logic_error("FrontierRegions: update() has not labelled a map");
+    const eea_collision_cfg cfg = collision_.deviceConfig(grid);
+    if (static_cast<size_t>(cfg.xsize) * cfg.ysize != cells_ || cfg.xsize != xsize_) {
+      throw std::logic_error("FrontierRegions: auction() needs the map of the last update");
+    }
+    Assignment out;
+    const unsigned P = static_cast<unsigned>(poses.n_cols());
+    if (P == 0) return out;
+    size_t ws_bytes = 0;
+    throw_on_error(eea_frontier_auction_ws_bytes(&cfg, P, max_regions_, &ws_bytes));
+    const size_t path_bytes = sizeof(double) * 3 * P * n_steps;
+    // one block: the workspace (an allocation's start: 8-byte aligned), the poses, the path, the four int outputs, the state
+    const size_t ws_room = (ws_bytes + 7) / 8 * 8;
+    const size_t need = ws_room + sizeof(double) * 3 * P + path_bytes + sizeof(int) * 4 * P + sizeof(unsigned) * 4;
+    hip_check(hipSetDevice(device_ordinal()));
+    if (need > auction_capacity_) {
+      release_auction();
+      hip_check(hipMalloc(&d_auction_, need));
+      auction_capacity_ = need;
+    }
+    char* const base = static_cast<char*>(d_auction_);
+    double* const d_pose = reinterpret_cast<double*>(base + ws_room);
+    double* const d_path = d_pose + 3 * static_cast<size_t>(P);
+    int* const d_out = reinterpret_cast<int*>(reinterpret_cast<char*>(d_path) + path_bytes);
+    unsigned* const d_state = reinterpret_cast<unsigned*>(d_out + 4 * static_cast<size_t>(P));
+    hip_check(hipMemcpy(d_pose, poses.memptr(), sizeof(double) * 3 * P, hipMemcpyHostToDevice));
+    throw_on_error(eea_frontier_auction(device_ordinal(), &cfg, device_cells(grid), distance ? distance->squaredDistances() : nullptr,
+                                        clear_sq, flags, d_region_, d_regions_, d_state_, max_regions_, d_pose, P, n_auction, min_size,
+                                        cells_per_robot, 0, n_steps, d_out, d_out + P, d_out + 2 * static_cast<size_t>(P),
+                                        n_steps != 0 ? d_path : nullptr, d_out + 3 * static_cast<size_t>(P), d_auction_, d_state, nullptr));
+    std::vector<int>* const outs[4] = { &out.region, &out.cell, &out.cost, &out.len };
+    for (unsigned k = 0; k < 4; ++k) {
+      outs[k]->resize(P);
+      hip_check(hipMemcpy(outs[k]->data(), d_out + k * static_cast<size_t>(P), sizeof(int) * P, hipMemcpyDeviceToHost));
+    }
+    out.path = mat(3, static_cast<size_t>(P) * n_steps);
+    if (path_bytes != 0) hip_check(hipMemcpy(out.path.memptr(), d_path, path_bytes, hipMemcpyDeviceToHost));
+    unsigned state[4] = { 0, 0, 0, 0 };
+    hip_check(hipMemcpy(state, d_state, sizeof(state), hipMemcpyDeviceToHost));
+    out.final = state[0] != 0;
+    out.assigned = state[2];
+    out.rounds = state[3];
+    return out;
+  }
+
 private:
   int cell_of(const int* plane, unsigned i, unsigned j) const
   {
@@ -146,10 +209,17 @@ private:
     d_goal_cell_ = d_goal_region_ = nullptr;
     robots_capacity_ = 0;
   }
+  void release_auction()
+  {
+    if (d_auction_) (void)hipFree(d_auction_);
+    d_auction_ = nullptr;
+    auction_capacity_ = 0;
+  }
   void release()
   {
     release_planes();
     release_robots();
+    release_auction();
     built_ = false;
   }
   Collision collision_;
@@ -157,6 +227,8 @@ private:
   int *d_root_ = nullptr, *d_region_ = nullptr, *d_goal_cell_ = nullptr, *d_goal_region_ = nullptr;
   eea_frontier_region* d_regions_ = nullptr;
   void* d_ws_ = nullptr;
+  void* d_auction_ = nullptr;  // auction(): its workspace, poses and outputs
+  size_t auction_capacity_ = 0;
   unsigned* d_state_ = nullptr;
   double* d_goal_score_ = nullptr;
   unsigned state_[4] = { 0, 0, 0, 0 };

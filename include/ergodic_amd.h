@@ -1270,6 +1270,74 @@ eea_status eea_frontier_goals(int device, const eea_frontier_region* d_regions, 
                               unsigned P, unsigned min_size, double w_size, double w_cost, int* d_goal_cell, int* d_goal_region,
                               double* d_goal_score, void* stream);
 
+/* ---- frontier auction: a region for every robot, by distance and capacity (additive to ABI 6: detect these entries by
+ * symbol) -----------------------------------------------------------------------------------------------------------------
+ * No reference counterpart.  eea_frontier_goals gives a robot a region only if the robot OWNS the region's entry cell: a robot
+ * whose share of free space holds no frontier stands still, and nothing limits how many robots go for one region or sends a
+ * second robot to a large one.  The missing quantity is the distance from ANY robot to ANY region; a partition sourced at the
+ * regions gives it for the whole fleet in one build (the nearest-frontier rule), and repeating the build with the full regions
+ * closed makes it an auction.  The result is a function of the inputs alone: integers with a unique answer, way-points from the
+ * literal arithmetic of eea_geodesic_path_batch.  Bit-reproducible.
+ * eea_frontier_auction: d_region, d_regions, d_fstate and max_regions are the rank plane, the records, the state and the bound
+ *   of one eea_frontier_regions call on the same grid (d_fstate[1] is read on the device); d_grid, d_sq, clear_sq are
+ *   eea_geodesic_field's; flags takes only EEA_GEODESIC_UNKNOWN_BLOCKS.
+ *   robot cell    c_q: the cell of pose q by eea_geodesic_field's source rule.  A robot is PLACED if that cell is in the grid and
+ *                 does not block; a robot that is not placed never bids.
+ *   enterable     a cell that is traversable exactly as eea_geodesic_field defines it, or the cell of a placed robot (a robot
+ *                 is where it is: the test is waived for its cell, as it is for a source) -- for every robot, in every auction
+ *                 round, so the plane is built once per call.
+ *   eligible      a region r < min(d_fstate[1], max_regions) with size >= min_size.  Its capacity cap_r is 1 if
+ *                 cells_per_robot == 0, else ceil(size_r / cells_per_robot) (in 64 bits); rem_r = cap_r before round 0.
+ *   round a       a = 0 .. n_auction - 1.  If no placed robot is unassigned or no eligible region has rem_r > 0 the round is
+ *                 idle and does nothing.  Otherwise:
+ *     seeds       every cell g with d_region[g] = r, r eligible, rem_r > 0 and !blocks(d_grid[g]) holds the key (0, r), whether
+ *                 it is enterable or not; nothing moves INTO a seed that is not enterable.
+ *     field       the unique fixed point of eea_geodesic_partition's key rule on these seeds: the 5-7 chamfer moves into
+ *                 enterable cells only, a diagonal one between two enterable cells, the key (cost, label) under lexicographic
+ *                 order with label = region rank.
+ *     bid         an unassigned placed robot q with a key (cost, r) at c_q bids for r with K_q = cost << 32 | q.
+ *     accept      region r accepts the min(rem_r, bidders_r) bidders of the smallest K; rem_r drops by that number.
+ *     an accepted robot gets d_goal_region[q] = r, d_goal_cost[q] = cost, and the walk from c_q down the field: the step rule
+ *                 is eea_partition_path_batch's (the first of the eight moves onto a cell of label r that accounts for the
+ *                 cost, a diagonal one between two cells of the field), until the cost is 0.  d_goal_cell[q] is the cell
+ *                 where the walk ends -- a member of r -- also for a walk longer than n_steps.  Rows, headings, the repeat rule
+ *                 and d_len are eea_geodesic_path_batch's; the moves are forward ones, nothing is reversed.  A robot on a
+ *                 seed gets len 0, its own cell as goal, and n_steps rows of its cell's centre with the pose's heading.
+ *   A robot that is unassigned after the last round, or not placed, gets goal_region = goal_cell = goal_cost = len = -1 and
+ *   its pose in all rows.  EVERY element of d_goal_region, d_goal_cell, d_goal_cost [P], d_path [P][n_steps][3] and d_len [P] is
+ *   overwritten.  n_steps == 0 is allowed with d_path == NULL; d_len may be NULL.
+ *   max_rounds    as eea_geodesic_partition's.  0: every field is built to the end; the call waits on `stream` and reads state
+ *                 words on the host every 16 tile rounds, and stops at the first idle auction round.  > 0: the call enqueues
+ *                 3 + n_auction * (max_rounds + 6) launches on `stream` and neither allocates, waits nor reads; an idle auction
+ *                 round leaves every tile flag 0, so its round launches exit at once.
+ *   d_state       (uint32 [4], device) [0] 1 iff every field build of the call was final; [1] the tile rounds that changed
+ *                 something, summed over the call; [2] the robots assigned; [3] the auction rounds that were not idle.  With
+ *                 [0] == 1 the outputs are bitwise the definition above.  With [0] == 0 each output element is -1, or the pose,
+ *                 or in range; nothing more is promised, and the caller must look at [0].
+ *   The launches: once per call the traversability plane, one lane per robot (its cell, the byte of that cell, the outputs'
+ *   unassigned state) and one lane per record (rem_r); per auction round a pass that seeds the key plane, the tile rounds of
+ *   eea_geodesic_partition, a pass that unpacks the keys, one lane per robot that bids (the bidders of a region counted with
+ *   integer atomics, combined per wavefront), one lane per robot that counts its rank -- the bids of the same region with a
+ *   smaller K, against all P bids streamed through LDS; K is unique, so no atomics -- and, accepted, writes its outputs and
+ *   walks, and one lane per record that lowers rem_r and counts the open regions and the unassigned robots for the next
+ *   round's idle test.  Nothing waits inside a kernel.
+ *   eea_frontier_auction_ws_bytes: host only; the bytes d_ws must hold (positive, monotone in the grid's size, in P and in
+ *   max_regions).  d_ws is device memory aligned to 8 bytes; its contents mean nothing between calls.
+ *   P == 0 is EEA_OK: it writes d_state = {1, 0, 0, 0} and nothing else.
+ *   Before the device is selected, with no output touched -- EEA_ERR_INVALID_ARGUMENT: cfg, d_grid, d_region, d_fstate, d_pose
+ *   (with P > 0), d_goal_region, d_goal_cell, d_goal_cost, d_ws or d_state null; d_regions null with max_regions > 0; d_path
+ *   null with n_steps > 0; clear_sq < 0; unknown flag bits; n_auction == 0; d_ws not 8-byte aligned; the configuration errors of
+ *   the geodesic calls.  EEA_ERR_UNSUPPORTED: their limits; P > 65536 (the bound of the all-pairs rank: to be lifted only with
+ *   a sort); max_regions > 2^31 - 1.
+ * eea_abi_version() stays 6. */
+eea_status eea_frontier_auction_ws_bytes(const eea_collision_cfg* cfg, unsigned P, unsigned max_regions, size_t* bytes);
+eea_status eea_frontier_auction(int device, const eea_collision_cfg* cfg, const int8_t* d_grid, const int* d_sq, int clear_sq,
+                                unsigned flags, const int* d_region, const eea_frontier_region* d_regions,
+                                const unsigned* d_fstate, unsigned max_regions, const double* d_pose, unsigned P,
+                                unsigned n_auction, unsigned min_size, unsigned cells_per_robot, unsigned max_rounds,
+                                unsigned n_steps, int* d_goal_region, int* d_goal_cell, int* d_goal_cost, double* d_path,
+                                int* d_len, void* d_ws, unsigned* d_state, void* stream);
+
 /* ---- footprint collision: a convex polygon base, checked through the distance field ----------------------------------
  * No reference counterpart (the reference README lists "model the robot's base as a polygon for collision detection" and "use
  * a distance field for detecting obstacle cells" under "Future Improvements").  Every other collision call treats the robot
