@@ -81,6 +81,8 @@ COLLISION_OFF_GRID = 3       # the distance queries only: the pose's cell is not
 DISTANCE_MAX_SIDE = 8192     # EEA_DISTANCE_MAX_SIDE
 GEODESIC_TILE_X, GEODESIC_TILE_Y = 32, 32           # EEA_GEODESIC_TILE_X / _Y: the tile of the geodesic field's rounds
 GEODESIC_UNKNOWN_BLOCKS, GEODESIC_CONTINUE = 1, 2   # EEA_GEODESIC_*: flags of geodesic_field
+GOTO_MAX_CELLS = 16384                              # EEA_GOTO_MAX_CELLS: the cells of a window of geodesic_goto_batch
+GOTO_OK, GOTO_NO_ROBOT, GOTO_NO_GOAL, GOTO_WINDOW, GOTO_CUT_OFF = range(5)   # EEA_GOTO_*: a robot's status
 FOOTPRINT_MAX_VERTICES = 16  # EEA_FOOTPRINT_MAX_VERTICES
 FRONTIER_OF_GRID, FRONTIER_OF_MASK = 0, 1           # EEA_FRONTIER_OF_*: kind of frontier_regions
 
@@ -284,6 +286,10 @@ def lib():
                                                C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_uint,
                                                C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "eea_geodesic_goto_batch"):    # additive to ABI 6 as well
+            L.eea_geodesic_goto_batch.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.c_void_p, C.c_void_p, C.c_int, C.c_uint, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         if hasattr(L, "eea_footprint_check_batch"):   # additive to ABI 6 as well
             L.eea_footprint_radii.argtypes = [C.POINTER(Footprint), C.POINTER(C.c_double), C.POINTER(C.c_double)]
             L.eea_footprint_check_batch.argtypes = [C.c_int, C.POINTER(CollisionCfg), C.POINTER(Footprint), C.c_void_p, C.c_void_p,
@@ -923,6 +929,22 @@ def frontier_auction(cfg, grid, region, regions, fstate, max_regions, pose, goal
                                      int(n_auction), int(min_size), int(cells_per_robot), int(max_rounds),
                                      0 if path is None else int(path.shape[1]), _ptr(goal_region), _ptr(goal_cell), _ptr(goal_cost),
                                      _ptr(path), _ptr(length), _ptr(ws), _ptr(state), C.c_void_p(stream or 0)))
+
+
+def geodesic_goto_batch(cfg, grid, pose, goal, cost, status, state, path=None, length=None, mask=None, sq=None, clear_sq=0, flags=0,
+                        margin=0, device=0, stream=None):
+    """eea_geodesic_goto_batch: per robot of pose [P][3] the shortest 5-7 chamfer path to its own cell goal[q] (int32 [P], row-major)
+    inside the window of the two cells grown by margin and clipped to the int8 device grid (at most GOTO_MAX_CELLS cells).  cost
+    int32 [P] = the path's cost or -1; status int32 [P] = GOTO_OK / _NO_ROBOT / _NO_GOAL / _WINDOW / _CUT_OFF; path float64
+    [P][n_steps][3] (or None: n_steps 0) = geodesic_path_batch's rows; length int32 [P] or None; mask int32 [P] or None (0 leaves
+    a robot out: nothing of it is read or written); state uint32 [4] = the robots OK, WINDOW, CUT_OFF, NO_ROBOT + NO_GOAL.  sq,
+    clear_sq, flags (GEODESIC_UNKNOWN_BLOCKS only) as geodesic_field.  No workspace.  Device tensors; asynchronous"""
+    if not hasattr(lib(), "eea_geodesic_goto_batch"):
+        raise RuntimeError("libergodic_amd.so has no eea_geodesic_goto_batch: rebuild it (there is no fallback)")
+    check(lib().eea_geodesic_goto_batch(device, C.byref(cfg), _ptr(grid), _ptr(sq), int(clear_sq), int(flags), _ptr(pose), _ptr(goal),
+                                        _ptr(mask), 0 if pose is None else int(pose.shape[0]), int(margin),
+                                        0 if path is None else int(path.shape[1]), _ptr(cost), _ptr(status), _ptr(path), _ptr(length),
+                                        _ptr(state), C.c_void_p(stream or 0)))
 
 
 def footprint_radii(fp):

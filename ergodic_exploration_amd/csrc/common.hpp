@@ -610,6 +610,24 @@ hipError_t launch_auction_settle(const CollisionParams& c, const AuctionArgs& a,
                                  int* d_goal_region, int* d_goal_cell, int* d_goal_cost, double* d_path, int* d_len, void* d_ws,
                                  unsigned* d_state, hipStream_t s);
 
+// ---- goal paths: every robot's way to its own goal, one LDS window each (goto_kernel.hip) ----
+// the cells of the largest window (the header publishes it): one 4-byte word per cell, 64 KB of LDS, two workgroups per CU
+constexpr unsigned kGotoMaxCells = 16384;
+// the workgroups of the largest launch: eight per CU at 256 CUs; a launch of fewer workgroups than robots strides over them
+constexpr unsigned kGotoMaxBlocks = 2048;
+// what a call reads of its arguments beside the buffers (g: clear_sq and unknown_blocks)
+struct GotoArgs
+{
+  GeodesicArgs g;
+  unsigned P, margin, n_steps;
+};
+// d_state = {0, 0, 0, 0}, then (a.P > 0) one workgroup per robot: d_cost, d_status, d_len (may be null) [P], d_path [P][n_steps][3]
+// and the four counts of d_state {OK, WINDOW, CUT_OFF, NO_ROBOT + NO_GOAL}; d_mask [P] (may be null): 0 leaves a robot out.  Two
+// launches, no workspace
+hipError_t launch_goto(const CollisionParams& c, const GotoArgs& a, const int8_t* d_grid, const int* d_sq, const double* d_pose,
+                       const int* d_goal, const int* d_mask, int* d_cost, int* d_status, double* d_path, int* d_len,
+                       unsigned* d_state, hipStream_t s);
+
 // ======================================================================================
 // device helpers
 // ======================================================================================

@@ -1,5 +1,5 @@
 // C ABI (include/ergodic_amd.h) of the entries that take a device or a layer and no engine: collision, clearance and distance
-// queries, the geodesic field and its paths, the geodesic partition with its goals and paths, the frontier regions and their goals, the frontier auction, the footprint and its planning entries, the range sensor, the census, the evidence grid, the gain and mutual-information fields, and the two layers with their
+// queries, the geodesic field and its paths, the geodesic partition with its goals and paths, the frontier regions and their goals, the frontier auction, the goal paths, the footprint and its planning entries, the range sensor, the census, the evidence grid, the gain and mutual-information fields, and the two layers with their
 // batch entries.  Argument checking (entry_util.hpp) and kernel dispatch; every refusal comes before the device is selected.
 #include "../../include/ergodic_amd.h"
 
@@ -435,6 +435,30 @@ eea_status eea_frontier_auction(int device, const eea_collision_cfg* cfg, const 
     EEA_HIP(eea::launch_auction_settle(c, a, round, d_pose, d_goal_region, d_goal_cell, d_goal_cost, d_path, d_len, d_ws, d_state, s));
   }
   if (max_rounds == 0u) EEA_HIP(hipStreamSynchronize(s));
+  return EEA_OK;
+}
+
+// ---- goal paths: every robot's way to its own goal, one LDS window each (goto_kernel.hip) ----
+eea_status eea_geodesic_goto_batch(int device, const eea_collision_cfg* cfg, const int8_t* d_grid, const int* d_sq, int clear_sq,
+                                   unsigned flags, const double* d_pose, const int* d_goal, const int* d_mask, unsigned P,
+                                   unsigned margin, unsigned n_steps, int* d_cost, int* d_status, double* d_path, int* d_len,
+                                   unsigned* d_state, void* stream)
+{
+  const eea_status st = geodesic_cfg_refusal(cfg);
+  if (st != EEA_OK) return st;
+  if (d_grid == nullptr || d_cost == nullptr || d_status == nullptr || d_state == nullptr) {
+    return fail(EEA_ERR_INVALID_ARGUMENT, "null argument");
+  }
+  if ((d_pose == nullptr || d_goal == nullptr) && P != 0u) return fail(EEA_ERR_INVALID_ARGUMENT, "d_pose or d_goal is null with P > 0");
+  if (d_path == nullptr && n_steps != 0u) return fail(EEA_ERR_INVALID_ARGUMENT, "d_path is null with n_steps > 0");
+  if ((flags & ~static_cast<unsigned>(EEA_GEODESIC_UNKNOWN_BLOCKS)) != 0u) return fail(EEA_ERR_INVALID_ARGUMENT, "unknown flag bits");
+  if (clear_sq < 0) return fail(EEA_ERR_INVALID_ARGUMENT, "clear_sq must be >= 0");
+  if (P > 0x7fffffffu) return fail(EEA_ERR_UNSUPPORTED, "more than 2^31 - 1 robots");
+  const eea::CollisionParams c = grid_params(cfg);
+  const eea::GotoArgs a{ eea::GeodesicArgs{ clear_sq, (flags & EEA_GEODESIC_UNKNOWN_BLOCKS) != 0u, false, P, 0u }, P, margin, n_steps };
+  EEA_HIP(hipSetDevice(device));
+  EEA_HIP(eea::launch_goto(c, a, d_grid, d_sq, d_pose, d_goal, d_mask, d_cost, d_status, d_path, d_len, d_state,
+                           static_cast<hipStream_t>(stream)));
   return EEA_OK;
 }
 

@@ -1338,6 +1338,60 @@ eea_status eea_frontier_auction(int device, const eea_collision_cfg* cfg, const 
                                 unsigned n_steps, int* d_goal_region, int* d_goal_cell, int* d_goal_cost, double* d_path,
                                 int* d_len, void* d_ws, unsigned* d_state, void* stream);
 
+/* ---- goal paths: every robot's way to its OWN goal, one bounded window each (additive to ABI 6: detect this entry by
+ * symbol) -----------------------------------------------------------------------------------------------------------------
+ * No reference counterpart.  eea_geodesic_path_batch walks to the nearest source of ONE field, eea_partition_path_batch to a goal
+ * inside the robot's own cell of the partition, eea_frontier_auction to the region it has just assigned.  A goal from anywhere
+ * else -- the one a robot was given last tick, an operator's way-point, a rendezvous cell -- had one whole-grid
+ * eea_geodesic_field per distinct goal as its only route to a path.  Here every robot's shortest path is computed inside a
+ * bounded window around the robot and its goal: the work follows the distance to the goal, not the size of the map.  The result
+ * is a function of the inputs alone: integers with a unique answer, way-points from the literal arithmetic of
+ * eea_geodesic_path_batch.  Bit-reproducible.
+ * eea_geodesic_goto_batch: d_grid, d_sq, clear_sq, blocks(v), the cell of a pose with gridBounds, traversable and the 5-7 moves
+ *   without corner cutting are eea_geodesic_field's; flags takes only EEA_GEODESIC_UNKNOWN_BLOCKS.  Per robot q of d_pose [P][3]
+ *   with d_mask == NULL || d_mask[q] != 0 (d_mask: int32 [P]), decided in this order:
+ *   1 robot cell  c_q = (i_c, j_c): the cell of pose q.  Off the grid, or blocks(d_grid[c_q]): status EEA_GOTO_NO_ROBOT.
+ *   2 goal        g = d_goal[q] (int32, a row-major index), (i_g, j_g) its row and column.  g < 0, g >= xsize * ysize or
+ *                 blocks(d_grid[g]): status EEA_GOTO_NO_GOAL.
+ *   3 window      rows [min(i_c, i_g) - margin, max(i_c, i_g) + margin] and columns [min(j_c, j_g) - margin, max(j_c, j_g) +
+ *                 margin], computed in 64 bits, then clipped to the grid: h rows, w columns.  h * w > EEA_GOTO_MAX_CELLS:
+ *                 status EEA_GOTO_WINDOW.
+ *   4 field       the unique fixed point of eea_geodesic_field's rule on the cells of the window only -- a move never leaves
+ *                 the window --, its one source g seeded with 0.  The unknown test and the clearance test are waived for g, as
+ *                 for any source (nothing moves into a g that is not traversable), and c_q is enterable whatever those tests
+ *                 say, as it is in eea_frontier_auction (a robot is where it is).
+ *   5             c_q has no cost: status EEA_GOTO_CUT_OFF (inside THIS window: a larger margin may find a way).
+ *   6             otherwise status EEA_GOTO_OK.
+ *   An OK robot gets d_cost[q] = the cost at c_q and the forward walk from c_q down the field by eea_geodesic_path_batch's step
+ *   rule: the eight moves tried in its order, the first whose target accounts for the cost taken, a diagonal one only between
+ *   two cells that have a cost; way-point centres (on the whole grid's indices), the eight literal headings and the repeat rule
+ *   are eea_geodesic_path_batch's.  len = the number of moves written, <= n_steps; the cost is the whole path's even when n_steps
+ *   is shorter.  A robot on its goal gets cost 0, len 0 and n_steps rows of its cell's centre with the pose's heading.  Every
+ *   other status gives cost = len = -1 and the pose in all rows.  EVERY element of d_cost, d_status, d_len [P] (int32) and d_path
+ *   [P][n_steps][3] that belongs to a robot that is not masked out is overwritten; of a masked-out robot nothing is read and
+ *   nothing written.  n_steps == 0 is allowed with d_path == NULL; d_len may be NULL.
+ *   d_state       (uint32 [4], device) is overwritten with four counts over the robots that are not masked out: [0] OK, [1]
+ *                 WINDOW, [2] CUT_OFF, [3] NO_ROBOT + NO_GOAL.
+ *   The caller falls back to the whole-grid field for a robot with status WINDOW or CUT_OFF; the cost of an OK robot is that of
+ *   the best path INSIDE the window, which is the whole grid's once the window holds such a path (it does not rise with margin).
+ *   The launches: one lane group clears d_state; then one workgroup of 256 threads per robot (a launch of at most 2048
+ *   workgroups strides over the robots) stages the window in LDS -- one 32-bit word per cell, a cost or "no move may enter",
+ *   EEA_GOTO_MAX_CELLS of them being 64 KB, so that two workgroups share a CU --, relaxes it in place to its fixed point with one workgroup-wide OR
+ *   per sweep, walks, and writes the rows; the counts are integer atomics, combined per workgroup first.  A value that cannot
+ *   lie on the robot's walk (>= the cost its own cell holds) is not stored.  No workspace, no allocation, nothing read on the
+ *   host, no synchronising call, nothing waits inside the kernel: asynchronous on `stream`.
+ *   P == 0 is EEA_OK: it writes d_state = {0, 0, 0, 0} and nothing else.
+ *   Before the device is selected, with no output touched -- EEA_ERR_INVALID_ARGUMENT: cfg, d_grid, d_cost, d_status or d_state
+ *   null; d_pose or d_goal null with P > 0; d_path null with n_steps > 0; clear_sq < 0; unknown flag bits; the configuration
+ *   errors of the geodesic calls.  EEA_ERR_UNSUPPORTED: their limits; P > 2^31 - 1.
+ * eea_abi_version() stays 6. */
+#define EEA_GOTO_MAX_CELLS 16384 /* a window's cells: one 4-byte word of LDS each, 64 KB */
+enum { EEA_GOTO_OK = 0, EEA_GOTO_NO_ROBOT = 1, EEA_GOTO_NO_GOAL = 2, EEA_GOTO_WINDOW = 3, EEA_GOTO_CUT_OFF = 4 };
+eea_status eea_geodesic_goto_batch(int device, const eea_collision_cfg* cfg, const int8_t* d_grid, const int* d_sq,
+                                   int clear_sq, unsigned flags, const double* d_pose, const int* d_goal,
+                                   const int* d_mask, unsigned P, unsigned margin, unsigned n_steps, int* d_cost,
+                                   int* d_status, double* d_path, int* d_len, unsigned* d_state, void* stream);
+
 /* ---- footprint collision: a convex polygon base, checked through the distance field ----------------------------------
  * No reference counterpart (the reference README lists "model the robot's base as a polygon for collision detection" and "use
  * a distance field for detecting obstacle cells" under "Future Improvements").  Every other collision call treats the robot
